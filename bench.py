@@ -23,7 +23,17 @@ GPU); under torch.distributed.run the ranks come from the environment.  The only
 are the barriers around the timed region, the max over ranks of its duration and a gather of
 the per-rank durations (rank_seconds).
 
-Also reported:
+A plain run sets up, warms up (--warmup steps, then as many more untimed steps as the --full
+survey takes, so both start timing in the same clock state), times --steps steps and prints
+the result line (metric, value, unit, ms_per_step, config, rank_seconds); nothing else runs.
+--dump-outputs DIR then also writes what the last timed step returned (rank 0: keypoints,
+descriptors, counts, vnMatches12, match counts; see dump_outputs) as DIR/<name>.npy.  The
+frames are a pure function of the arguments, so two builds run with the same arguments can be
+compared output for output.
+
+Also measured and reported with --full:
+  stages        per-stage times from an untimed survey pass with every stage bracketed by HIP
+                events, and workload_stats (keypoints per frame, matches per pair)
   roofline      dominant kernel: SURVEY.md §8d algorithmic bytes of its stage per launch / mean
                 launch duration, from HIP events recorded around that stage on its launch stream
                 inside the timed region; traffic = PMC-measured HBM bytes per launch of the same
@@ -224,6 +234,56 @@ def cpu_baseline(frames, nfeatures, threads, W, H, quota_threads=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step returned, as float32 .npy files
+# ---------------------------------------------------------------------------------------------
+DUMP_BYTES = 48 << 20  # budget of the sampled arrays (the unsampled ones are a few KB)
+KP_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")
+
+
+def keypoint_table(k):
+    """KEYPOINT_DTYPE records -> float32 (..., 7) in KP_FIELDS order (octave and class_id are small
+    integers: exact in float32)."""
+    return np.stack([k[f].astype(np.float32) for f in KP_FIELDS], axis=-1)
+
+
+def dump_outputs(dirname, d_f1, d_kps, d_desc, d_cnt, d_m12, d_nm):
+    """Write one step's outputs (extract_batch_device's keypoint records, descriptors and counts;
+    search_for_initialization_batch_device's vnMatches12 rows and match counts for the pairs
+    whose first frames are `d_f1`) as `dirname`/<name>.npy, all float32.  counts (B,) and
+    nmatches (P,) are whole.  The per-keypoint arrays cover a fixed sample (seed 0, as many as
+    fit DUMP_BYTES) of the frames (`frames`: their batch indices; keypoints (S, cap, 7) in
+    KP_FIELDS order, descriptors (S, cap, 32) byte values) and of the pairs (`pairs`; matches12
+    (S, cap): index of the matched keypoint of the second frame, or -1).  Slots past a frame's
+    count hold no output and are written as 0 (matches12: -1)."""
+    import torch
+
+    from orbslam_jpminipc_amd._native import KEYPOINT_DTYPE
+
+    os.makedirs(dirname, exist_ok=True)
+    B, cap = int(d_kps.shape[0]), int(d_kps.shape[1])
+    P = int(d_m12.shape[0])
+    cnt = d_cnt.cpu().numpy()
+    n_max = max(1, DUMP_BYTES // (cap * (len(KP_FIELDS) + 32 + 1) * 4))
+    rng = np.random.default_rng(0)
+    frames = np.sort(rng.choice(B, min(B, n_max), replace=False))
+    pairs = np.sort(rng.choice(P, min(P, n_max), replace=False))
+    fi = torch.from_numpy(frames).to(d_kps.device)
+    pi = torch.from_numpy(pairs).to(d_kps.device)
+    slot = np.arange(cap)[None, :]
+    live = (slot < cnt[frames][:, None])[..., None]
+    kps = keypoint_table(d_kps[fi].cpu().numpy().view(KEYPOINT_DTYPE)[..., 0])
+    desc = d_desc[fi].cpu().numpy()
+    live12 = slot < cnt[d_f1.cpu().numpy()[pairs]][:, None]  # row p runs over the keypoints of pair p's first frame
+    out = {
+        "counts": cnt, "nmatches": d_nm.cpu().numpy(), "frames": frames, "pairs": pairs,
+        "keypoints": np.where(live, kps, 0), "descriptors": np.where(live, desc, 0),
+        "matches12": np.where(live12, d_m12[pi].cpu().numpy(), -1),
+    }
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+# ---------------------------------------------------------------------------------------------
 # launcher: N rank processes, spawned before anything touches a GPU
 # ---------------------------------------------------------------------------------------------
 def _free_port():
@@ -293,12 +353,18 @@ def run_dry(args):
     t0 = time.perf_counter()
     n = 0
     for _ in range(args.steps):
-        for f in frames:
-            n += len(ora.extract(f)[0])
+        outs = [ora.extract(f) for f in frames]
+        n += sum(len(k) for k, _ in outs)
     dt = time.perf_counter() - t0
     replicas.barrier(info)
     tmax = replicas.max_over_ranks(dt, info)
     ranks = replicas.gather_over_ranks(dt, info)
+    if args.dump_outputs and info.rank == 0:  # the last step's keypoints and descriptors, frame after frame
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("counts", [len(k) for k, _ in outs]),
+                        ("keypoints", np.concatenate([keypoint_table(k) for k, _ in outs])),
+                        ("descriptors", np.concatenate([d for _, d in outs]))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float32))
     if info.rank == 0:
         print(json.dumps({"metric": METRIC, "value": replicas.whole_job_rate(B * args.steps, info.world, tmax),
                           "unit": "frames/s", "n_gpus": info.world, "steps": args.steps, "warmup": args.warmup,
@@ -681,6 +747,8 @@ def run_rank(args):
         if timed:
             b.record(stream)
             ev_m.append((a, b))
+        if args.dump_outputs:
+            st["out"] = (kps, desc, cnt, m12, nm)  # what a caller of the step receives
         return nm
 
     def step(timed=False):
@@ -738,25 +806,77 @@ def run_rank(args):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # stage survey (untimed, serial): an event pair around every stage gives the per-stage
-    # table; each pair is a stream boundary (~10 us), so the timed run below brackets only the
-    # dominant stage
-    ext.profile_enable(True)
-    for _ in range(args.survey_steps):
-        step(timed=True)
-    torch.cuda.synchronize()
-    survey = ext.profile_read()
-    ext.profile_enable(False)
-    survey["k_match_init"] = (sum(a.elapsed_time(b) for a, b in ev_m), len(ev_m))
-    ev_m.clear()
-    dom = max(survey, key=lambda k: survey[k][0])
-    time_match = dom == "k_match_init"
-    if args.overlap:  # the serial step, for reference (no events)
-        serial_elapsed, _ = timed_run(False, False)
-        serial_tmax = replicas.max_over_ranks(serial_elapsed, info)
-    if not time_match:
-        ext.profile_enable_stages([dom])
+    dom, time_match = None, False
+    if args.full:
+        # stage survey (untimed, serial): an event pair around every stage gives the per-stage
+        # table; each pair is a stream boundary (~10 us), so the timed run below brackets only
+        # the dominant stage
+        ext.profile_enable(True)
+        for _ in range(args.survey_steps):
+            step(timed=True)
+        torch.cuda.synchronize()
+        survey = ext.profile_read()
+        ext.profile_enable(False)
+        survey["k_match_init"] = (sum(a.elapsed_time(b) for a, b in ev_m), len(ev_m))
+        ev_m.clear()
+        dom = max(survey, key=lambda k: survey[k][0])
+        time_match = dom == "k_match_init"
+        if args.overlap:  # the serial step, for reference (no events)
+            serial_elapsed, _ = timed_run(False, False)
+            serial_tmax = replicas.max_over_ranks(serial_elapsed, info)
+        if not time_match:
+            ext.profile_enable_stages([dom])
+    else:
+        # the survey's steps without its events: the clocks still ramp over the first steps, so
+        # the timed region starts after as many steps as it does under --full
+        for _ in range(args.survey_steps):
+            step()
+        torch.cuda.synchronize()
     elapsed, nm = timed_run(args.overlap, time_match)
+    tmax = replicas.max_over_ranks(elapsed, info)
+    rank_seconds = replicas.gather_over_ranks(elapsed, info)
+    per_step_s = tmax / args.steps
+    frames_job = per * wl["streams"] if wl["streams"] else B * world  # every rank's frames of one step
+    value = frames_job * args.steps / tmax
+    label = wl["label"] if not custom else f"custom {W}x{H}, ORBextractor({NF},1.2,8,FAST,20) + SearchForInitialization"
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": per_step_s * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if wl["streams"] else "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (csrc/synth.c: rectangles+discs+noise, consecutive frames of a stream shifted)",
+        "config": {
+            "workload": label,
+            "preset": args.workload,
+            "width": W, "height": H, "nfeatures": NF,
+            "batch_per_gpu": B,
+            "pairs_per_gpu": P,
+            "streams_of_rank0": my_streams,
+            "parallelism": f"replicas x{world} (no collectives)",
+            "control_backend": backend if world > 1 else None,
+            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+            "streams": {0: "one stream, extract then match",
+                        1: "extract(t) || SearchForInitialization(t-1), double-buffered",
+                        2: "pyramid(t) || SearchForInitialization(t-1), then the rest of extract(t)"}
+                       [args.overlap],
+        },
+        "rank_seconds": rank_seconds,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f1, *st["out"])
+    if not args.full:  # the plain run ends here: the headline figure and nothing else
+        if rank == 0:
+            print(json.dumps(result))
+        replicas.shutdown(info)
+        return 0
+
     if time_match:
         live = (sum(a.elapsed_time(b) for a, b in ev_m), len(ev_m))
     else:
@@ -764,9 +884,6 @@ def run_rank(args):
         ext.profile_enable(False)
     prof = dict(survey)
     prof[dom] = live  # the dominant stage: measured inside the timed region
-
-    tmax = replicas.max_over_ranks(elapsed, info)
-    rank_seconds = replicas.gather_over_ranks(elapsed, info)
 
     # workload statistics of the last step (identical every step: same frames)
     cnt = d_cnt.cpu().numpy().astype(np.int64)
@@ -812,11 +929,7 @@ def run_rank(args):
         s["GBps"] = s["bytes_per_launch"] / (s["ms_per_launch"] * 1e-3) / 1e9
         s["note"] = "per pyramid level (levels 1-7; the small levels share one k_pyr_resize_tail launch)"
     ds = stages[dom]
-    per_step_s = tmax / args.steps
-    frames_job = per * wl["streams"] if wl["streams"] else B * world  # every rank's frames of one step
-
-    value = frames_job * args.steps / tmax
-    traffic, traffic_src, pmc = pmc_traffic(dom, args.workload, W, H, B, NF)
+    traffic,traffic_src, pmc = pmc_traffic(dom, args.workload, W, H, B, NF)
     pmc = pmc or {}
     valu_insts = pmc.get("SQ_INSTS_VALU")
     # VALU issue ceiling: each SIMD issues one wave64 VALU instruction per 2 cycles
@@ -846,36 +959,7 @@ def run_rank(args):
     if traffic:
         roofs["hbm_measured_traffic"] = traffic / launch_s / 1e9 / HBM_PEAK_GBS
     binding = max(roofs, key=roofs.get) if roofs else None
-    label = wl["label"] if not custom else f"custom {W}x{H}, ORBextractor({NF},1.2,8,FAST,20) + SearchForInitialization"
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": per_step_s * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if wl["streams"] else "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (csrc/synth.c: rectangles+discs+noise, consecutive frames of a stream shifted)",
-        "config": {
-            "workload": label,
-            "preset": args.workload,
-            "width": W, "height": H, "nfeatures": NF,
-            "batch_per_gpu": B,
-            "pairs_per_gpu": P,
-            "streams_of_rank0": my_streams,
-            "parallelism": f"replicas x{world} (no collectives)",
-            "control_backend": backend if world > 1 else None,
-            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-            "streams": {0: "one stream, extract then match",
-                        1: "extract(t) || SearchForInitialization(t-1), double-buffered",
-                        2: "pyramid(t) || SearchForInitialization(t-1), then the rest of extract(t)"}
-                       [args.overlap],
-        },
-        "rank_seconds": rank_seconds,
+    result.update({
         "roofline": {
             "kernel": dom,
             "bound": "hbm",
@@ -918,7 +1002,7 @@ def run_rank(args):
         "stages": stages,
         "workload_stats": {"keypoints_per_frame": n_kp / B, "octave0_per_frame": float(oct0.mean()),
                            "matches_per_pair": float(nm_h.mean())},
-    }
+    })
     if args.overlap:
         result["serial_step"] = {"value": frames_job * args.steps / serial_tmax,
                                  "ms_per_step": serial_tmax / args.steps * 1e3}
@@ -1013,9 +1097,14 @@ def main():
                     help="1: measure the BoW leg (vocabulary transform + batched SearchByBoW; rank 0, N = 1)")
     ap.add_argument("--overlap", type=int, default=0,
                     help="0 (default): serial step; 1 / 2: stream-overlap experiments, measured slower")
-    ap.add_argument("--survey-steps", type=int, default=5, help="untimed steps with every stage bracketed")
+    ap.add_argument("--survey-steps", type=int, default=5, help="untimed steps after the warm-up (--full: with every stage bracketed)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU of the affinity set")
     ap.add_argument("--dry-run", action="store_true", help="CPU only: launcher + rank plumbing with the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline figure: the stage survey and "
+                         "rooflines, workload statistics, and the host-fed, BoW, latency and CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last one as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     args.survey_steps = max(1, args.survey_steps)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:

@@ -16,7 +16,7 @@ timeout -k 10 900 python -u -m pytest tests -q -m gpu --maxfail=5 --timeout 180 
 rc=$?; tail -15 $OUT/pytest_gpu.log >> $OUT/summary.txt; step pytest_gpu $rc
 timeout -k 10 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
 step smoke $?
-timeout -k 10 600 python bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 step bench $?
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --cpu-frames 0 --latency 0 --host-fed 0 "$@" > $OUT/prof.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full --cpu-frames 0 --latency 0 --host-fed 0 "$@" > $OUT/prof.log 2>&1
 step rocprof $?

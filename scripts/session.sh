@@ -9,8 +9,8 @@
 #   gpu:EXPR             the -m gpu tests selected by -k EXPR (e.g. gpu:desc-or-extract, '-' = ' ')
 #   smoke                __graft_entry__.smoke()
 #   diag[:REPS]          k_orient_desc determinism screen of the in-tree library (scripts/od_diag.py)
-#   bench:WL[:ARGS]      bench.py --workload WL (default legs), ARGS comma-separated extra flags
-#   quick:WL[:ARGS]      bench.py --workload WL without the CPU / latency / host-fed / BoW legs
+#   bench:WL[:ARGS]      bench.py --full --workload WL (every leg), ARGS comma-separated extra flags
+#   quick:WL[:ARGS]      bench.py --workload WL, the plain run: the timed steps and the headline figure only
 #   prof:WL              rocprofv3 --kernel-trace --stats of quick:WL -> prof_WL/
 #   pmc:WL               the PMC passes of scripts/pmc_pass.sh for WL + pmc_summary -> pmc_WL.json
 #   ab:WL:V1,V2,..       per-kernel rocprofv3 means of the in-tree library and build/variants/V*.so
@@ -37,7 +37,6 @@ wl_args() {  # workload -> stage_times.py shape flags
         c5) echo "--batch 512 --width 1280 --height 720 --nfeatures 2500" ;;
     esac
 }
-QUICK="--cpu-frames 0 --latency 0 --host-fed 0 --bow 0"
 for S in "$@"; do
     IFS=: read -r kind a b <<< "$S"
     case "$kind" in
@@ -53,13 +52,13 @@ for S in "$@"; do
         REPS=${a:-10} timeout -k 10 600 python scripts/od_diag.py 640 480 2000 "${a:-10}" > "$OUT/diag.txt" 2>&1
         rc=$?; grep -v amdgpu.ids "$OUT/diag.txt" | tail -1 | tee -a "$OUT/summary.txt"; fin diag $rc fatal ;;
     bench|quick)
-        extra=${b//,/ }; [ "$kind" = quick ] && extra="$QUICK $extra"
+        extra=${b//,/ }; [ "$kind" = bench ] && extra="--full $extra"
         timeout -k 10 900 python bench.py --workload "$a" $extra > "$OUT/${kind}_$a.json" 2> "$OUT/${kind}_$a.err"
         rc=$?; python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['value']), round(d['ms_per_step'], 4))" "$OUT/${kind}_$a.json" "$S" 2>/dev/null | tee -a "$OUT/summary.txt"
         fin "$S" $rc fatal ;;
     prof)
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$a" -o run --output-format csv -- \
-            python bench.py --workload "$a" $QUICK --steps 20 > "$OUT/prof_$a.log" 2>&1
+            python bench.py --workload "$a" --steps 20 > "$OUT/prof_$a.log" 2>&1
         rc=$?; fin "$S" $rc fatal
         f=$(find "$OUT/prof_$a" -name '*kernel_stats.csv' | head -1); cp "$f" "$OUT/kernel_stats_$a.csv"
         python3 - "$f" <<'PY' | tee -a "$OUT/summary.txt"
@@ -94,7 +93,7 @@ PY
             for v in intree ${b//,/ }; do
                 lib=""; [ "$v" = intree ] || lib=$PWD/build/variants/$v.so
                 f=$OUT/abbench_${a}_${v}_$rep.json
-                ORB_HIP_LIB=$lib timeout -k 10 600 python bench.py --workload "$a" $QUICK --steps 50 > "$f" 2> "${f%.json}.err"
+                ORB_HIP_LIB=$lib timeout -k 10 600 python bench.py --workload "$a" --steps 50 > "$f" 2> "${f%.json}.err"
                 rc=$?; [ $rc -eq 0 ] || fin "abbench $a $v" $rc fatal
                 python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('abbench', sys.argv[2], round(d['value']), round(d['ms_per_step'], 4))" "$f" "$a $rep $v" | tee -a "$OUT/summary.txt"
             done

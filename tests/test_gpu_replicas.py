@@ -21,7 +21,7 @@ def _bench(*args):
     env.pop("WORLD_SIZE", None)
     env.pop("ORB_BENCH_BACKEND", None)  # the default control plane
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--survey-steps", "1", "--cpu-frames", "0", "--latency", "0", "--host-fed", "0", *args],
+                        "--full", "--survey-steps", "1", "--cpu-frames", "0", "--latency", "0", "--host-fed", "0", *args],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads(r.stdout.strip().splitlines()[-1])

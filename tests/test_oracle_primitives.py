@@ -72,10 +72,10 @@ def test_nth_element_replay_matches_libstdcxx():
         assert np.array_equal(a & 0xFFFFFF, idx.astype(np.uint32)), trial
 
 
-def test_nth_element_native_check():
+def test_nth_element_native_check(tmp_path):
     """Compile and run tests/native/nth_check.cpp: orbsel:: vs libstdc++ including the
     depth-limited __heap_select branch."""
-    exe = pathlib.Path("/tmp/orb_nth_check")
+    exe = tmp_path / "orb_nth_check"
     subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), str(ROOT / "tests/native/nth_check.cpp")],
                    check=True)
     r = subprocess.run([str(exe), "5000"], capture_output=True, text=True)
