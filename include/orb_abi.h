@@ -252,6 +252,11 @@ int orb_search_by_bow_kf_kf(const orb_frame_view_t* KF1, const uint8_t* usable1,
  * d_usable [B][cap]: the frame's keypoint has a MapPoint that is not bad (both sides for kf_kf =
  * 1, the KF side for kf_kf = 0); NULL = every keypoint.  d_match rows are written whole (-1 past
  * the count); d_nmatches[p] = the reference's return value.  cap <= 8192, d_desc 16-B aligned.
+ * Each feature of a frame must appear in exactly one node of its FeatureVector, as
+ * orb_vocabulary_transform_batch_device produces it: the nodes of a pair are resolved
+ * independently of each other (one wave each), which is the reference's node-by-node loop only
+ * while no two nodes share a keypoint.  The host entry points (orb_search_by_bow_kf_f / _kf_kf)
+ * check this and route a vector that lists a feature twice to the generic sequential resolver.
  * Asynchronous on `stream`. */
 int orb_search_by_bow_batch_device(int kf_kf, const orb_keypoint_t* d_kps, const uint8_t* d_desc,
                                    const int32_t* d_counts, int cap, const uint32_t* d_fv_nodes,

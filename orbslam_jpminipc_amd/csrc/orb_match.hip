@@ -1882,7 +1882,7 @@ int grid_match(Job J, const orb_frame_view_t* T, const uint8_t* taken, const Gri
     int nm = 0;
     if ((st = C.download(out, jo.out, (size_t)outN * 4)) || (st = C.download(&nm, jo.nOut, 4)) || (st = C.sync()))
         return st;
-    if (nm < 0) return fail(ORB_EDEVICE, "local-map resolver did not converge");
+    if (nm < 0) return fail(ORB_EDEVICE, "fixed-point resolver did not converge (grid matcher)");
     *n_out = nm;
     return ORB_OK;
 }

@@ -4,14 +4,17 @@ and 715-850): match arrays and counts identical, pair by pair, bit for bit.
 
 Cases: the synthetic scenes of test_gpu_matcher_family (many pairs in one launch, usable flags,
 both nnratios / checkOri), nodes with more than 64 candidates (the strided path) and heavy
-contention, empty frames, and the real chain extract -> vocabulary transform -> BoW match on
-device-resident 640x480 frames (Frame::ComputeBoW, Tracking.cc:927)."""
+contention, empty frames, the real chain extract -> vocabulary transform -> BoW match on
+device-resident 640x480 frames (Frame::ComputeBoW, Tracking.cc:927), and the constructed scenes
+of tests/adversarial_scenes.py: a node for every size around the kernel's path switches and
+dependency chains inside a node, checked against the expectation known by construction too."""
 import numpy as np
 import pytest
 
 import orbslam_jpminipc_amd as orb
 from orbslam_jpminipc_amd.views import FeatureVector, View
 from oracle_lib import OracleMatcher
+import adversarial_scenes as A
 import scenes as S
 from vocab_util import random_vocabulary
 
@@ -64,7 +67,9 @@ def _pack(views, fvs, usable=None):
     return t(kps), t(desc), t(cnt), fv, t(us)
 
 
-def _run(kf_kf, nn, co, views, fvs, usable, pairs):
+def _run(kf_kf, nn, co, views, fvs, usable, pairs, expect=None):
+    """One launch over `pairs`, every pair checked against the oracle (and against expect[p],
+    the match array known by construction, where given).  Returns the total match count."""
     import torch
 
     d_kps, d_desc, d_cnt, fv, d_us = _pack(views, fvs, usable)
@@ -88,6 +93,9 @@ def _run(kf_kf, nn, co, views, fvs, usable, pairs):
         assert n[p] == no, (p, n[p], no)
         np.testing.assert_array_equal(m[p, :rows], mo)
         assert (m[p, rows:] == -1).all()
+        if expect is not None and p in expect:
+            np.testing.assert_array_equal(m[p, :rows], expect[p])
+            assert n[p] == (expect[p] >= 0).sum()
         total += no
     return total
 
@@ -177,3 +185,66 @@ def test_extract_transform_match_chain():
                 rows = cnt[p + 1]
             assert n[p] == no and no > 50, (p, n[p], no)
             np.testing.assert_array_equal(m[p, :rows], mo)
+
+
+SWEEPS = {"unstaged": ((1, 2, 15, 16, 17, 63, 64, 65, 130), (1, 3, 4, 5, 63, 64, 65, 67, 130)),
+          "staged": ((1, 15, 16, 17, 64, 65), (1, 4, 5, 64, 65, 67))}
+
+
+def _sweep_expect(kf_kf, nn, co, Q, uq, fvq, T, ut, fvt):
+    """The plain loop over the nodes (A.bow_loop), then the rotation filter."""
+    _, by_t, by_q = A.bow_loop(kf_kf, nn, Q, uq, fvq, T, ut, fvt)
+    if not co:
+        return by_q if kf_kf else by_t
+    if kf_kf:
+        return A.apply_rot_filter(by_q, lambda p, v: p, lambda p, v: v, Q, T)[1]
+    return A.apply_rot_filter(by_t, lambda p, v: v, lambda p, v: p, Q, T)[1]
+
+
+@pytest.mark.parametrize("which", list(SWEEPS))
+@pytest.mark.parametrize("kf_kf", [False, True])
+def test_node_size_sweep(kf_kf, which):
+    """A node for every (candidates, queries) combination around k_bow_pairs' path switches
+    (16 / 17 candidates: four speculated queries per step against one query per step; 64 / 65:
+    a candidate per lane against the strided scan with taken flags in LDS) and around the
+    64-query reloads (63 .. 67 queries, misaligned by the short steps of the four-per-step
+    path), in the unstaged template (3 618 features per frame) and the staged one (<= 1 800).
+    Queries chain on their predecessors' candidates, one node in seven repeats a candidate
+    (equal distances), every third query and fifth target is unusable; nnratio 1.25 lets a tie
+    of best and second through, so the first-in-candidate-order rule shows.  The same two
+    frames serve several pairs of the launch, forward and reversed."""
+    Sw = A.node_sweep(np.random.default_rng([12, len(SWEEPS[which][0])]), *SWEEPS[which])
+    assert (max(Sw.Q.n, Sw.T.n) <= 1800) == (which == "staged")
+    views, fvs = [Sw.Q, Sw.T], [Sw.fvq, Sw.fvt]
+    pairs = [(0, 1), (1, 0), (0, 1), (1, 0), (0, 1)]
+    for nn, co in ((0.75, False), (0.9, True), (1.25, False)):
+        for usable in ([Sw.uq, Sw.ut], None):
+            uq, ut = usable if usable else (None, None)
+            fwd = _sweep_expect(kf_kf, nn, co, Sw.Q, uq, Sw.fvq, Sw.T, ut, Sw.fvt)
+            rev = _sweep_expect(kf_kf, nn, co, Sw.T, ut, Sw.fvt, Sw.Q, uq, Sw.fvq)
+            total = _run(kf_kf, nn, co, views, fvs, usable, pairs, {0: fwd, 1: rev, 2: fwd, 3: rev, 4: fwd})
+            assert total > 5 * (Sw.Q.n // 10)
+
+
+@pytest.mark.parametrize("kf_kf", [False, True])
+def test_chains_inside_nodes(kf_kf):
+    """A kind-A chain (A.chain_scene: link q matches only once link q-1 holds its target) of 16
+    links in a 16-candidate node and of 64 in a 64-candidate node, after 0, 3 and 7 unusable
+    filler queries (every alignment of the four-query steps), unbroken (all match), without its
+    head (nothing matches) and broken in the middle (nothing after the break matches)."""
+    views, fvs, usable, pairs, expect, expect_ori = [], [], [], [], {}, {}
+    for n in (16, 64):
+        for lead, broken in ((0, None), (3, None), (7, None), (3, 0), (7, n // 2 + 3)):
+            C = A.chain_scene(np.random.default_rng([13, n, lead, 999 if broken is None else broken]), n, "A", "short",
+                              lead, broken)
+            fq, ft = A.chain_bow(C)
+            p = len(pairs)
+            pairs.append((len(views), len(views) + 1))
+            views += [C.Q, C.T]
+            fvs += [fq, ft]
+            usable += [C.usable, np.ones(C.T.n, np.uint8)]
+            expect[p] = C.by_query(False) if kf_kf else C.by_target
+            expect_ori[p] = C.by_query(True) if kf_kf else C.by_target_ori
+    for nn in (0.9, 0.75):
+        assert _run(kf_kf, nn, False, views, fvs, usable, pairs, expect) == 3 * (16 + 64) + 11 + 35
+        assert _run(kf_kf, nn, True, views, fvs, usable, pairs, expect_ori) > 100
