@@ -481,6 +481,88 @@ int orb_vocabulary_transform(orb_vocabulary_t* v, const uint8_t* desc, int n, in
                              double* bow_values, int* bow_n, uint32_t* fv_nodes, int32_t* fv_offsets,
                              int32_t* fv_features, int* fv_n);
 
+/* ---- BoW score and KeyFrameDatabase (GPU: csrc/orb_kfdb.hip) ------------------------ */
+/* Only L1_NORM vocabularies (ORBvoc is one) are supported: every entry point of this section
+ * returns ORB_EINVAL, with orb_last_error naming the scoring type, for a vocabulary of another
+ * scoring (orb_kfdb_create refuses it, so no database handle of one exists).  DESIGN.md §8.
+ *
+ * TemplatedVocabulary::score = L1Scoring::score (ScoringObject.cpp:23-68) of two BowVectors
+ * (words ascending): score += fabs(vi - wi) - fabs(vi) - fabs(wi) over the shared words in
+ * ascending word order, in double, then -score / 2.  Host buffers, synchronous (computed on the
+ * host). */
+int orb_vocabulary_score(const orb_vocabulary_t* v, const uint32_t* words1, const double* values1, int n1,
+                         const uint32_t* words2, const double* values2, int n2, double* score);
+/* The same for P pairs of frames laid out as orb_vocabulary_transform_batch_device writes
+ * BowVectors (frame f: d_bow_words / d_bow_values + f * cap, d_bow_n[f] entries):
+ * d_score[p] = score(frame d_pair_a[p], frame d_pair_b[p]), the loop of LoopClosing.cc:138-150.
+ * The pair indices are the caller's to keep in range.  Every double equals the sequential sum
+ * bit for bit.  cap <= 8192.  Asynchronous on `stream`. */
+int orb_vocabulary_score_pairs_device(const orb_vocabulary_t* v, int P, const uint32_t* d_bow_words,
+                                      const double* d_bow_values, const int32_t* d_bow_n, int cap,
+                                      const int32_t* d_pair_a, const int32_t* d_pair_b, double* d_score, void* stream);
+
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc): the keyframes' BowVectors on one device and the
+ * two candidate queries.  Keyframe ids are dense integers 0 <= id < max_keyframes chosen by the
+ * caller (id = slot; the wrappers map arbitrary ids).  max_keyframes <= 65536; max_entries bounds
+ * the (word, value) entries of all live keyframes together.  A handle is serialised: one call at
+ * a time.  Host entry points run on the handle's own stream and return when done; a device entry
+ * point enqueues on the caller's stream (the default stream included) and records an event
+ * there, and the next call on the handle, whichever stream it uses, is ordered after that event:
+ * a host call waits for it, a device call makes its stream wait.  The caller's stream may be
+ * destroyed once the call has returned. */
+typedef struct orb_keyframe_db orb_keyframe_db_t; /* opaque handle */
+int orb_kfdb_create(const orb_vocabulary_t* voc, int max_keyframes, int64_t max_entries, int device,
+                    orb_keyframe_db_t** out);
+int orb_kfdb_destroy(orb_keyframe_db_t* db);
+/* KeyFrameDatabase::clear (KeyFrameDatabase.cc:68-72); also forgets every covisibility list. */
+int orb_kfdb_clear(orb_keyframe_db_t* db);
+/* The number of live keyframes. */
+int orb_kfdb_size(const orb_keyframe_db_t* db);
+/* KeyFrameDatabase::add (39-45) of a host BowVector: words strictly ascending and below the
+ * vocabulary's word count, else ORB_EINVAL; a live id is ORB_EINVAL (the reference would list it
+ * twice, and never does); more than 8192 words is ORB_ENOTSUP.  Every add takes the next value of
+ * a monotonic counter `seq`, the keyframe's position in every inverted list of the reference.
+ * The keyframe's stored reloc score starts at 0.0f (the reference leaves mRelocScore
+ * uninitialised, KeyFrame.cc:33; its map loader sets 0, SaveLoadWorld.h:402).  When the pool's
+ * tail has no room the pool is compacted on the device first; ORB_ERANGE only when live entries
+ * + n > max_entries. */
+int orb_kfdb_add(orb_keyframe_db_t* db, int id, const uint32_t* words, const double* values, int n);
+/* B frames of a batched transform (layout as above) added as keyframes ids[0 .. B) (host array)
+ * in that order, device to device; d_bow_n is read back on `stream`.  The words are trusted to
+ * be what the transform wrote.  All of the batch is added or none. */
+int orb_kfdb_add_batch_device(orb_keyframe_db_t* db, int B, const int32_t* ids, const uint32_t* d_bow_words,
+                              const double* d_bow_values, const int32_t* d_bow_n, int cap, void* stream);
+/* KeyFrameDatabase::erase (47-66); an id that is not live is a no-op. */
+int orb_kfdb_erase(orb_keyframe_db_t* db, int id);
+/* GetBestCovisibilityKeyFrames(10) of keyframe `id`, in its order (n <= 10).  Kept per slot, may
+ * be set before the id is live; neighbours that are not live at query time are skipped. */
+int orb_kfdb_set_covisible(orb_keyframe_db_t* db, int id, const int32_t* neighbour_ids, int n);
+/* DetectRelocalisationCandidates (198-308) for a host BowVector; out_ids in the reference's
+ * order.  Every call is a query id of its own (the reference accumulates word counts when a
+ * caller reuses a frame id; that is not modelled).  Stateful as the reference: the score of every
+ * keyframe with common > minCommon is stored, and a covisible neighbour that shares a word but
+ * was not scored contributes the score it kept from an earlier query (or 0.0f).  n = 0 or nothing
+ * shared: *n_out = 0.  More candidates than out_cap: ORB_ERANGE with *n_out = the count needed
+ * and nothing written (the scores are stored all the same; the repeated call returns the same
+ * candidates). */
+int orb_kfdb_detect_relocalisation_candidates(orb_keyframe_db_t* db, const uint32_t* words, const double* values,
+                                              int n, int32_t* out_ids, int out_cap, int* n_out);
+/* DetectLoopCandidates (75-196): connected_ids = GetConnectedKeyFrames() of the query keyframe
+ * (any ids; those not live are ignored), min_score as there.  Reads and writes no stored score. */
+int orb_kfdb_detect_loop_candidates(orb_keyframe_db_t* db, const uint32_t* words, const double* values, int n,
+                                    const int32_t* connected_ids, int n_connected, float min_score, int32_t* out_ids,
+                                    int out_cap, int* n_out);
+/* Q relocalisation queries in the batched-transform layout, without a host round trip: results
+ * and final state are those of Q single calls in the order q = 0 .. Q-1.  d_n_out[q] = the true
+ * count; at most out_cap ids are written to d_out_ids + q * out_cap (the caller checks).
+ * The query rows are trusted to be what the transform wrote (words strictly ascending and below
+ * the vocabulary's word count): nothing on this path validates them, where the host entry points
+ * return ORB_EINVAL.  Asynchronous on `stream`. */
+int orb_kfdb_detect_relocalisation_candidates_batch_device(orb_keyframe_db_t* db, int Q, const uint32_t* d_bow_words,
+                                                           const double* d_bow_values, const int32_t* d_bow_n,
+                                                           int cap, int32_t* d_out_ids, int out_cap,
+                                                           int32_t* d_n_out, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

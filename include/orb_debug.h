@@ -42,6 +42,14 @@ int orb_debug_set_fast_corner_list(orb_extractor_t* h, int cap);
 /* The current geometry's k_pyr_stream plan: returns 1 (and level-0 rows per round, rounds,
  * LDS bytes) when there is one, 0 when the geometry only runs per-level launches. */
 int orb_debug_pyramid_plan(const orb_extractor_t* h, int* rows_per_round, int* rounds, int* lds_bytes);
+/* Per-slot tables of the database's last host query (q = 0) or of query q of its last batch, for
+ * slots 0 .. min(cap, highest id used + 1) - 1 (the return value): common = shared words (0 for a
+ * slot that is not live), first_word = the smallest shared word (0xFFFFFFFF: none), seq = the
+ * slot's add counter now, scored = 1 where common > minCommon in the sharing list, score = the
+ * L1 score of the scan (every sharing keyframe has one).  Tests use it to tell a wrong count from
+ * a wrong score from a wrong order (device sync). */
+int orb_debug_kfdb_last_query(orb_keyframe_db_t* db, int q, int32_t* common, uint32_t* first_word, uint32_t* seq,
+                              uint8_t* scored, double* score, int cap);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,9 @@
 // cv::InputArray / cv::KeyPoint overloads are available; without OpenCV the POD overloads
 // are (std::vector<orb_keypoint_t>, row-major N x 32 descriptor bytes).
 //
+// gpu::KeyFrameDatabase re-exposes KeyFrameDatabase (include/KeyFrameDatabase.h:44-71) over
+// keyframe ids, and gpu::score is mpVoc->score(...) (L1 vocabularies).
+//
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
 // non-OK status, and keeps the reference's early return on an empty image
@@ -19,6 +22,7 @@
 
 #include <climits>
 #include <cstdint>
+#include <map>
 #include <stdexcept>
 #include <utility>
 #include <string>
@@ -246,6 +250,114 @@ public:
 private:
     float mfNNratio;
     bool mbCheckOrientation;
+};
+
+// A DBoW2::BowVector (std::map<WordId, WordValue>) as the C ABI takes it: words ascending.
+struct BowVector {
+    std::vector<uint32_t> words;
+    std::vector<double> values;
+    BowVector() {}
+    template <class Map>  // any map<unsigned, double>-like container iterated in key order
+    explicit BowVector(const Map& m) {
+        words.reserve(m.size());
+        values.reserve(m.size());
+        for (typename Map::const_iterator it = m.begin(); it != m.end(); ++it) {
+            words.push_back((uint32_t)it->first);
+            values.push_back((double)it->second);
+        }
+    }
+    int size() const { return (int)words.size(); }
+};
+
+// mpVoc->score(v1, v2) (TemplatedVocabulary::score, L1Scoring::score).
+inline double score(const orb_vocabulary_t* voc, const BowVector& v1, const BowVector& v2) {
+    double s = 0.0;
+    orb_check(orb_vocabulary_score(voc, v1.words.data(), v1.values.data(), v1.size(), v2.words.data(),
+                                   v2.values.data(), v2.size(), &s));
+    return s;
+}
+
+// KeyFrameDatabase over keyframe ids (KeyFrame::mnId).  The caller passes what the reference
+// reads through the KeyFrame*: mBowVec on add and on a query, GetBestCovisibilityKeyFrames(10)
+// whenever the covisibility graph changes, GetConnectedKeyFrames() with a loop query.  Every id
+// met gets the next slot of the native database and keeps it until clear(), so maxKeyFrames
+// bounds the ids met between two clear() calls.
+class KeyFrameDatabase {
+public:
+    typedef long unsigned int Id;
+
+    KeyFrameDatabase(const orb_vocabulary_t* voc, int maxKeyFrames = 4096, int64_t maxEntries = 0, int device = 0)
+        : max_(maxKeyFrames) {
+        orb_check(orb_kfdb_create(voc, maxKeyFrames, maxEntries > 0 ? maxEntries : (int64_t)1024 * maxKeyFrames, device,
+                                  &h_));
+    }
+    ~KeyFrameDatabase() { orb_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+    void add(Id mnId, const BowVector& bow) {
+        orb_check(orb_kfdb_add(h_, slot(mnId), bow.words.data(), bow.values.data(), bow.size()));
+    }
+    void erase(Id mnId) {
+        std::map<Id, int>::const_iterator it = slot_.find(mnId);
+        if (it != slot_.end()) orb_check(orb_kfdb_erase(h_, it->second));
+    }
+    void clear() {
+        orb_check(orb_kfdb_clear(h_));
+        slot_.clear();
+        id_.clear();
+    }
+    int size() const { return orb_kfdb_size(h_); }
+    // pKF->GetBestCovisibilityKeyFrames(10) as ids, in its order.
+    void SetBestCovisibilityKeyFrames(Id mnId, const std::vector<Id>& neighbours) {
+        std::vector<int32_t> nb;
+        for (size_t i = 0; i < neighbours.size(); ++i) nb.push_back(slot(neighbours[i]));
+        orb_check(orb_kfdb_set_covisible(h_, slot(mnId), nb.data(), (int)nb.size()));
+    }
+    // DetectLoopCandidates(pKF, minScore): bow = pKF->mBowVec, connected = pKF->GetConnectedKeyFrames().
+    std::vector<Id> DetectLoopCandidates(const BowVector& bow, const std::vector<Id>& connected, float minScore) {
+        std::vector<int32_t> conn;
+        for (size_t i = 0; i < connected.size(); ++i) {
+            std::map<Id, int>::const_iterator it = slot_.find(connected[i]);
+            if (it != slot_.end()) conn.push_back(it->second);
+        }
+        std::vector<int32_t> out(id_.size() + 1);
+        int n = 0;
+        orb_check(orb_kfdb_detect_loop_candidates(h_, bow.words.data(), bow.values.data(), bow.size(), conn.data(),
+                                                  (int)conn.size(), minScore, out.data(), (int)out.size(), &n));
+        return ids(out, n);
+    }
+    // DetectRelocalisationCandidates(F): bow = F->mBowVec.
+    std::vector<Id> DetectRelocalisationCandidates(const BowVector& bow) {
+        std::vector<int32_t> out(id_.size() + 1);
+        int n = 0;
+        orb_check(orb_kfdb_detect_relocalisation_candidates(h_, bow.words.data(), bow.values.data(), bow.size(),
+                                                            out.data(), (int)out.size(), &n));
+        return ids(out, n);
+    }
+    orb_keyframe_db_t* handle() { return h_; }
+    // The native slot of an id (for the device entry points), assigned on first use.
+    int slot(Id mnId) {
+        std::map<Id, int>::const_iterator it = slot_.find(mnId);
+        if (it != slot_.end()) return it->second;
+        if ((int)id_.size() >= max_) throw std::runtime_error("orb: more keyframe ids than maxKeyFrames");
+        const int s = (int)id_.size();
+        slot_[mnId] = s;
+        id_.push_back(mnId);
+        return s;
+    }
+    Id id(int slot) const { return id_.at((size_t)slot); }
+
+private:
+    std::vector<Id> ids(const std::vector<int32_t>& out, int n) const {
+        std::vector<Id> r;
+        for (int i = 0; i < n; ++i) r.push_back(id_[(size_t)out[i]]);
+        return r;
+    }
+    orb_keyframe_db_t* h_ = nullptr;
+    int max_;
+    std::map<Id, int> slot_;
+    std::vector<Id> id_;
 };
 
 }  // namespace gpu

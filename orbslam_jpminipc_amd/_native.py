@@ -187,6 +187,20 @@ HIP_SIGNATURES = {
         [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     ),
     "orb_vocabulary_transform": (_i, [_vp, _vp, _i, _i, _vp, _vp, _pi, _vp, _vp, _vp, _pi]),
+    "orb_vocabulary_score": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "orb_vocabulary_score_pairs_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "orb_kfdb_create": (_i, [_vp, _i, _i64, _i, ctypes.POINTER(_vp)]),
+    "orb_kfdb_destroy": (_i, [_vp]),
+    "orb_kfdb_clear": (_i, [_vp]),
+    "orb_kfdb_size": (_i, [_vp]),
+    "orb_kfdb_add": (_i, [_vp, _i, _vp, _vp, _i]),
+    "orb_kfdb_add_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "orb_kfdb_erase": (_i, [_vp, _i]),
+    "orb_kfdb_set_covisible": (_i, [_vp, _i, _vp, _i]),
+    "orb_kfdb_detect_relocalisation_candidates": (_i, [_vp, _vp, _vp, _i, _vp, _i, _pi]),
+    "orb_kfdb_detect_loop_candidates": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _pi]),
+    "orb_kfdb_detect_relocalisation_candidates_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),
     "orb_extract_set_phases": (_i, [_vp, ctypes.c_uint]),

@@ -29,3 +29,7 @@ struct OrbHostCtx {
     int reserve(size_t dev_bytes, size_t host_bytes);
 };
 __attribute__((visibility("hidden"))) OrbHostCtx* orb_internal_thread_ctx(int device);
+
+// The device a vocabulary handle lives on (orb_voc.hip), for the units that take one (orb_kfdb.hip).
+struct orb_vocabulary;
+__attribute__((visibility("hidden"))) int orb_internal_vocabulary_device(const orb_vocabulary* v);

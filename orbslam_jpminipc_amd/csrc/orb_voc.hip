@@ -328,6 +328,8 @@ struct orb_vocabulary {
     }
 };
 
+int orb_internal_vocabulary_device(const orb_vocabulary* v) { return v->device; }
+
 namespace {
 
 int check_header(int k, int L, int scoring, int weighting) {

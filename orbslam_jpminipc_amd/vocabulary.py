@@ -157,6 +157,44 @@ class ORBVocabulary:
             ptr(o["fv_offsets"]), ptr(o["fv_features"]), ptr(o["fv_n"]), ctypes.c_void_p(s.cuda_stream)))
         return out
 
+    # ---- score --------------------------------------------------------------------------
+    def score(self, bow1, bow2) -> float:
+        """TemplatedVocabulary::score of two BowVectors (dicts {word: value} or (words, values)
+        pairs in ascending word order).  L1_NORM vocabularies only."""
+        w1, v1 = bow_arrays(bow1)
+        w2, v2 = bow_arrays(bow2)
+        out = ctypes.c_double()
+        check(self._lib.orb_vocabulary_score(self._h, ptr(w1), ptr(v1), len(w1), ptr(w2), ptr(v2), len(w2),
+                                             ctypes.byref(out)))
+        return out.value
+
+    def score_pairs_device(self, bow_words, bow_values, bow_n, pair_a, pair_b, stream=None):
+        """score(frame pair_a[p], frame pair_b[p]) for BowVectors laid out as transform_batch_device
+        writes them ((B, cap) tensors, bow_n (B,)); returns a (P,) float64 device tensor."""
+        import torch
+
+        P, cap = int(pair_a.shape[0]), int(bow_words.shape[1])
+        out = torch.empty((P,), dtype=torch.float64, device=bow_words.device)
+        s = stream if stream is not None else torch.cuda.current_stream(bow_words.device)
+        check(self._lib.orb_vocabulary_score_pairs_device(self._h, P, ptr(bow_words), ptr(bow_values), ptr(bow_n), cap,
+                                                          ptr(pair_a), ptr(pair_b), ptr(out),
+                                                          ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+
+def bow_arrays(bow):
+    """(uint32 words, float64 values) of a BowVector given as a dict (sorted by word, std::map
+    order) or as a (words, values) pair (taken as it is)."""
+    if isinstance(bow, dict):
+        keys = sorted(bow)
+        return np.array(keys, np.uint32), np.array([bow[k] for k in keys], np.float64)
+    w, v = bow
+    w = np.ascontiguousarray(np.asarray(w, np.uint32))
+    v = np.ascontiguousarray(np.asarray(v, np.float64))
+    if w.shape != v.shape or w.ndim != 1:
+        raise ValueError("words and values differ in shape")
+    return w, v
+
 
 def write_text(path, k, L, scoring, weighting, parent, is_leaf, desc, weight, weight_fmt: str = "%.17g") -> None:
     """Write a vocabulary in the format TemplatedVocabulary::saveToTextFile produces
