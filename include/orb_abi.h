@@ -563,6 +563,57 @@ int orb_kfdb_detect_relocalisation_candidates_batch_device(orb_keyframe_db_t* db
                                                            int cap, int32_t* d_out_ids, int out_cap,
                                                            int32_t* d_n_out, void* stream);
 
+/* ---- Initializer: two-view model scoring (GPU: csrc/orb_initializer.hip) ------------- */
+/* Initializer::CheckHomography (reference src/Initializer.cc:303-386) and CheckFundamental
+ * (388-466) for all RANSAC hypotheses of a frame pair at once, with the "keep the best" rule of
+ * FindHomography / FindFundamental (146-169, 197-220).  The hypotheses are the caller's:
+ * ComputeH21 / ComputeF21 (224-301, cv::SVDecomp), Normalize and the T2inv*Hn*T1 / H21i.inv()
+ * products stay on the host.  mvMatches12 is built as Initializer.cc:54-63 builds it: the pairs
+ * (i, matches12[i]) with matches12[i] >= 0 in ascending i; N = their number, a match's ordinal its
+ * position among them.  Every score is the reference's float sum bit for bit (one add chain per
+ * hypothesis in match order, first-image term before second-image term); a NaN
+ * chi-square is an inlier term and makes the score NaN, an infinite one is an outlier, and a NaN
+ * score never wins.  Best hypothesis: score starts at 0.0 and is replaced on a strict >, so the
+ * first maximum wins; when no hypothesis scores above 0 the best index is -1, the best score 0
+ * and the mask all 0.
+ * Limits: at most 8192 keypoints per frame (ORB_ENOTSUP), 1 <= n_hyp <= 1024 (ORB_EINVAL; the
+ * reference runs 200, Tracking.cc:374).
+ *
+ * One pair, host buffers, synchronous.
+ *   kps1 (n1), kps2 (n2): the frames' mvKeysUn; matches12: n1 ints, vnMatches12, each in
+ *   [-1, n2) (ORB_EINVAL otherwise); sigma: mSigma (1.0, Tracking.cc:374).
+ *   H21, H12, F21: n_hyp x 9 row-major floats each (H21i, H12i = H21i.inv(), F21i of iteration
+ *   i).  H21 and H12 both NULL skips the homographies, F21 NULL the fundamental matrices; the
+ *   outputs of a skipped model are not written.
+ *   scores_h / scores_f: n_hyp floats, the currentScore of every iteration (may be NULL).
+ *   best_h / best_f: the winning iteration or -1; best_score_*: its score (SH / SF,
+ *   Initializer.cc:110); inliers_*: u8 of capacity n1, vbMatchesInliers of the winner, entries
+ *   [0, *n_matches) written.  *n_matches = N.  Any output may be NULL. */
+int orb_initializer_check(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                          const int32_t* matches12, float sigma, int n_hyp, const float* H21, const float* H12,
+                          const float* F21, float* scores_h, float* scores_f, int32_t* best_h, float* best_score_h,
+                          uint8_t* inliers_h, int32_t* best_f, float* best_score_f, uint8_t* inliers_f,
+                          int* n_matches, int device);
+/* The same for P pairs on device-resident extractor and matcher output: pair p = frames
+ * (d_pair_f1[p], d_pair_f2[p]) of a batch laid out as by orb_extract_batch_device (d_kps /
+ * d_counts, per-frame capacity cap; for a distorted camera the undistorted records), its
+ * vnMatches12 = row p of d_matches12 (P x cap) as orb_search_for_initialization_batch_device
+ * writes it.  Hypotheses d_H21 / d_H12 / d_F21: P x n_hyp x 9 floats.  Outputs per pair:
+ * d_scores_* P x n_hyp, d_best_* / d_best_score_* / d_n_matches P, d_inliers_* P x cap (entries
+ * [0, d_n_matches[p]) of row p written).  NULL rules as above; a model whose d_scores_* is NULL
+ * keeps its scores in stream-ordered scratch for the length of the call.
+ * Precondition: row p of d_matches12 holds vnMatches12 of the pair.  An entry outside
+ * [0, d_counts[f2]), or at an index >= d_counts[f1], counts as unmatched (the host entry point
+ * returns ORB_EINVAL instead); nothing outside the batch arrays is read.  The pair indices are
+ * the caller's to keep in range.  P <= 65535.  Asynchronous on `stream`. */
+int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                       const int32_t* d_pair_f1, const int32_t* d_pair_f2,
+                                       const int32_t* d_matches12, float sigma, int n_hyp, const float* d_H21,
+                                       const float* d_H12, const float* d_F21, float* d_scores_h, float* d_scores_f,
+                                       int32_t* d_best_h, float* d_best_score_h, uint8_t* d_inliers_h,
+                                       int32_t* d_best_f, float* d_best_score_f, uint8_t* d_inliers_f,
+                                       int32_t* d_n_matches, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

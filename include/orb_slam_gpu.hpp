@@ -11,7 +11,9 @@
 // are (std::vector<orb_keypoint_t>, row-major N x 32 descriptor bytes).
 //
 // gpu::KeyFrameDatabase re-exposes KeyFrameDatabase (include/KeyFrameDatabase.h:44-71) over
-// keyframe ids, and gpu::score is mpVoc->score(...) (L1 vocabularies).
+// keyframe ids, and gpu::score is mpVoc->score(...) (L1 vocabularies).  gpu::Initializer is the
+// scoring half of Initializer (include/Initializer.h:31-97): FindHomography / FindFundamental over
+// hypotheses the caller has computed.
 //
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
@@ -358,6 +360,77 @@ private:
     int max_;
     std::map<Id, int> slot_;
     std::vector<Id> id_;
+};
+
+// The scoring half of ORB_SLAM::Initializer (Initializer.cc:122-221, 303-466).  The caller runs
+// the front of each RANSAC iteration as the reference does (minimal set, ComputeH21 / ComputeF21,
+// the T2inv*Hn*T1, H21i.inv() and T2t*Fn*T1 products) for ALL iterations first and hands the
+// matrices over, 9 row-major floats per iteration; one call then scores them all and keeps the
+// best as the reference's loop does.
+class Initializer {
+public:
+    // Initializer(ReferenceFrame, sigma, iterations) (Initializer.cc:33-42): keys1 = the
+    // reference frame's mvKeysUn.
+    Initializer(const std::vector<orb_keypoint_t>& keys1, float sigma = 1.0f, int iterations = 200, int device = 0)
+        : mvKeys1(keys1), mSigma(sigma), mMaxIterations(iterations), device_(device) {}
+
+    // The head of Initialize (Initializer.cc:49-65): keys2 = CurrentFrame.mvKeysUn, vMatches12 as
+    // SearchForInitialization wrote it.  Returns N = mvMatches12.size().
+    int SetMatches(const std::vector<orb_keypoint_t>& keys2, const std::vector<int>& vMatches12) {
+        if (vMatches12.size() != mvKeys1.size()) throw std::runtime_error("orb: vMatches12 must have one entry per key of frame 1");
+        mvKeys2 = keys2;
+        matches12_.assign(vMatches12.begin(), vMatches12.end());
+        mvMatches12.clear();
+        for (size_t i = 0; i < matches12_.size(); ++i)
+            if (matches12_[i] >= 0) mvMatches12.push_back(std::make_pair((int)i, (int)matches12_[i]));
+        return (int)mvMatches12.size();
+    }
+
+    // FindHomography (Initializer.cc:122-170) over vH21 / vH12 (mMaxIterations x 9 floats each):
+    // vbMatchesInliers (N flags), score and H21 (9 floats) of the winning iteration; when no
+    // iteration scores above 0 the flags are all false, score is 0 and H21 is left as it was (the
+    // reference leaves its cv::Mat empty).  Returns the winning iteration or -1.
+    int FindHomography(const std::vector<float>& vH21, const std::vector<float>& vH12,
+                       std::vector<bool>& vbMatchesInliers, float& score, std::vector<float>& H21) {
+        need(vH21);
+        need(vH12);
+        return find(vH21.data(), vH12.data(), nullptr, vH21, vbMatchesInliers, score, H21);
+    }
+    // FindFundamental (Initializer.cc:173-221) over vF21 (mMaxIterations x 9 floats).
+    int FindFundamental(const std::vector<float>& vF21, std::vector<bool>& vbMatchesInliers, float& score,
+                        std::vector<float>& F21) {
+        need(vF21);
+        return find(nullptr, nullptr, vF21.data(), vF21, vbMatchesInliers, score, F21);
+    }
+
+    std::vector<std::pair<int, int> > mvMatches12;  // (index in frame 1, index in frame 2), as the reference's
+    std::vector<orb_keypoint_t> mvKeys1, mvKeys2;
+    float mSigma;
+    int mMaxIterations;
+
+private:
+    void need(const std::vector<float>& v) const {
+        if (v.size() != (size_t)mMaxIterations * 9) throw std::runtime_error("orb: hypothesis array must hold mMaxIterations x 9 floats");
+    }
+    int find(const float* h21, const float* h12, const float* f21, const std::vector<float>& src,
+             std::vector<bool>& vbMatchesInliers, float& score, std::vector<float>& M) {
+        std::vector<uint8_t> in(mvKeys1.size() + 1, 0);
+        int32_t best = -1;
+        int n = 0;
+        float s = 0.0f;
+        orb_check(orb_initializer_check(mvKeys1.data(), (int)mvKeys1.size(), mvKeys2.data(), (int)mvKeys2.size(),
+                                        matches12_.data(), mSigma, mMaxIterations, h21, h12, f21, nullptr, nullptr,
+                                        f21 ? nullptr : &best, f21 ? nullptr : &s, f21 ? nullptr : in.data(),
+                                        f21 ? &best : nullptr, f21 ? &s : nullptr, f21 ? in.data() : nullptr, &n,
+                                        device_));
+        score = s;
+        vbMatchesInliers.assign((size_t)n, false);
+        for (int i = 0; i < n; ++i) vbMatchesInliers[(size_t)i] = in[(size_t)i] != 0;
+        if (best >= 0) M.assign(src.begin() + (size_t)best * 9, src.begin() + (size_t)best * 9 + 9);
+        return best;
+    }
+    std::vector<int32_t> matches12_;
+    int device_;
 };
 
 }  // namespace gpu

@@ -16,6 +16,7 @@ from .extractor import ORBextractor, keypoints_from_bytes
 from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
+from .initializer import Initializer
 from .vocabulary import ORBVocabulary
 
 __all__ = [
@@ -23,6 +24,7 @@ __all__ = [
     "ORBmatcher",
     "ORBVocabulary",
     "KeyFrameDatabase",
+    "Initializer",
     "Frame",
     "KEYPOINT_DTYPE",
     "FAST_SCORE",

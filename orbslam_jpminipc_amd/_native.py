@@ -200,6 +200,10 @@ HIP_SIGNATURES = {
     "orb_kfdb_detect_relocalisation_candidates": (_i, [_vp, _vp, _vp, _i, _vp, _i, _pi]),
     "orb_kfdb_detect_loop_candidates": (_i, [_vp, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _pi]),
     "orb_kfdb_detect_relocalisation_candidates_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "orb_initializer_check": (_i, [_vp, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _pi, _i]),
+    "orb_initializer_check_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),
