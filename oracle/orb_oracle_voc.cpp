@@ -15,12 +15,27 @@
 // contracts to fma(v, v, norm) there, written explicitly below; nothing else on the path has
 // a contractible shape.
 //
-// Two reference behaviours are undefined and therefore not restated:
+// Pinned to the compiled reference (tests/test_ref_dbow2.py against tests/golden/ref_dbow2_*, the
+// recorded outputs of the reference's own DBoW2 built by oracle/ref_dbow2/): load_text, transform
+// and transform_one are bit-exact on every recorded case — tie order in the descent, stopped
+// features left out of the FeatureVector, the mustNormalize table, the TF `/= size` branch,
+// nid = root for levelsup >= L, the text format as saveToTextFile writes it.  The contraction
+// claim above is tested too: the reference built -ffp-contract=off and built -mfma
+// -ffp-contract=fast agree byte for byte except in L2-normalised values, and where those differ
+// this file gives the contracted build's.
+//
+// Two reference behaviours are undefined and therefore not restated; they stay
+// undefined there, so the recorded cases keep clear of them and what is written here for them is
+// this project's choice, shared with the product.
 //  * loadFromTextFile's `while(!f.eof()) getline` turns a trailing newline into an extra root
 //    child whose descriptor bytes are never written (FORB::fromString parses nothing into a
 //    fresh cv::Mat); blank lines are skipped here and in the product.
 //  * a leaf reached above level m_L - levelsup leaves the caller's `nid` unwritten
 //    (TemplatedVocabulary.h:1251-1252); here and in the product nid = that leaf.
+// A third lies in the reference's create(): a k-means iteration that leaves a cluster empty makes
+// FORB::meanValue release that cluster's cv::Mat (TemplatedVocabulary.h:716), which
+// FORB::distance then reads (line 739).  That is the reference's behaviour; nothing here restates
+// create(), and the recorded vocabularies do not come from it.
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
