@@ -614,6 +614,87 @@ int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_
                                        int32_t* d_best_f, float* d_best_score_f, uint8_t* d_inliers_f,
                                        int32_t* d_n_matches, void* stream);
 
+/* ---- Solvers: PnP / Sim3 RANSAC consensus (GPU: csrc/orb_solvers.hip) ---------------- */
+/* PnPsolver::CheckInliers (reference src/PnPsolver.cc:280-311) and Sim3Solver::CheckInliers
+ * (src/Sim3Solver.cc:335-359) for all RANSAC hypotheses of a solver at once, with the
+ * per-correspondence set-up of the two constructors and the keep-the-best rule of the two
+ * iterate() loops.  The hypotheses are the caller's: EPnP compute_pose (cvSVD), Refine's pose and
+ * Sim3Solver::computeT (cv::eigen) stay on the host, as do the random minimal sets and the
+ * iteration counters.  Counts and masks are the reference's bit for bit: a NaN
+ * error is an outlier, a point behind the camera is not excluded.
+ * Correspondence i of hypothesis h is bit i % 64 of word i / 64 of the h-th mask row (W words per
+ * row); bits past n are zero.
+ * Keep-the-best, over the hypotheses in order, starting from best_in (mnBestInliers of earlier
+ * iterate() calls, 0 at first): best_at[h] = the hypothesis holding mvbBestInliers after iteration
+ * h, -1 for none, -2 for "still the earlier calls' best" (best_in > 0 and not yet replaced).
+ *   PnP  (PnPsolver.cc:181-196): h qualifies when counts[h] >= min_inliers; among those the best
+ *        is replaced on a strict >, so the first maximum wins.  first_ok = the first qualifying h
+ *        (where the reference goes on to Refine), or -1.  Refine's pose is scored by a call with
+ *        one hypothesis.
+ *   Sim3 (Sim3Solver.cc:183-200): the best is replaced on counts[h] >= best, so the last maximum
+ *        wins.  first_accept = the first h that replaces the best with counts[h] > min_inliers
+ *        (where the reference returns), or -1.
+ * min_inliers is the adjusted mRansacMinInliers (SetRansacParameters; the wrappers compute it).
+ * Limits: n, cap <= 8192 (ORB_ENOTSUP), 1 <= n_hyp <= 1024 (ORB_EINVAL), every sigma2 finite and
+ * >= 0 and, for Sim3, 9.21 * sigma2 < 2^63 (ORB_EINVAL).
+ *
+ * One PnPsolver, host buffers, synchronous.  The n correspondences as the constructor compacts
+ * them: p3d n x 3 (mvP3Dw), p2d n x 2 (mvP2D), sigma2 n (mvSigma2); mvMaxError = sigma2 * th2.
+ * fu, fv, uc, vc: the calibration as the solver's doubles.  R n_hyp x 9, t n_hyp x 3 doubles (mRi,
+ * mti of iteration h).  Outputs, each may be NULL: counts n_hyp (mnInliersi), masks n_hyp x W
+ * with W = (n + 63) / 64 (mvbInliersi), best_at n_hyp, *first_ok. */
+int orb_pnp_check_inliers(int n, const float* p3d, const float* p2d, const float* sigma2, float th2, double fu,
+                          double fv, double uc, double vc, int n_hyp, const double* R, const double* t,
+                          int min_inliers, int best_in, int32_t* counts, uint64_t* masks, int32_t* best_at,
+                          int32_t* first_ok, int device);
+/* One Sim3Solver, host buffers, synchronous.  x3dc1 / x3dc2 n x 3 (mvX3Dc1 / mvX3Dc2), sigma2_1 /
+ * sigma2_2 n (GetSigma2 of the two keypoints' octaves): mvP1im1 / mvP2im2 (FromCameraToImage) and
+ * the bounds mvnMaxError1/2 = (size_t)(9.210 * sigma2) are computed here.  K1 / K2: fx, fy, cx,
+ * cy.  T12 / T21: n_hyp x 12 floats, rows 0-2 of mT12i / mT21i (row-major 3 x 4).  Outputs as
+ * above with *first_accept. */
+int orb_sim3_check_inliers(int n, const float* x3dc1, const float* x3dc2, const float* sigma2_1,
+                           const float* sigma2_2, const float* K1, const float* K2, int n_hyp, const float* T12,
+                           const float* T21, int min_inliers, int best_in, int32_t* counts, uint64_t* masks,
+                           int32_t* best_at, int32_t* first_accept, int device);
+/* S PnPsolvers on device-resident data: solver s = (keyframe d_pair_a[s], frame d_pair_b[s]) of
+ * a batch laid out as by orb_extract_batch_device (d_kps / d_counts, per-frame capacity cap; the
+ * undistorted records), row s of d_match (S x cap) as orb_search_by_bow_batch_device with
+ * kf_kf = 0 writes it (d_match[s][j] = the keyframe keypoint matched to frame keypoint j).
+ * d_mp_pos B x cap x 3: the world position of the MapPoint of each keypoint of the batch;
+ * d_mp_bad B x cap u8 (may be NULL): its isBad().  level_sigma2: nlevels (1..16) host floats.
+ * Correspondences, as PnPsolver.cc:51-73 builds them: the frame keypoints j in ascending order
+ * whose match is a keyframe keypoint with a MapPoint that is not bad.  Hypotheses d_R S x n_hyp x
+ * 9, d_t S x n_hyp x 3 doubles; d_best_in S (NULL = all 0).  Outputs per solver, each may be NULL:
+ * d_n S (N), d_index S x cap (mvKeyPointIndices, -1 past N), d_counts_out S x n_hyp, d_masks S x
+ * n_hyp x W with W = (cap + 63) / 64 (written whole), d_best_at S x n_hyp, d_first_ok S.
+ * A match entry outside [0, d_counts[keyframe]), or at an index >= d_counts[frame], is no match;
+ * an octave outside [0, nlevels) is clamped; nothing outside the batch arrays is read.  The pair
+ * indices are the caller's to keep in range.  S <= 65535.  Asynchronous on `stream`. */
+int orb_pnp_check_inliers_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                       const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                       const float* d_mp_pos, const uint8_t* d_mp_bad, const float* level_sigma2,
+                                       int nlevels, float th2, double fu, double fv, double uc, double vc, int n_hyp,
+                                       const double* d_R, const double* d_t, int min_inliers,
+                                       const int32_t* d_best_in, int32_t* d_n, int32_t* d_index,
+                                       int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                       int32_t* d_first_ok, void* stream);
+/* S Sim3Solvers likewise: solver s = keyframes (d_pair_a[s], d_pair_b[s]), row s of d_match as
+ * orb_search_by_bow_batch_device with kf_kf = 1 writes it (d_match[s][i1] = idx2).  d_mp_pos /
+ * d_mp_bad apply to both keyframes; d_pose B x 12 floats, Rcw (row-major 3 x 3) then tcw, gives
+ * mvX3Dc1/2 = Rcw * Pos + tcw.  K: fx, fy, cx, cy, one calibration for the call.  d_T12 / d_T21
+ * S x n_hyp x 12 floats.  d_index = mvnIndices1.
+ * Precondition: the pair (i1, idx2) stands for GetIndexInKeyFrame of the two MapPoints, i.e. each
+ * MapPoint is observed in its keyframe at the keypoint the match row names (what SearchByBoW
+ * matched), and a keypoint without a MapPoint is flagged in d_mp_bad. */
+int orb_sim3_check_inliers_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                        const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                        const float* d_mp_pos, const uint8_t* d_mp_bad, const float* d_pose,
+                                        const float* level_sigma2, int nlevels, const float* K, int n_hyp,
+                                        const float* d_T12, const float* d_T21, int min_inliers,
+                                        const int32_t* d_best_in, int32_t* d_n, int32_t* d_index,
+                                        int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                        int32_t* d_first_accept, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

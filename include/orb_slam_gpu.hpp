@@ -13,7 +13,9 @@
 // gpu::KeyFrameDatabase re-exposes KeyFrameDatabase (include/KeyFrameDatabase.h:44-71) over
 // keyframe ids, and gpu::score is mpVoc->score(...) (L1 vocabularies).  gpu::Initializer is the
 // scoring half of Initializer (include/Initializer.h:31-97): FindHomography / FindFundamental over
-// hypotheses the caller has computed.
+// hypotheses the caller has computed.  gpu::PnPsolver and gpu::Sim3Solver are the consensus halves
+// of PnPsolver (include/PnPsolver.h) and Sim3Solver (include/Sim3Solver.h): CheckInliers and the
+// keep-the-best rule of iterate over poses the caller has computed.
 //
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
@@ -22,7 +24,9 @@
 #ifndef ORB_SLAM_GPU_HPP
 #define ORB_SLAM_GPU_HPP
 
+#include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -430,6 +434,197 @@ private:
         return best;
     }
     std::vector<int32_t> matches12_;
+    int device_;
+};
+
+// The consensus half of ORB_SLAM::PnPsolver (PnPsolver.cc:39-230, 280-311).  The caller draws the
+// minimal sets and runs EPnP's compute_pose for a block of iterations first (the callers ask for 5
+// at a time, Tracking.cc:961) and hands the poses over; one call scores them all and applies
+// lines 181-196.
+class PnPsolver {
+public:
+    // PnPsolver(F, vpMapPointMatches) (PnPsolver.cc:39-82) over PODs: keysUn = F.mvKeysUn,
+    // levelSigma2 = F.mvLevelSigma2; for every keypoint i, usable[i] = vpMapPointMatches[i] is set
+    // and not bad, worldPos[3 i ..] = its GetWorldPos().
+    PnPsolver(const std::vector<orb_keypoint_t>& keysUn, const std::vector<float>& levelSigma2,
+              const std::vector<uint8_t>& usable, const std::vector<float>& worldPos, float fx, float fy, float cx,
+              float cy, int device = 0)
+        : fu(fx), fv(fy), uc(cx), vc(cy), mnIterations(0), mnBestInliers(0), mnBest(-1), N(0), nKeys_(keysUn.size()),
+          device_(device) {
+        if (usable.size() != keysUn.size() || worldPos.size() != keysUn.size() * 3)
+            throw std::runtime_error("orb: usable / worldPos must have one entry per keypoint");
+        for (size_t i = 0; i < keysUn.size(); ++i) {
+            if (!usable[i]) continue;
+            mvP2D.push_back(keysUn[i].x);
+            mvP2D.push_back(keysUn[i].y);
+            mvSigma2.push_back(levelSigma2.at((size_t)keysUn[i].octave));
+            mvP3Dw.insert(mvP3Dw.end(), worldPos.begin() + 3 * i, worldPos.begin() + 3 * i + 3);
+            mvKeyPointIndices.push_back(i);
+        }
+        SetRansacParameters();
+    }
+
+    // PnPsolver.cc:93-129 (mvMaxError = mvSigma2 * th2 is formed on the device)
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4,
+                             float epsilon = 0.4f, float th2 = 5.991f) {
+        N = (int)mvSigma2.size();
+        int nMinInliers = (int)(N * epsilon);
+        if (nMinInliers < minInliers) nMinInliers = minInliers;
+        if (nMinInliers < minSet) nMinInliers = minSet;
+        mRansacMinInliers = nMinInliers;
+        mRansacEpsilon = epsilon;
+        if (mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N;
+        mRansacMaxIts = ransac_iterations(probability, mRansacEpsilon, mRansacMinInliers == N, maxIterations);
+        mRansacTh = th2;
+    }
+
+    // vR (k x 9) / vt (k x 3): mRi / mti of the next k iterations.  Returns the first of them whose
+    // count reaches mRansacMinInliers (where the reference calls Refine; the later ones are not
+    // taken as run), or -1 when none does.  mnIterations, mnBestInliers and mvbBestInliers advance
+    // as iterate() advances them; mnBest is the index, within the call that set it, of the pose
+    // holding mvbBestInliers.
+    int iterate(const std::vector<double>& vR, const std::vector<double>& vt) {
+        const int k = (int)(vt.size() / 3);
+        if (k < 1 || vR.size() != (size_t)k * 9 || vt.size() != (size_t)k * 3)
+            throw std::runtime_error("orb: poses must be k x 9 and k x 3 doubles");
+        const int W = (N + 63) / 64;
+        std::vector<int32_t> counts((size_t)k), best_at((size_t)k);
+        std::vector<uint64_t> masks((size_t)k * W + 1);
+        int32_t first = -1;
+        orb_check(orb_pnp_check_inliers(N, mvP3Dw.data(), mvP2D.data(), mvSigma2.data(), mRansacTh, fu, fv, uc, vc, k,
+                                        vR.data(), vt.data(), mRansacMinInliers, mnBestInliers, counts.data(),
+                                        masks.data(), best_at.data(), &first, device_));
+        const int last = first >= 0 ? first : k - 1;
+        mnIterations += last + 1;
+        const int holder = best_at[(size_t)last];
+        if (holder >= 0) {
+            mnBest = holder;
+            mnBestInliers = counts[(size_t)holder];
+            unpack(&masks[(size_t)holder * W], mvbBestInliers);
+        }
+        return first;
+    }
+
+    // CheckInliers for one pose (Refine's scoring, PnPsolver.cc:255-262): the count and the flags.
+    int CheckInliers(const double* R, const double* t, std::vector<bool>& vbInliers) const {
+        std::vector<uint64_t> mask((size_t)(N + 63) / 64 + 1);
+        int32_t count = 0;
+        orb_check(orb_pnp_check_inliers(N, mvP3Dw.data(), mvP2D.data(), mvSigma2.data(), mRansacTh, fu, fv, uc, vc, 1,
+                                        R, t, mRansacMinInliers, 0, &count, mask.data(), nullptr, nullptr, device_));
+        unpack(mask.data(), vbInliers);
+        return count;
+    }
+
+    // vbInliers of iterate / find (PnPsolver.cc:201-206, 219-224): per frame keypoint.
+    std::vector<bool> InliersByKeyPoint(const std::vector<bool>& vbInliers) const {
+        std::vector<bool> v(nKeys_, false);
+        for (int i = 0; i < N && i < (int)vbInliers.size(); ++i)
+            if (vbInliers[(size_t)i]) v[mvKeyPointIndices[(size_t)i]] = true;
+        return v;
+    }
+
+    static int ransac_iterations(double probability, float epsilon, bool all, int maxIterations) {
+        int nIterations;
+        if (all)
+            nIterations = 1;
+        else {
+            const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));
+            nIterations = v >= -2147483648.0 && v < 2147483648.0 ? (int)v : INT_MIN;  // as x86-64 converts
+        }
+        return std::max(1, std::min(nIterations, maxIterations));
+    }
+
+    std::vector<float> mvP2D, mvSigma2, mvP3Dw;  // N x 2, N, N x 3
+    std::vector<size_t> mvKeyPointIndices;
+    std::vector<bool> mvbBestInliers;
+    double fu, fv, uc, vc;
+    int mnIterations, mnBestInliers, mnBest;
+    int mRansacMinInliers, mRansacMaxIts;
+    float mRansacEpsilon, mRansacTh;
+    int N;
+
+private:
+    void unpack(const uint64_t* w, std::vector<bool>& v) const {
+        v.assign((size_t)N, false);
+        for (int i = 0; i < N; ++i) v[(size_t)i] = (w[i >> 6] >> (i & 63)) & 1;
+    }
+    size_t nKeys_;
+    int device_;
+};
+
+// The consensus half of ORB_SLAM::Sim3Solver (Sim3Solver.cc:37-207, 335-418): the caller draws the
+// minimal sets and runs computeT for a block of iterations (5 at a time, LoopClosing.cc:314) and
+// hands rows 0-2 of mT12i / mT21i over.
+class Sim3Solver {
+public:
+    // Sim3Solver(pKF1, pKF2, vpMatched12) (Sim3Solver.cc:37-112) over PODs, one entry per kept
+    // correspondence: x3Dc1 / x3Dc2 (N x 3, mvX3Dc1 / mvX3Dc2), sigma2_1 / sigma2_2 (GetSigma2 of the
+    // keypoints' octaves), indices1 (mvnIndices1); N1 = vpMatched12.size(); K1 / K2: fx, fy, cx, cy.
+    Sim3Solver(const std::vector<float>& x3Dc1, const std::vector<float>& x3Dc2, const std::vector<float>& sigma2_1,
+               const std::vector<float>& sigma2_2, const std::vector<size_t>& indices1, int N1, const float* K1,
+               const float* K2, int device = 0)
+        : mvX3Dc1(x3Dc1), mvX3Dc2(x3Dc2), mvSigma2_1(sigma2_1), mvSigma2_2(sigma2_2), mvnIndices1(indices1),
+          mnIterations(0), mnBestInliers(0), mnBest(-1), mN1(N1), device_(device) {
+        N = (int)sigma2_1.size();
+        if (x3Dc1.size() != (size_t)N * 3 || x3Dc2.size() != (size_t)N * 3 || sigma2_2.size() != (size_t)N ||
+            indices1.size() != (size_t)N)
+            throw std::runtime_error("orb: the correspondence arrays must have one entry per correspondence");
+        for (int k = 0; k < 4; ++k) mK1[k] = K1[k], mK2[k] = K2[k];
+        SetRansacParameters();
+    }
+
+    // Sim3Solver.cc:114-138
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacMinInliers = minInliers;
+        const float epsilon = (float)mRansacMinInliers / N;
+        mRansacMaxIts = PnPsolver::ransac_iterations(probability, epsilon, mRansacMinInliers == N, maxIterations);
+        mnIterations = 0;
+    }
+
+    // vT12 / vT21 (k x 12 floats): the next k iterations.  Returns the first of them the reference
+    // returns at (count >= the running best and > mRansacMinInliers; the later ones are not taken
+    // as run), or -1.  vbInliers (mN1 flags by keyframe-1 keypoint) and nInliers are set as
+    // iterate() sets them: filled on acceptance, all false / 0 otherwise.
+    int iterate(const std::vector<float>& vT12, const std::vector<float>& vT21, std::vector<bool>& vbInliers,
+                int& nInliers) {
+        const int k = (int)(vT12.size() / 12);
+        if (k < 1 || vT12.size() != (size_t)k * 12 || vT21.size() != (size_t)k * 12)
+            throw std::runtime_error("orb: transforms must be k x 12 floats each");
+        const int W = (N + 63) / 64;
+        std::vector<int32_t> counts((size_t)k), best_at((size_t)k);
+        std::vector<uint64_t> masks((size_t)k * W + 1);
+        int32_t first = -1;
+        orb_check(orb_sim3_check_inliers(N, mvX3Dc1.data(), mvX3Dc2.data(), mvSigma2_1.data(), mvSigma2_2.data(), mK1,
+                                         mK2, k, vT12.data(), vT21.data(), mRansacMinInliers, mnBestInliers,
+                                         counts.data(), masks.data(), best_at.data(), &first, device_));
+        const int last = first >= 0 ? first : k - 1;
+        mnIterations += last + 1;
+        const int holder = best_at[(size_t)last];
+        if (holder >= 0) {
+            mnBest = holder;
+            mnBestInliers = counts[(size_t)holder];
+            mvbBestInliers.assign((size_t)N, false);
+            for (int i = 0; i < N; ++i) mvbBestInliers[(size_t)i] = (masks[(size_t)holder * W + (i >> 6)] >> (i & 63)) & 1;
+        }
+        vbInliers.assign((size_t)mN1, false);
+        nInliers = 0;
+        if (first >= 0) {
+            nInliers = counts[(size_t)first];
+            for (int i = 0; i < N; ++i)
+                if (mvbBestInliers[(size_t)i]) vbInliers[mvnIndices1[(size_t)i]] = true;
+        }
+        return first;
+    }
+
+    std::vector<float> mvX3Dc1, mvX3Dc2, mvSigma2_1, mvSigma2_2;
+    std::vector<size_t> mvnIndices1;
+    std::vector<bool> mvbBestInliers;
+    float mK1[4], mK2[4];
+    int mnIterations, mnBestInliers, mnBest;
+    int mRansacMinInliers, mRansacMaxIts;
+    int N, mN1;
+
+private:
     int device_;
 };
 

@@ -17,6 +17,7 @@ from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
 from .initializer import Initializer
+from .solvers import PnPConsensus, Sim3Consensus, pnp_ransac_parameters, sim3_ransac_parameters
 from .vocabulary import ORBVocabulary
 
 __all__ = [
@@ -25,6 +26,10 @@ __all__ = [
     "ORBVocabulary",
     "KeyFrameDatabase",
     "Initializer",
+    "PnPConsensus",
+    "Sim3Consensus",
+    "pnp_ransac_parameters",
+    "sim3_ransac_parameters",
     "Frame",
     "KEYPOINT_DTYPE",
     "FAST_SCORE",

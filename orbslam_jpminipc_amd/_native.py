@@ -61,6 +61,7 @@ _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _f = ctypes.c_float
+_d = ctypes.c_double
 
 MAX_VIEW_LEVELS = 16
 
@@ -204,6 +205,12 @@ HIP_SIGNATURES = {
                                    _pi, _i]),
     "orb_initializer_check_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_pnp_check_inliers": (_i, [_i, _vp, _vp, _vp, _f, _d, _d, _d, _d, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "orb_sim3_check_inliers": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "orb_pnp_check_inliers_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _d, _d, _d, _d,
+                                                _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_sim3_check_inliers_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp,
+                                                 _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),
