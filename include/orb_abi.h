@@ -695,6 +695,54 @@ int orb_sim3_check_inliers_batch_device(const orb_keypoint_t* d_kps, const int32
                                         int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
                                         int32_t* d_first_accept, void* stream);
 
+/* ---- Optimizer: motion-only pose optimisation (GPU: csrc/orb_optimizer.hip) ----------- */
+/* Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285) with the parts of g2o
+ * it runs, in double: one SE3 vertex (quaternion + translation), one EdgeSE3ProjectXYZ per
+ * keypoint that has a MapPoint (fixed point, information invSigma2 * I, Huber kernel of delta
+ * (float)sqrt(5.991)), four rounds of Levenberg ({10, 10, 7, 5} iterations, up to 10 trials each)
+ * over the edges not flagged, each followed by the classification against chi2 = {9.210f, 7.378f,
+ * 5.991f, 5.991f}.  The whole schedule runs in one launch, one workgroup per problem; DESIGN.md
+ * §13 lists the semantics kept (the quirks included) and what a sum order may change.  Poses are
+ * 12 values: Rcw row-major, then tcw.  pose_in goes through Converter::toSE3Quat (quaternion of R,
+ * normalised), so pose_out of a problem without edges is pose_in after that round trip.
+ * pose_out = (float)pose_out_f64.  outlier = mvbOutlier (0 where there is no MapPoint);
+ * *n_inliers = nInitialCorrespondences - nBad of the last round run (an edge whose chi2 is NaN
+ * keeps its flag and is not counted in nBad, as in the reference).
+ * Limits: n, cap <= 8192, S <= 65535 (ORB_ENOTSUP); a non-finite pose or calibration value,
+ * fx == 0 or fy == 0: ORB_EINVAL (the host entry point checks pose_in, both check K). */
+typedef struct {
+    int32_t n_initial;     /* nInitialCorrespondences: the edges                            */
+    int32_t n_bad;         /* nBad of the last round run                                    */
+    int32_t rounds;        /* rounds run: 4, or 1 when there are fewer than 10 edges        */
+    int32_t iterations[4]; /* diagnostics: Levenberg iterations run per round ...           */
+    int32_t trials;        /* ... trial steps in all ...                                    */
+    double lambda;         /* ... the last lambda (-1: no round had an edge) ...            */
+    double chi2;           /* ... and the robust chi2 the last iteration ended with         */
+} orb_pose_opt_info_t;
+/* One frame, host buffers, synchronous.  Keypoint i: p3d n x 3 (GetWorldPos), obs n x 2
+ * (mvKeysUn[i].pt), inv_sigma2 n (mvInvLevelSigma2[octave]); has_mp n u8 (NULL: every keypoint has
+ * a MapPoint).  pose_out_f64 and info may be NULL. */
+int orb_pose_optimization(int n, const float* p3d, const float* obs, const float* inv_sigma2, const uint8_t* has_mp,
+                          float fx, float fy, float cx, float cy, const float* pose_in, float* pose_out,
+                          double* pose_out_f64, uint8_t* outlier, int32_t* n_inliers, orb_pose_opt_info_t* info,
+                          int device);
+/* S problems on device-resident data: problem s reads the undistorted records of frame
+ * d_frame_of[s] of a batch laid out as by orb_extract_batch_device (d_kps / d_counts, capacity
+ * cap) and its own row of d_mp_pos (S x cap x 3, the MapPoint of keypoint i) and d_has_mp (S x cap
+ * u8), so one frame may serve several problems (relocalisation candidates).  inv_level_sigma2:
+ * n_levels (1..16) host floats, mvInvLevelSigma2; K4: fx, fy, cx, cy host floats.  d_pose_in S x
+ * 12.  Outputs: d_pose_out S x 12 f32, d_pose_out_f64 S x 12 (may be NULL), d_outlier S x cap
+ * (written whole: 0 past the frame's count), d_n_inliers S, d_info S (may be NULL).
+ * An index at or past the frame's count is no edge; an octave outside [0, n_levels) is clamped;
+ * nothing outside the batch arrays is read.  The frame indices are the caller's to keep in range.
+ * Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_pose_optimization_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                       const int32_t* d_frame_of, const float* d_mp_pos, const uint8_t* d_has_mp,
+                                       const float* inv_level_sigma2, int n_levels, const float* K4,
+                                       const float* d_pose_in, float* d_pose_out, double* d_pose_out_f64,
+                                       uint8_t* d_outlier, int32_t* d_n_inliers, orb_pose_opt_info_t* d_info,
+                                       void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

@@ -15,7 +15,8 @@
 // scoring half of Initializer (include/Initializer.h:31-97): FindHomography / FindFundamental over
 // hypotheses the caller has computed.  gpu::PnPsolver and gpu::Sim3Solver are the consensus halves
 // of PnPsolver (include/PnPsolver.h) and Sim3Solver (include/Sim3Solver.h): CheckInliers and the
-// keep-the-best rule of iterate over poses the caller has computed.
+// keep-the-best rule of iterate over poses the caller has computed.  gpu::Optimizer::PoseOptimization
+// is Optimizer::PoseOptimization (include/Optimizer.h), the motion-only optimisation, whole.
 //
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
@@ -626,6 +627,40 @@ public:
 
 private:
     int device_;
+};
+
+// ORB_SLAM::Optimizer::PoseOptimization(Frame*) (Optimizer.cc:154-285) over PODs; bundle adjustment
+// and the essential graph stay with the reference's g2o.
+class Optimizer {
+public:
+    // F.keysUn = pFrame->mvKeysUn (N of them), invLevelSigma2 = mvInvLevelSigma2, fx..cy the
+    // frame's calibration; for every keypoint i, hasMP[i] = mvpMapPoints[i] is set and
+    // worldPos[3 i ..] = its GetWorldPos().  Tcw: Rcw row-major then tcw (12 floats), read as
+    // pFrame->mTcw and overwritten with the optimised pose.  mvbOutlier is resized to N and
+    // written as the reference writes it (false where there is no MapPoint).  Returns
+    // nInitialCorrespondences - nBad.
+    static int PoseOptimization(const FrameView& F, const std::vector<float>& invLevelSigma2, float fx, float fy,
+                                float cx, float cy, const std::vector<uint8_t>& hasMP,
+                                const std::vector<float>& worldPos, float* Tcw, std::vector<bool>& mvbOutlier,
+                                int device = 0, orb_pose_opt_info_t* info = nullptr) {
+        const size_t N = (size_t)std::max(F.N, 0);
+        if (hasMP.size() != N || worldPos.size() != N * 3)
+            throw std::runtime_error("orb: hasMP / worldPos must have one entry per keypoint");
+        std::vector<float> obs(N * 2), inv(N);
+        for (size_t i = 0; i < N; ++i) {
+            obs[2 * i] = F.keysUn[i].x, obs[2 * i + 1] = F.keysUn[i].y;
+            inv[i] = hasMP[i] ? invLevelSigma2.at((size_t)F.keysUn[i].octave) : 0.0f;
+        }
+        std::vector<uint8_t> flags(std::max<size_t>(N, 1));
+        float out[12];
+        int32_t nInliers = 0;
+        orb_check(orb_pose_optimization((int)N, worldPos.data(), obs.data(), inv.data(), hasMP.data(), fx, fy, cx, cy,
+                                        Tcw, out, nullptr, flags.data(), &nInliers, info, device));
+        std::copy(out, out + 12, Tcw);
+        mvbOutlier.assign(N, false);
+        for (size_t i = 0; i < N; ++i) mvbOutlier[i] = flags[i] != 0;
+        return nInliers;
+    }
 };
 
 }  // namespace gpu

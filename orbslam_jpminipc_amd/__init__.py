@@ -17,6 +17,7 @@ from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
 from .initializer import Initializer
+from .optimizer import Optimizer
 from .solvers import PnPConsensus, Sim3Consensus, pnp_ransac_parameters, sim3_ransac_parameters
 from .vocabulary import ORBVocabulary
 
@@ -26,6 +27,7 @@ __all__ = [
     "ORBVocabulary",
     "KeyFrameDatabase",
     "Initializer",
+    "Optimizer",
     "PnPConsensus",
     "Sim3Consensus",
     "pnp_ransac_parameters",

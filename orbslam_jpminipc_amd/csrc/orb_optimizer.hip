@@ -1,0 +1,723 @@
+// orb_optimizer.hip — Optimizer::PoseOptimization(Frame*) on the GPU (part of liborb_hip.so).
+//
+// The motion-only optimisation that ends every tracking-time chain of the reference
+// (src/Optimizer.cc:154-285; called from Tracking.cc:557, 580, 611, 643, 988, 1004, 1019), with the
+// parts of g2o it runs restated in double:
+//   set-up          Optimizer.cc:168-237: one edge per keypoint with a MapPoint, obs and the
+//                   calibration widened from float, information invSigma2 * I, Huber delta
+//                   (double)(float)sqrt(5.991)
+//   pose in / out   Converter::toSE3Quat (Converter.cc:38-48), SE3Quat(R, t) + normalizeRotation
+//                   (se3quat.h:58-59, 280-285), to_homogeneous_matrix (270-278)
+//   edge            EdgeSE3ProjectXYZ::computeError / cam_project / _jacobianOplusXj
+//                   (types_six_dof_expmap.h:172-177, .cpp:407-428)
+//   quadratic form  base_binary_edge.hpp:91-113 with RobustKernelHuber (robust_kernel_impl.cpp:78-91);
+//                   the rho[2] term is commented out in base_edge.h:96-102
+//   Levenberg       optimization_algorithm_levenberg.cpp:61-189, update exp(x) * T
+//                   (types_six_dof_expmap.h:104-107, se3quat.h:104-110, 223-257)
+//   dense solver    linear_solver_dense.h:104-112: Eigen::LDLT, refused when not positive (Eigen is
+//                   not in the reference tree: ldlt6 follows Eigen 3's documented algorithm)
+//   four rounds     Optimizer.cc:242-276
+//
+// Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
+// prepare step.  Sums over edges are taken in a fixed order (thread-strided partial sums, an
+// xor butterfly across the wave, the four waves in order), so a call gives the same bits on every
+// run; the order differs from g2o's edge order, which is what the tests' tolerance measures.
+// There is no floating-point atomic.
+//
+//   k_po_prepare  one workgroup per problem: compacts the keypoints that have a MapPoint in index
+//                 order (ballot + popcount prefix, wave totals through LDS) to SoA doubles
+//                 X Y Z u v invSigma2 and the index list; zeroes the outlier row.
+//   k_po_solve    one workgroup per problem runs the whole schedule.  Thread t owns the edges t,
+//                 t + 256, ...; a build pass reduces the 21 + 6 + 1 values of H, b and the robust
+//                 chi2, a trial pass one value.  After a reduction every thread holds the same
+//                 bits, so the 6 x 6 solve, the update and every decision of the schedule are
+//                 taken redundantly by all threads: no broadcast, and branches are uniform.
+//                 Every loop has a static bound (4 rounds, its[r] iterations, 10 trials,
+//                 ceil(n / 256) edges).  The flags live in LDS, the edges' chi2 of their last
+//                 evaluation in scratch, as the classification reads them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/orb_abi.h"
+#include "orb_internal.h"
+
+namespace {
+
+int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
+
+#define PCHK(expr)                                                                                \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+constexpr int PO_MAX_CAP = 8192;
+constexpr int PO_THREADS = 256;
+constexpr int PO_WAVES = PO_THREADS / 64;
+constexpr int PO_NV = 7;   // X Y Z u v invSigma2 | chi2 of the last evaluation
+constexpr int PO_NACC = 28;  // 21 of H (upper triangle), 6 of b, the robust chi2
+
+struct PoArgs {
+    // batch form: extractor records of frame frame_of[s]; mp_pos / has_mp rows per problem
+    const orb_keypoint_t* kps;
+    const int32_t* kcounts;
+    const int32_t* frame_of;
+    // host form (n_direct >= 0): one problem, obs n x 2 and inv_sigma2 n given directly
+    const float* obs;
+    const float* inv_sigma2;
+    int n_direct;
+    const float* mp_pos;
+    const uint8_t* has_mp;
+    float inv_level_sigma2[ORB_MAX_VIEW_LEVELS];
+    int nlevels;
+    double fx, fy, cx, cy;
+    double delta;  // the Huber delta, (double)(float)sqrt(5.991) (Optimizer.cc:189)
+    const float* pose_in;
+    float* pose_out;
+    double* pose_out64;
+    uint8_t* outlier;
+    int32_t* n_inliers;
+    orb_pose_opt_info_t* info;
+    // scratch
+    double* soa;     // S x PO_NV x cap
+    int32_t* index;  // S x cap
+    int32_t* n;      // S
+    int cap, S;
+};
+
+__global__ void __launch_bounds__(PO_THREADS) k_po_prepare(PoArgs a) {
+    __shared__ int s_wtot[PO_WAVES];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool direct = a.n_direct >= 0;
+    const int f = direct ? 0 : a.frame_of[s];
+    // an index past the frame's count is no edge, so no read leaves the batch arrays
+    const int n_row = direct ? a.n_direct : min(max(a.kcounts[f], 0), a.cap);
+    uint8_t* outl = a.outlier + (size_t)s * a.cap;
+    for (int i = tid; i < (direct ? a.n_direct : a.cap); i += PO_THREADS) outl[i] = 0;
+    double* q = a.soa + (size_t)s * PO_NV * a.cap;
+    int32_t* index = a.index + (size_t)s * a.cap;
+    const size_t row = (size_t)s * a.cap;
+    int base = 0;
+    for (int i0 = 0; i0 < n_row; i0 += PO_THREADS) {
+        const int i = i0 + tid;
+        const bool ok = i < n_row && (a.has_mp ? a.has_mp[row + i] != 0 : true);
+        const unsigned long long bal = __ballot(ok);
+        if (lane == 0) s_wtot[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base, tot = 0;
+#pragma unroll
+        for (int w = 0; w < PO_WAVES; ++w) {
+            const int t = s_wtot[w];
+            if (w < wave) off += t;
+            tot += t;
+        }
+        if (ok) {
+            const int o = off + __popcll(bal & ((1ull << lane) - 1ull));
+            float u, v, is2;
+            if (direct) {
+                u = a.obs[2 * i], v = a.obs[2 * i + 1], is2 = a.inv_sigma2[i];
+            } else {
+                const orb_keypoint_t& kp = a.kps[(size_t)f * a.cap + i];
+                u = kp.x, v = kp.y;
+                is2 = a.inv_level_sigma2[min(max(kp.octave, 0), a.nlevels - 1)];
+            }
+            const float* X = a.mp_pos + 3 * (row + i);
+            q[o] = (double)X[0], q[a.cap + o] = (double)X[1], q[2 * a.cap + o] = (double)X[2];
+            q[3 * a.cap + o] = (double)u, q[4 * a.cap + o] = (double)v, q[5 * a.cap + o] = (double)is2;
+            index[o] = i;
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.n[s] = base;
+}
+
+struct Pose {
+    double q[4];  // x y z w
+    double t[3];
+};
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Eigen's Quaternion * Vector3: v + w * 2(q x v) + q x 2(q x v)
+__device__ __forceinline__ void rotate(const double* q, const double* v, double* o) {
+    double uv[3], c[3];
+    cross3(q, v, uv);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
+    cross3(q, uv, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = v[k] + q[3] * uv[k] + c[k];
+}
+
+__device__ __forceinline__ void normalize_rotation(Pose& p) {  // se3quat.h:280-285
+    if (p.q[3] < 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p.q[k] *= -1;
+    }
+    const double n = sqrt(p.q[0] * p.q[0] + p.q[1] * p.q[1] + p.q[2] * p.q[2] + p.q[3] * p.q[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p.q[k] /= n;
+}
+
+// Eigen's Quaterniond(Matrix3d), m row-major
+__device__ void quat_from_matrix(const double* m, double* q) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+}
+
+// Eigen's toRotationMatrix, row-major
+__device__ void matrix_from_quat(const double* q, double* R) {
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
+    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
+}
+
+// VertexSE3Expmap::oplusImpl: exp(x) * T with x = (omega, upsilon)
+__device__ Pose exp_update(const double* x, const Pose& T) {
+    const double* om = x;
+    const double* up = x + 3;
+    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
+    double O2[9], R[9], V[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = O[3 * i] * O[j];
+            s += O[3 * i + 1] * O[3 + j];
+            s += O[3 * i + 2] * O[6 + j];
+            O2[3 * i + j] = s;
+        }
+    if (theta < 0.00001) {  // se3quat.h:237-243
+#pragma unroll
+        for (int k = 0; k < 9; ++k) V[k] = R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k];
+    } else {
+        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta),
+                     c = (theta - sin(theta)) / pow(theta, 3.0);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const double I = k % 4 == 0 ? 1.0 : 0.0;
+            R[k] = (I + a * O[k]) + b * O2[k];
+            V[k] = (I + b * O[k]) + c * O2[k];
+        }
+    }
+    Pose e;
+    quat_from_matrix(R, e.q);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double s = V[3 * i] * up[0];
+        s += V[3 * i + 1] * up[1];
+        s += V[3 * i + 2] * up[2];
+        e.t[i] = s;
+    }
+    normalize_rotation(e);
+    // SE3Quat::operator* (se3quat.h:104-110): t += r * T.t; r *= T.r; normalizeRotation
+    Pose r = e;
+    double rt[3];
+    rotate(e.q, T.t, rt);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.t[k] += rt[k];
+    const double *a = e.q, *b = T.q;
+    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    normalize_rotation(r);
+    return r;
+}
+
+struct Cam {
+    double fx, fy, cx, cy;
+};
+
+// computeError (obs - cam_project(T.map(X))) and chi2 = e' * (invSigma2 I) * e; Xc for the Jacobian
+__device__ __forceinline__ double edge_chi2(const Pose& T, const Cam& c, const double* q, int cap, int e, double* err,
+                                            double* Xc) {
+    const double X[3] = {q[e], q[cap + e], q[2 * cap + e]};
+    double r[3];
+    rotate(T.q, X, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Xc[k] = r[k] + T.t[k];
+    err[0] = q[3 * cap + e] - ((Xc[0] / Xc[2]) * c.fx + c.cx);
+    err[1] = q[4 * cap + e] - ((Xc[1] / Xc[2]) * c.fy + c.cy);
+    const double s = q[5 * cap + e];
+    return err[0] * (s * err[0]) + err[1] * (s * err[1]);
+}
+
+// RobustKernelHuber::robustify: rho[0], rho[1]
+__device__ __forceinline__ void huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
+    if (e <= dsqr) {
+        *rho0 = e, *rho1 = 1.;
+    } else {
+        const double sqrte = sqrt(e);
+        *rho0 = 2 * sqrte * delta - dsqr;
+        *rho1 = delta / sqrte;
+    }
+}
+
+// Sum of v[0..W) over the workgroup, in a fixed order; every thread gets the same bits.
+template <int W>
+__device__ __forceinline__ void block_sum(double* v, double (*s_red)[PO_NACC]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m);
+    }
+    __syncthreads();  // the readers of the last reduction are done
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) s_red[wave][k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        double s = s_red[0][k];
+#pragma unroll
+        for (int w = 1; w < PO_WAVES; ++w) s += s_red[w][k];
+        v[k] = s;
+    }
+}
+
+// Eigen::LDLT of the 6 x 6 A (full symmetric storage, overwritten) and the solve of A x = b:
+// diagonal pivoting on the largest |a_ii|, the sign tracked over the pivots; false (x untouched)
+// when the matrix is not positive (LDLT::isPositive, linear_solver_dense.h:108).
+__device__ bool ldlt6(double* A, const double* b, double* x) {
+    int tr[6];
+    int sign = 0;  // 0 zero, 1 positive semi-definite, -1 negative semi-definite, 2 indefinite
+    for (int k = 0; k < 6; ++k) {
+        int p = k;
+        double big = fabs(A[7 * k]);
+        for (int i = k + 1; i < 6; ++i)
+            if (fabs(A[7 * i]) > big) big = fabs(A[7 * i]), p = i;
+        tr[k] = p;
+        if (p != k) {
+            for (int j = 0; j < 6; ++j) {
+                const double t = A[6 * k + j];
+                A[6 * k + j] = A[6 * p + j], A[6 * p + j] = t;
+            }
+            for (int j = 0; j < 6; ++j) {
+                const double t = A[6 * j + k];
+                A[6 * j + k] = A[6 * j + p], A[6 * j + p] = t;
+            }
+        }
+        double temp[6];
+        for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
+        for (int j = 0; j < k; ++j) A[7 * k] -= A[6 * k + j] * temp[j];
+        for (int i = k + 1; i < 6; ++i) {
+            double s = A[6 * i + k];
+            for (int j = 0; j < k; ++j) s -= A[6 * i + j] * temp[j];
+            A[6 * i + k] = s;
+        }
+        const double akk = A[7 * k];
+        if (fabs(akk) > 0)
+            for (int i = k + 1; i < 6; ++i) A[6 * i + k] /= akk;
+        if (sign == 1) {
+            if (akk < 0) sign = 2;
+        } else if (sign == -1) {
+            if (akk > 0) sign = 2;
+        } else if (sign == 0) {
+            if (akk > 0) sign = 1;
+            else if (akk < 0) sign = -1;
+        }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    double y[6];
+    for (int k = 0; k < 6; ++k) y[k] = b[k];
+    for (int k = 0; k < 6; ++k) {
+        const double t = y[k];
+        y[k] = y[tr[k]], y[tr[k]] = t;
+    }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < i; ++j) y[i] -= A[6 * i + j] * y[j];
+    const double tol = 1.0 / DBL_MAX;
+    for (int i = 0; i < 6; ++i) y[i] = fabs(A[7 * i]) > tol ? y[i] / A[7 * i] : 0.0;
+    for (int i = 5; i >= 0; --i)
+        for (int j = i + 1; j < 6; ++j) y[i] -= A[6 * j + i] * y[j];
+    for (int k = 5; k >= 0; --k) {
+        const double t = y[k];
+        y[k] = y[tr[k]], y[tr[k]] = t;
+    }
+    for (int k = 0; k < 6; ++k) x[k] = y[k];
+    return true;
+}
+
+__global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
+    __shared__ double s_red[PO_WAVES][PO_NACC];
+    __shared__ uint8_t s_flag[PO_MAX_CAP];  // mvbOutlier of the edges = their level
+    __shared__ int s_cnt[2];                // nBad, edges left in the optimisation
+    const int s = blockIdx.x, tid = threadIdx.x, cap = a.cap;
+    const int n = min(max(a.n[s], 0), min(cap, PO_MAX_CAP));
+    double* q = a.soa + (size_t)s * PO_NV * cap;
+    double* chi2_e = q + (size_t)6 * cap;
+    const Cam cam{a.fx, a.fy, a.cx, a.cy};
+    const double delta = a.delta;
+    const double dsqr = delta * delta;
+    for (int e = tid; e < n; e += PO_THREADS) s_flag[e] = 0;
+    if (tid == 0) s_cnt[0] = 0, s_cnt[1] = n;
+    Pose T;
+    {  // Converter::toSE3Quat
+        const float* p = a.pose_in + (size_t)s * 12;
+        double R[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = (double)p[k];
+        quat_from_matrix(R, T.q);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) T.t[k] = (double)p[9 + k];
+        normalize_rotation(T);
+    }
+    __syncthreads();
+    const float th[4] = {9.210f, 7.378f, 5.991f, 5.991f};
+    const int its[4] = {10, 10, 7, 5};
+    int iters[4] = {0, 0, 0, 0};
+    int trials = 0, rounds = 0, n_bad = 0;
+    double lambda = -1., ni = 2., last_chi = 0.;
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    for (int r = 0; r < 4; ++r) {
+        const int n_active = s_cnt[1];
+        int bad_steps = 0;
+        bool stop = n_active <= 0;  // no level-0 edge: optimize() returns at once
+        for (int it = 0; it < its[r]; ++it) {
+            if (stop) break;
+            ++iters[r];
+            // computeActiveErrors + activeRobustChi2 + buildSystem at T
+            double acc[PO_NACC];
+#pragma unroll
+            for (int k = 0; k < PO_NACC; ++k) acc[k] = 0.;
+            for (int e = tid; e < n; e += PO_THREADS) {
+                if (s_flag[e]) continue;
+                double err[2], Xc[3], rho0, rho1, J[12];
+                const double c2 = edge_chi2(T, cam, q, cap, e, err, Xc);
+                chi2_e[e] = c2;
+                huber(c2, delta, dsqr, &rho0, &rho1);
+                const double X = Xc[0], Y = Xc[1], Z = Xc[2], z_2 = Z * Z;
+                J[0] = X * Y / z_2 * cam.fx;
+                J[1] = -(1 + (X * X / z_2)) * cam.fx;
+                J[2] = Y / Z * cam.fx;
+                J[3] = -1. / Z * cam.fx;
+                J[4] = 0;
+                J[5] = X / z_2 * cam.fx;
+                J[6] = (1 + Y * Y / z_2) * cam.fy;
+                J[7] = -X * Y / z_2 * cam.fy;
+                J[8] = -X / Z * cam.fy;
+                J[9] = 0;
+                J[10] = -1. / Z * cam.fy;
+                J[11] = Y / z_2 * cam.fy;
+                const double sg = q[5 * cap + e];
+                const double w = sg * rho1;  // weightedOmega = rho[1] * omega
+                const double r0 = (-(sg * err[0])) * rho1, r1 = (-(sg * err[1])) * rho1;
+                int c = 0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j)
+#pragma unroll
+                    for (int k = j; k < 6; ++k) acc[c++] += (J[j] * w) * J[k] + (J[6 + j] * w) * J[6 + k];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) acc[21 + j] += J[j] * r0 + J[6 + j] * r1;
+                acc[27] += rho0;
+            }
+            block_sum<PO_NACC>(acc, s_red);
+            double H[36], b[6];
+            {
+                int c = 0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j)
+#pragma unroll
+                    for (int k = j; k < 6; ++k) H[6 * j + k] = H[6 * k + j] = acc[c++];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) b[j] = acc[21 + j];
+            }
+            double cur = acc[27];
+            double temp = cur;
+            const double ini = cur;
+            if (it == 0) {  // computeLambdaInit
+                double mx = 0.;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {  // std::max(fabs(h_jj), maxDiagonal)
+                    const double v = fabs(H[7 * j]);
+                    mx = v < mx ? mx : v;
+                }
+                lambda = 1e-5 * mx;
+                ni = 2.;
+                bad_steps = 0;
+            }
+            double rho = 0;
+            int qmax = 0;
+            bool again = true;
+            for (int tr = 0; tr < 10; ++tr) {
+                if (!again) break;
+                const Pose backup = T;
+                double A[36];
+#pragma unroll
+                for (int k = 0; k < 36; ++k) A[k] = H[k];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) A[7 * j] += lambda;
+                const bool ok2 = ldlt6(A, b, x);
+                T = exp_update(x, T);
+                double t1[1] = {0.};
+                for (int e = tid; e < n; e += PO_THREADS) {
+                    if (s_flag[e]) continue;
+                    double err[2], Xc[3], rho0, rho1;
+                    const double c2 = edge_chi2(T, cam, q, cap, e, err, Xc);
+                    chi2_e[e] = c2;
+                    huber(c2, delta, dsqr, &rho0, &rho1);
+                    t1[0] += rho0;
+                }
+                block_sum<1>(t1, s_red);
+                temp = t1[0];
+                if (!ok2) temp = DBL_MAX;
+                rho = cur - temp;
+                double scale = 0.;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + b[j]);
+                scale += 1e-3;
+                rho /= scale;
+                if (rho > 0 && isfinite(temp)) {
+                    double alpha = 1. - pow(2 * rho - 1, 3.0);
+                    alpha = 2. / 3. < alpha ? 2. / 3. : alpha;           // std::min(alpha, upper)
+                    const double f = 1. / 3. < alpha ? alpha : 1. / 3.;  // std::max(lower, alpha)
+                    lambda *= f;
+                    ni = 2;
+                    cur = temp;
+                } else {
+                    lambda *= ni;
+                    ni *= 2;
+                    T = backup;
+                }
+                ++qmax;
+                ++trials;
+                again = rho < 0 && qmax < 10;  // a NaN rho leaves the loop
+            }
+            last_chi = cur;
+            if (qmax == 10 || rho == 0) stop = true;  // Terminate
+            if (!stop) {
+                if ((ini - cur) * 1e3 < ini) ++bad_steps;
+                else bad_steps = 0;
+                if (bad_steps >= 3) stop = true;
+            }
+        }
+        // classification (Optimizer.cc:251-272)
+        __syncthreads();
+        if (tid == 0) s_cnt[0] = 0, s_cnt[1] = 0;
+        __syncthreads();
+        const double thr = (double)th[r];
+        int bad = 0, act = 0;
+        for (int e = tid; e < n; e += PO_THREADS) {
+            if (s_flag[e]) {
+                double err[2], Xc[3];
+                chi2_e[e] = edge_chi2(T, cam, q, cap, e, err, Xc);
+            }
+            const double c2 = chi2_e[e];
+            if (c2 > thr) {
+                s_flag[e] = 1, ++bad;
+            } else if (c2 <= thr) {
+                s_flag[e] = 0;
+            }
+            act += s_flag[e] ? 0 : 1;
+        }
+        if (bad) atomicAdd(&s_cnt[0], bad);
+        if (act) atomicAdd(&s_cnt[1], act);
+        __syncthreads();
+        n_bad = s_cnt[0];
+        rounds = r + 1;
+        if (n < 10) break;  // optimizer.edges().size() < 10
+    }
+    const int32_t* index = a.index + (size_t)s * cap;
+    uint8_t* outl = a.outlier + (size_t)s * cap;
+    for (int e = tid; e < n; e += PO_THREADS) outl[index[e]] = s_flag[e];
+    if (tid == 0) {
+        double M[12];
+        matrix_from_quat(T.q, M);
+        for (int k = 0; k < 3; ++k) M[9 + k] = T.t[k];
+        for (int k = 0; k < 12; ++k) {
+            if (a.pose_out64) a.pose_out64[(size_t)s * 12 + k] = M[k];
+            a.pose_out[(size_t)s * 12 + k] = (float)M[k];
+        }
+        a.n_inliers[s] = n - n_bad;
+        if (a.info) {
+            orb_pose_opt_info_t I;
+            I.n_initial = n, I.n_bad = n_bad, I.rounds = rounds;
+            for (int k = 0; k < 4; ++k) I.iterations[k] = iters[k];
+            I.trials = trials, I.lambda = lambda, I.chi2 = last_chi;
+            a.info[s] = I;
+        }
+    }
+}
+
+int launch(PoArgs a, hipStream_t st) {
+    a.delta = (double)(float)std::sqrt(5.991);
+    hipLaunchKernelGGL(k_po_prepare, dim3(a.S), dim3(PO_THREADS), 0, st, a);
+    PCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_po_solve, dim3(a.S), dim3(PO_THREADS), 0, st, a);
+    PCHK(hipGetLastError());
+    return ORB_OK;
+}
+
+int check_camera(const char* who, const float* K) {
+    static const char* const name[4] = {"fx", "fy", "cx", "cy"};
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(K[k]) || (k < 2 && K[k] == 0.0f))
+            return fail(ORB_EINVAL, std::string(who) + ": " + name[k] + " = " + std::to_string(K[k]) +
+                                        (k < 2 ? " must be finite and not 0" : " must be finite"));
+    return ORB_OK;
+}
+
+size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int orb_pose_optimization(int n, const float* p3d, const float* obs, const float* inv_sigma2, const uint8_t* has_mp,
+                          float fx, float fy, float cx, float cy, const float* pose_in, float* pose_out,
+                          double* pose_out_f64, uint8_t* outlier, int32_t* n_inliers, orb_pose_opt_info_t* info,
+                          int device) {
+    const char* who = "pose_optimization";
+    if (n < 0 || (n && (!p3d || !obs || !inv_sigma2 || !outlier)) || !pose_in || !pose_out || !n_inliers)
+        return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (n > PO_MAX_CAP) return fail(ORB_ENOTSUP, std::string(who) + ": more than 8192 keypoints");
+    const float K[4] = {fx, fy, cx, cy};
+    if (int r = check_camera(who, K)) return r;
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose_in[k]))
+            return fail(ORB_EINVAL, std::string(who) + ": pose_in[" + std::to_string(k) + "] is not finite");
+    int ndev = 0;
+    PCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) PCHK(hipGetDevice(&device));
+    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
+    PCHK(hipSetDevice(device));
+    const int cap = std::max(n, 1);
+    // staging: in  [p3d | obs | inv_sigma2 | has_mp | pose_in]
+    //          out [pose f64 | info | pose f32 | n_inliers | outlier]   then the scratch (device only)
+    const size_t oP = 0, oO = al(oP + (size_t)n * 12), oS = al(oO + (size_t)n * 8), oH = al(oS + (size_t)n * 4),
+                 oT = al(oH + (size_t)n), in_end = al(oT + 48);
+    const size_t o64 = in_end, oI = al(o64 + 96), o32 = al(oI + sizeof(orb_pose_opt_info_t)), oN = al(o32 + 48),
+                 oF = al(oN + 4), out_end = al(oF + (size_t)cap);
+    const size_t oSoa = out_end, oIdx = al(oSoa + (size_t)PO_NV * cap * 8), oCnt = al(oIdx + (size_t)cap * 4),
+                 total = al(oCnt + 4);
+    if (int r = C->reserve(total, out_end)) return r;
+    uint8_t* hp = C->pinned;
+    if (n) {
+        std::memcpy(hp + oP, p3d, (size_t)n * 12);
+        std::memcpy(hp + oO, obs, (size_t)n * 8);
+        std::memcpy(hp + oS, inv_sigma2, (size_t)n * 4);
+        if (has_mp) std::memcpy(hp + oH, has_mp, (size_t)n);
+    }
+    std::memcpy(hp + oT, pose_in, 48);
+    PCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    uint8_t* d = C->buf;
+    PoArgs a{};
+    a.n_direct = n;
+    a.mp_pos = (const float*)(d + oP);
+    a.obs = (const float*)(d + oO);
+    a.inv_sigma2 = (const float*)(d + oS);
+    a.has_mp = has_mp ? d + oH : nullptr;
+    a.nlevels = 1;
+    a.fx = (double)fx, a.fy = (double)fy, a.cx = (double)cx, a.cy = (double)cy;
+    a.pose_in = (const float*)(d + oT);
+    a.pose_out64 = (double*)(d + o64);
+    a.info = (orb_pose_opt_info_t*)(d + oI);
+    a.pose_out = (float*)(d + o32);
+    a.n_inliers = (int32_t*)(d + oN);
+    a.outlier = d + oF;
+    a.soa = (double*)(d + oSoa);
+    a.index = (int32_t*)(d + oIdx);
+    a.n = (int32_t*)(d + oCnt);
+    a.cap = cap;
+    a.S = 1;
+    const int r = launch(a, C->stream);
+    hipError_t e = hipSuccess;
+    if (r == ORB_OK) e = hipMemcpyAsync(hp + o64, d + o64, out_end - o64, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
+    if (r) return r;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    std::memcpy(pose_out, hp + o32, 48);
+    if (pose_out_f64) std::memcpy(pose_out_f64, hp + o64, 96);
+    if (info) std::memcpy(info, hp + oI, sizeof *info);
+    std::memcpy(n_inliers, hp + oN, 4);
+    if (n) std::memcpy(outlier, hp + oF, (size_t)n);
+    return ORB_OK;
+}
+
+int orb_pose_optimization_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                       const int32_t* d_frame_of, const float* d_mp_pos, const uint8_t* d_has_mp,
+                                       const float* inv_level_sigma2, int n_levels, const float* K4,
+                                       const float* d_pose_in, float* d_pose_out, double* d_pose_out_f64,
+                                       uint8_t* d_outlier, int32_t* d_n_inliers, orb_pose_opt_info_t* d_info,
+                                       void* stream) {
+    const char* who = "pose_optimization_batch";
+    if (S < 0 || cap <= 0 || !K4) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (cap > PO_MAX_CAP) return fail(ORB_ENOTSUP, std::string(who) + ": more than 8192 keypoints per frame");
+    if (S > 65535) return fail(ORB_ENOTSUP, std::string(who) + ": more than 65535 problems per call");
+    if (!inv_level_sigma2 || n_levels < 1 || n_levels > ORB_MAX_VIEW_LEVELS)
+        return fail(ORB_EINVAL, std::string(who) + ": n_levels must be in [1, 16]");
+    if (int r = check_camera(who, K4)) return r;
+    if (S == 0) return ORB_OK;
+    if (!d_kps || !d_counts || !d_frame_of || !d_mp_pos || !d_has_mp || !d_pose_in || !d_pose_out || !d_outlier ||
+        !d_n_inliers)
+        return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    PoArgs a{};
+    a.kps = d_kps;
+    a.kcounts = d_counts;
+    a.frame_of = d_frame_of;
+    a.n_direct = -1;
+    a.mp_pos = d_mp_pos;
+    a.has_mp = d_has_mp;
+    std::memcpy(a.inv_level_sigma2, inv_level_sigma2, (size_t)n_levels * 4);
+    a.nlevels = n_levels;
+    a.fx = (double)K4[0], a.fy = (double)K4[1], a.cx = (double)K4[2], a.cy = (double)K4[3];
+    a.pose_in = d_pose_in;
+    a.pose_out = d_pose_out;
+    a.pose_out64 = d_pose_out_f64;
+    a.outlier = d_outlier;
+    a.n_inliers = d_n_inliers;
+    a.info = d_info;
+    a.cap = cap;
+    a.S = S;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t b_soa = al((size_t)S * PO_NV * cap * 8), b_idx = al((size_t)S * cap * 4), b_n = al((size_t)S * 4);
+    void* tmp = nullptr;
+    hipError_t e = hipMallocAsync(&tmp, b_soa + b_idx + b_n, st);
+    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string(who) + ": scratch: " + hipGetErrorString(e));
+    a.soa = (double*)tmp;
+    a.index = (int32_t*)((uint8_t*)tmp + b_soa);
+    a.n = (int32_t*)((uint8_t*)tmp + b_soa + b_idx);
+    const int r = launch(a, st);
+    (void)hipFreeAsync(tmp, st);
+    return r;
+}
+
+}  // extern "C"
