@@ -743,6 +743,67 @@ int orb_pose_optimization_batch_device(const orb_keypoint_t* d_kps, const int32_
                                        uint8_t* d_outlier, int32_t* d_n_inliers, orb_pose_opt_info_t* d_info,
                                        void* stream);
 
+/* ---- Optimizer: Sim3 optimisation of a loop candidate (GPU: csrc/orb_sim3opt.hip) ------ */
+/* Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1721-1917; LoopClosing.cc:340) with the parts
+ * of g2o it runs, in double: one Sim3 vertex (quaternion, never normalised, translation, scale) and
+ * per usable slot two edges over fixed camera-frame points, e12 = obs1 - cam1(project(S.map(X2)))
+ * with information invSigma2(octave1) * I and e21 = obs2 - cam2(project(S^-1.map(X1))) with
+ * information sigma2(octave2) * I (GetSigma2, Optimizer.cc:1842: the reference's behaviour, kept),
+ * both with a Huber kernel of delta (float)sqrt(th2); the Jacobian is g2o's numeric one (central
+ * differences at 1e-9 through oplus).  optimize(5); every pair with chi2(e12) > th2 || chi2(e21) >
+ * th2 is removed and its slot cleared (n_bad); fewer than 10 pairs left: the result is 0 and the
+ * Sim3 outputs are the input's (after the quaternion conversion), the cleared slots stay cleared;
+ * else optimize(n_bad > 0 ? 10 : 5) and a second classification that clears slots and counts the
+ * inliers.  The whole schedule runs in one launch, one workgroup per problem; DESIGN.md §14 lists
+ * the semantics kept and what a sum order may change.  A Sim3 is 13 floats in and out (R row-major,
+ * t, s; out = (float) of toRotationMatrix, t, s) and 8 doubles out (qx qy qz qw, t, s).  A pair whose
+ * chi2 is NaN on both edges is not > th2: it stays and counts as an inlier, as in the reference.
+ * Limits: n, cap <= 8192, S <= 65535 (ORB_ENOTSUP); a non-finite calibration value, fx == 0 or
+ * fy == 0, th2 not finite or < 0, and in the host form a non-finite sim3_in: ORB_EINVAL. */
+typedef struct {
+    int32_t n_correspondences; /* nCorrespondences: the usable slots                           */
+    int32_t n_bad;             /* nBad: the pairs removed by the first classification          */
+    int32_t more_iterations;   /* nMoreIterations: 5 or 10; 0 when the routine returned early  */
+    int32_t iterations[2];     /* diagnostics: Levenberg iterations run per optimize() ...     */
+    int32_t trials;            /* ... trial steps in all ...                                   */
+    double lambda;             /* ... the last lambda (-1: nothing ran) ...                    */
+    double chi2;               /* ... and the robust chi2 the last iteration ended with        */
+} orb_sim3_opt_info_t;
+/* One candidate, host buffers, synchronous.  Slot i (i = keypoint of KF1): x3dc1 / x3dc2 n x 3 (P3D1c
+ * / P3D2c: the two MapPoints in their own keyframe's camera frame), obs1 n x 2 (kpUn1.pt), obs2 n x
+ * 2 (kpUn2.pt of keypoint i2 = GetIndexInKeyFrame(pKF2)), inv_sigma2_1 n (GetInvSigma2(octave1)),
+ * sigma2_2 n (GetSigma2(octave2)); usable n u8 (NULL: all): vpMatches1[i] set, both MapPoints
+ * there and not bad, i2 >= 0.  K1 / K2: fx, fy, cx, cy.  Outputs: kept n u8 (the slot is still
+ * matched afterwards; 0 where not usable); sim3_out_f64 (8), sim3_out (13), n_inliers and info may
+ * be NULL. */
+int orb_optimize_sim3(int n, const float* x3dc1, const float* x3dc2, const float* obs1, const float* obs2,
+                      const float* inv_sigma2_1, const float* sigma2_2, const uint8_t* usable, const float* K1,
+                      const float* K2, float th2, const float* sim3_in, uint8_t* kept, double* sim3_out_f64,
+                      float* sim3_out, int32_t* n_inliers, orb_sim3_opt_info_t* info, int device);
+/* S candidates on device-resident data, laid out as for orb_sim3_check_inliers_batch_device:
+ * problem s = keyframes (d_pair_a[s], d_pair_b[s]) of a batch (d_kps / d_counts, capacity cap; the
+ * undistorted records), row s of d_match (S x cap, d_match[s][i1] = idx2) as
+ * orb_search_by_bow_batch_device with kf_kf = 1 or SearchBySim3 leaves it.  d_mp_pos B x cap x 3
+ * and d_mp_bad B x cap u8 (may be NULL) apply to both keyframes; d_pose B x 12 floats (Rcw row-major,
+ * tcw) gives P3D1c / P3D2c = Rcw * Pos + tcw as float row sums.  level_sigma2 / inv_level_sigma2:
+ * nlevels (1..16) host floats (mvLevelSigma2, mvInvLevelSigma2); K: fx, fy, cx, cy, one calibration
+ * for the call.  d_sim3_in S x 13.  Outputs, each may be NULL: d_match_out S x cap (the row as it
+ * came, the cleared slots at -1; may be d_match itself), d_sim3_out S x 13, d_sim3_out_f64 S x 8,
+ * d_n_inliers S, d_info S.
+ * Precondition, as there: the pair (i1, idx2) stands for GetIndexInKeyFrame of the two MapPoints,
+ * and a keypoint without a MapPoint is flagged in d_mp_bad.  A match entry outside [0,
+ * d_counts[b]), or at an index >= d_counts[a], is no correspondence (it is copied to d_match_out as
+ * it is); an octave outside [0, nlevels) is clamped; nothing outside the batch arrays is read.  The
+ * pair indices are the caller's to keep in range.  Asynchronous on `stream`; scratch is
+ * stream-ordered. */
+int orb_optimize_sim3_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                   const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                   const float* d_mp_pos, const uint8_t* d_mp_bad, const float* d_pose,
+                                   const float* level_sigma2, const float* inv_level_sigma2, int nlevels,
+                                   const float* K, float th2, const float* d_sim3_in, int32_t* d_match_out,
+                                   float* d_sim3_out, double* d_sim3_out_f64, int32_t* d_n_inliers,
+                                   orb_sim3_opt_info_t* d_info, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

@@ -16,7 +16,8 @@
 // hypotheses the caller has computed.  gpu::PnPsolver and gpu::Sim3Solver are the consensus halves
 // of PnPsolver (include/PnPsolver.h) and Sim3Solver (include/Sim3Solver.h): CheckInliers and the
 // keep-the-best rule of iterate over poses the caller has computed.  gpu::Optimizer::PoseOptimization
-// is Optimizer::PoseOptimization (include/Optimizer.h), the motion-only optimisation, whole.
+// is Optimizer::PoseOptimization (include/Optimizer.h), the motion-only optimisation, whole, and
+// gpu::Optimizer::OptimizeSim3 is Optimizer::OptimizeSim3, the 7-DoF optimisation of a loop candidate.
 //
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
@@ -629,8 +630,9 @@ private:
     int device_;
 };
 
-// ORB_SLAM::Optimizer::PoseOptimization(Frame*) (Optimizer.cc:154-285) over PODs; bundle adjustment
-// and the essential graph stay with the reference's g2o.
+// ORB_SLAM::Optimizer::PoseOptimization(Frame*) (Optimizer.cc:154-285) and Optimizer::OptimizeSim3
+// (Optimizer.cc:1721-1917) over PODs; bundle adjustment and the essential graph stay with the
+// reference's g2o.
 class Optimizer {
 public:
     // F.keysUn = pFrame->mvKeysUn (N of them), invLevelSigma2 = mvInvLevelSigma2, fx..cy the
@@ -660,6 +662,48 @@ public:
         mvbOutlier.assign(N, false);
         for (size_t i = 0; i < N; ++i) mvbOutlier[i] = flags[i] != 0;
         return nInliers;
+    }
+
+    // ORB_SLAM::Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2) (Optimizer.cc:1721-1917)
+    // over PODs.  KF1.keysUn / KF2.keysUn: the two keyframes' undistorted keypoints;
+    // invLevelSigma2_1 = pKF1's mvInvLevelSigma2, levelSigma2_2 = pKF2's mvLevelSigma2 (the reference
+    // weights e21 with GetSigma2).  Slot i of vpMatches1 (one per keypoint of KF1) holds i2 =
+    // vpMatches1[i]->GetIndexInKeyFrame(pKF2), or -1 where there is no usable pair (no match, a
+    // MapPoint missing or bad, i2 < 0); p3d1c[3 i ..] = R1w * P3D1w + t1w and p3d2c[3 i ..] = R2w *
+    // P3D2w + t2w of the pair, as the caller's cv::Mat arithmetic gives them.  S12: 13 floats (R
+    // row-major, t, s), read as g2oS12 and overwritten with the optimised Sim3; when the routine
+    // returns 0 because fewer than 10 pairs are left it keeps the input, as the reference's does.
+    // Slots the routine clears are set to -1.  Returns nIn.
+    static int OptimizeSim3(const FrameView& KF1, const FrameView& KF2, const std::vector<float>& invLevelSigma2_1,
+                            const std::vector<float>& levelSigma2_2, const float* K1, const float* K2,
+                            std::vector<int>& vpMatches1, const std::vector<float>& p3d1c,
+                            const std::vector<float>& p3d2c, float* S12, float th2, int device = 0,
+                            orb_sim3_opt_info_t* info = nullptr) {
+        const size_t N = vpMatches1.size();
+        if (N > (size_t)std::max(KF1.N, 0) || p3d1c.size() != N * 3 || p3d2c.size() != N * 3)
+            throw std::runtime_error("orb: vpMatches1 / p3d1c / p3d2c must have one entry per keypoint of KF1");
+        std::vector<float> obs1(N * 2), obs2(N * 2), w1(N), w2(N);
+        std::vector<uint8_t> usable(std::max<size_t>(N, 1)), kept(std::max<size_t>(N, 1));
+        for (size_t i = 0; i < N; ++i) {
+            const int i2 = vpMatches1[i];
+            usable[i] = i2 >= 0 && i2 < KF2.N;
+            if (!usable[i]) continue;
+            obs1[2 * i] = KF1.keysUn[i].x, obs1[2 * i + 1] = KF1.keysUn[i].y;
+            obs2[2 * i] = KF2.keysUn[i2].x, obs2[2 * i + 1] = KF2.keysUn[i2].y;
+            w1[i] = invLevelSigma2_1.at((size_t)KF1.keysUn[i].octave);
+            w2[i] = levelSigma2_2.at((size_t)KF2.keysUn[i2].octave);
+        }
+        float out[13];
+        int32_t nIn = 0;
+        orb_sim3_opt_info_t inf;
+        orb_check(orb_optimize_sim3((int)N, p3d1c.data(), p3d2c.data(), obs1.data(), obs2.data(), w1.data(), w2.data(),
+                                    usable.data(), K1, K2, th2, S12, kept.data(), nullptr, out, &nIn, &inf, device));
+        if (info) *info = inf;
+        for (size_t i = 0; i < N; ++i)
+            if (usable[i] && !kept[i]) vpMatches1[i] = -1;
+        // the reference copies the estimate out only past its early return (Optimizer.cc:1887-1888, 1914)
+        if (inf.more_iterations != 0) std::copy(out, out + 13, S12);
+        return nIn;
     }
 };
 

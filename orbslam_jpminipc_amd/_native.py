@@ -214,6 +214,9 @@ HIP_SIGNATURES = {
     "orb_pose_optimization": (_i, [_i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_pose_optimization_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp]),
+    "orb_optimize_sim3": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orb_optimize_sim3_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp]),
     "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),

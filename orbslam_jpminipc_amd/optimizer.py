@@ -1,10 +1,12 @@
-"""Optimizer::PoseOptimization(Frame*) on the GPU (reference src/Optimizer.cc:154-285), over the C
-ABI of ``include/orb_abi.h`` (csrc/orb_optimizer.hip).
+"""Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285, csrc/orb_optimizer.hip)
+and Optimizer::OptimizeSim3 (Optimizer.cc:1721-1917, csrc/orb_sim3opt.hip) on the GPU, over the C
+ABI of ``include/orb_abi.h``.
 
 The motion-only optimisation of one frame's pose against its keypoint <-> MapPoint associations:
 the whole g2o schedule (four rounds of Levenberg with the outlier classification between them)
-runs in one launch per call, one workgroup per problem.  Local and global bundle adjustment are
-not part of this package.
+runs in one launch per call, one workgroup per problem.  The Sim3 optimisation of a loop candidate
+(two optimize() calls with the pair classification between and after them) likewise.  Local and
+global bundle adjustment are not part of this package.
 """
 from __future__ import annotations
 
@@ -33,6 +35,33 @@ INFO_DTYPE = np.dtype([("n_initial", "<i4"), ("n_bad", "<i4"), ("rounds", "<i4")
 assert INFO_DTYPE.itemsize == ctypes.sizeof(PoseOptInfo) == 48
 
 
+class Sim3OptInfo(ctypes.Structure):
+    """orb_sim3_opt_info_t."""
+
+    _fields_ = [("n_correspondences", ctypes.c_int32), ("n_bad", ctypes.c_int32), ("more_iterations", ctypes.c_int32),
+                ("iterations", ctypes.c_int32 * 2), ("trials", ctypes.c_int32), ("lambda_", ctypes.c_double),
+                ("chi2", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"n_correspondences": self.n_correspondences, "n_bad": self.n_bad,
+                "more_iterations": self.more_iterations, "iterations": list(self.iterations), "trials": self.trials,
+                "lambda": self.lambda_, "chi2": self.chi2}
+
+
+SIM3_INFO_DTYPE = np.dtype([("n_correspondences", "<i4"), ("n_bad", "<i4"), ("more_iterations", "<i4"),
+                            ("iterations", "<i4", (2,)), ("trials", "<i4"), ("lambda", "<f8"), ("chi2", "<f8")])
+assert SIM3_INFO_DTYPE.itemsize == ctypes.sizeof(Sim3OptInfo) == 40
+
+
+def _sim3_13(sim3) -> np.ndarray:
+    """13 floats (R row-major, t, s) from that, or from a (R, t, s) triple."""
+    if isinstance(sim3, (tuple, list)) and len(sim3) == 3:
+        R, t, s = sim3
+        sim3 = np.concatenate([np.asarray(R, np.float32).reshape(9), np.asarray(t, np.float32).reshape(3),
+                               np.float32([s])])
+    return np.ascontiguousarray(sim3, np.float32).reshape(13)
+
+
 def inv_level_sigma2(level_sigma2) -> np.ndarray:
     """mvInvLevelSigma2[i] = 1 / mvLevelSigma2[i], a float division (Frame.cc:105-107)."""
     return (np.float32(1.0) / np.ascontiguousarray(level_sigma2, np.float32)).astype(np.float32)
@@ -46,7 +75,8 @@ def _pose12(pose) -> np.ndarray:
 
 
 class Optimizer:
-    """The GPU half of the reference's Optimizer: ``pose_optimization`` and its batch form."""
+    """The GPU half of the reference's Optimizer: ``pose_optimization``, ``optimize_sim3`` and their
+    batch forms."""
 
     def __init__(self, device: int = 0):
         self._lib = hip_lib()
@@ -135,4 +165,84 @@ class Optimizer:
             ptr(d_kps), ptr(d_counts), cap, S, ptr(frame_of), ptr(d_mp_pos.contiguous()), ptr(d_has_mp.contiguous()),
             ptr(tab), len(tab), ptr(K4), ptr(d_pose_in.contiguous()), ptr(out["pose"]), ptr(out.get("pose_f64")),
             ptr(out["outlier"]), ptr(out["n_inliers"]), ptr(out.get("info")), ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def optimize_sim3(self, x3dc1, x3dc2, obs1, obs2, inv_sigma2_1, sigma2_2, K1, K2, sim3_in, th2: float = 10.0,
+                      usable=None, want_info: bool = True) -> dict:
+        """One loop candidate (host buffers, synchronous): Optimizer::OptimizeSim3(pKF1, pKF2,
+        vpMatches1, g2oS12, th2).  Slot i is keypoint i of KF1: x3dc1 / x3dc2 (n, 3) the two
+        MapPoints in their own keyframe's camera frame, obs1 / obs2 (n, 2) the undistorted positions
+        of keypoint i and of its partner i2 in KF2, inv_sigma2_1 (n,) = GetInvSigma2(octave1),
+        sigma2_2 (n,) = GetSigma2(octave2) (the reference weights e21 with sigma2, not its
+        inverse); usable (n,) flags, None = all.  K1 / K2: fx, fy, cx, cy.  sim3_in: 13 floats (R
+        row-major, t, s) or an (R, t, s) triple.  Returns kept (n,) bool (the slot is still matched),
+        n_inliers (0 when fewer than 10 pairs survive the first classification: the Sim3 is then the
+        input's), sim3 (13,) float32, sim3_f64 (8,) = qx qy qz qw t s, R, t, s and info."""
+        x1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3)
+        x2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        o1 = np.ascontiguousarray(obs1, np.float32).reshape(-1, 2)
+        o2 = np.ascontiguousarray(obs2, np.float32).reshape(-1, 2)
+        w1 = np.ascontiguousarray(inv_sigma2_1, np.float32).reshape(-1)
+        w2 = np.ascontiguousarray(sigma2_2, np.float32).reshape(-1)
+        us = None if usable is None else np.ascontiguousarray(usable, np.uint8).reshape(-1)
+        n = len(x1)
+        if any(len(a) != n for a in (x2, o1, o2, w1, w2)) or (us is not None and len(us) != n):
+            raise ValueError("every per-slot array must hold one entry per slot")
+        k1 = np.ascontiguousarray(K1, np.float32).reshape(4)
+        k2 = np.ascontiguousarray(K2, np.float32).reshape(4)
+        sin = _sim3_13(sim3_in)
+        kept, out64, out32 = np.zeros(max(n, 1), np.uint8), np.zeros(8, np.float64), np.zeros(13, np.float32)
+        ninl, info = ctypes.c_int32(0), Sim3OptInfo()
+        check(self._lib.orb_optimize_sim3(
+            n, ptr(x1), ptr(x2), ptr(o1), ptr(o2), ptr(w1), ptr(w2), ptr(us), ptr(k1), ptr(k2), float(th2), ptr(sin),
+            ptr(kept), ptr(out64), ptr(out32), ctypes.addressof(ninl),
+            ctypes.addressof(info) if want_info else None, self.device))
+        out = {"kept": kept[:n].astype(bool), "n_inliers": int(ninl.value), "sim3": out32, "sim3_f64": out64,
+               "R": out32[:9].reshape(3, 3), "t": out32[9:12], "s": float(out32[12])}
+        if want_info:
+            out["info"] = info.as_dict()
+        return out
+
+    def optimize_sim3_batch_device(self, d_kps, d_counts, pair_a, pair_b, d_match, d_mp_pos, d_mp_bad, d_pose,
+                                   level_sigma2, K, d_sim3_in, th2: float = 10.0, want_f64: bool = True,
+                                   want_info: bool = True, stream=None) -> dict:
+        """S loop candidates on device-resident data (orb_optimize_sim3_batch_device), laid out as
+        for ``Sim3Consensus.check_batch_device``: d_kps (B, cap, 28) / d_counts (B,), pair_a /
+        pair_b (S,) int32 device tensors, d_match (S, cap) int32 as SearchByBoW (kf_kf) or
+        SearchBySim3 leaves it, d_mp_pos (B, cap, 3) float32, d_mp_bad (B, cap) uint8 or None, d_pose
+        (B, 12) float32; level_sigma2: the host level table (its float inverse is taken here as
+        Frame.cc:105-107 does), K: fx, fy, cx, cy; d_sim3_in (S, 13) float32.  Returns device tensors
+        match (S, cap) int32 (the row with the cleared slots at -1), sim3 (S, 13) float32, sim3_f64
+        (S, 8), n_inliers (S,) and info (S, 40) uint8 (view it as SIM3_INFO_DTYPE on the host).
+        Asynchronous on `stream`."""
+        import torch
+
+        S, cap = int(pair_a.shape[0]), int(d_kps.shape[1])
+        B = int(d_kps.shape[0])
+        if tuple(d_match.shape) != (S, cap) or tuple(d_mp_pos.shape) != (B, cap, 3) or tuple(d_pose.shape) != (B, 12) \
+                or tuple(d_sim3_in.shape) != (S, 13) or (d_mp_bad is not None and tuple(d_mp_bad.shape) != (B, cap)):
+            raise ValueError("d_match must be (S, cap), d_mp_pos (B, cap, 3), d_mp_bad (B, cap), d_pose (B, 12) "
+                             "and d_sim3_in (S, 13)")
+        if d_match.dtype != torch.int32 or d_mp_pos.dtype != torch.float32 or d_pose.dtype != torch.float32 \
+                or d_sim3_in.dtype != torch.float32 or (d_mp_bad is not None and d_mp_bad.dtype != torch.uint8):
+            raise ValueError("d_match must be int32, d_mp_pos / d_pose / d_sim3_in float32 and d_mp_bad uint8")
+        dev = d_kps.device
+        tab = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        inv = inv_level_sigma2(tab)
+        K4 = np.ascontiguousarray(K, np.float32).reshape(4)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            out = {"match": torch.empty((S, cap), dtype=torch.int32, device=dev),
+                   "sim3": torch.empty((S, 13), dtype=torch.float32, device=dev),
+                   "n_inliers": torch.empty((S,), dtype=torch.int32, device=dev)}
+            if want_f64:
+                out["sim3_f64"] = torch.empty((S, 8), dtype=torch.float64, device=dev)
+            if want_info:
+                out["info"] = torch.empty((S, SIM3_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        check(self._lib.orb_optimize_sim3_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, S, ptr(pair_a), ptr(pair_b), ptr(d_match.contiguous()),
+            ptr(d_mp_pos.contiguous()), ptr(d_mp_bad.contiguous()) if d_mp_bad is not None else None,
+            ptr(d_pose.contiguous()), ptr(tab), ptr(inv), len(tab), ptr(K4), float(th2), ptr(d_sim3_in.contiguous()),
+            ptr(out["match"]), ptr(out["sim3"]), ptr(out.get("sim3_f64")), ptr(out["n_inliers"]),
+            ptr(out.get("info")), ctypes.c_void_p(s.cuda_stream)))
         return out
