@@ -25,12 +25,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define FCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // The reference camera (Tracking.cc:52-70): K = [fx 0 cx; 0 fy cy; 0 0 1], mDistCoef =
 // (k1, k2, p1, p2); cvUndistortPoints widens both to double, k[4..7] = 0.
 struct Camera {
@@ -99,13 +93,13 @@ int camera_of(const float* K4, const float* dist4, Camera* c) {
 // d + out_off into `out`.
 template <class F>
 int host_call(int device, const void* in, size_t bytes_in, size_t out_off, size_t bytes_out, void* out, F launch) {
-    if (device < 0) FCHK(hipGetDevice(&device));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
     OrbHostCtx* C = orb_internal_thread_ctx(device);
     if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
     const size_t total = out_off + bytes_out;
     if (int r = C->reserve(total, total)) return r;
     std::memcpy(C->pinned, in, bytes_in);
-    FCHK(hipMemcpyAsync(C->buf, C->pinned, bytes_in, hipMemcpyHostToDevice, C->stream));
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, C->pinned, bytes_in, hipMemcpyHostToDevice, C->stream));
     launch(C->buf, C->stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
@@ -131,7 +125,7 @@ int orb_undistort_keypoints_batch_device(const orb_keypoint_t* d_kps, const int3
     const long long n = (long long)B * cap;
     hipLaunchKernelGGL(k_undistort, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_kps,
                        d_counts, cap, B, cam, d_kps_un);
-    FCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 

@@ -1,0 +1,347 @@
+// orb_g2o_math.h — the double-precision restatement of g2o and Eigen that the GPU optimizers share
+// (orb_optimizer.hip: PoseOptimization; orb_sim3opt.hip: OptimizeSim3, §14).
+//
+// One definition each of the quaternion / rotation helpers, the Huber kernel, Eigen's dense LDLT
+// solve, the Levenberg bookkeeping of optimization_algorithm_levenberg.cpp, the workgroup sum and
+// the prepare kernels' compaction step.  The units that include it are built -ffp-contract=off;
+// every sum here has one written order, and that order is part of the contract.
+//
+// Functions marked ORB_G2O_FN use only + - * /, sqrt, fabs and comparisons, all correctly rounded
+// on the host and on the device: the same source compiled by a plain C++ compiler gives the same
+// bits (tests/native/g2o_math_host.cpp pins them against the CPU models).  What calls
+// sin / cos / pow or a wave intrinsic is device code only and sits in the __HIPCC__ block below.
+#pragma once
+#include <cfloat>
+#include <cmath>
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#define ORB_G2O_FN __host__ __device__
+#else
+#define ORB_G2O_FN
+#endif
+
+ORB_G2O_FN static inline __attribute__((always_inline)) void cross3(const double* a, const double* b, double* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Eigen's Quaternion * Vector3: v + w * 2(q x v) + q x 2(q x v); q is x y z w
+ORB_G2O_FN static inline __attribute__((always_inline)) void rotate(const double* q, const double* v, double* o) {
+    double uv[3], c[3];
+    cross3(q, v, uv);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
+    cross3(q, uv, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = v[k] + q[3] * uv[k] + c[k];
+}
+
+// Eigen's Quaternion * Quaternion (SE3Quat::operator*, Sim3::operator*)
+ORB_G2O_FN static inline __attribute__((always_inline)) void quat_mul(const double* a, const double* b, double* o) {
+    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+}
+
+// Eigen's Quaterniond(Matrix3d), m row-major.  Eigen picks i = argmax of the diagonal (the first
+// largest: i = 0; if (m11 > m00) i = 1; if (m22 > m_ii) i = 2) and indexes by i, j = (i + 1) % 3,
+// k = (j + 1) % 3.  That is written out here as one branch per i, which is the form kept of the two
+// this tree had: every index is a constant, so q and m stay in registers on the device, and each
+// branch can be read against Eigen's line by line.  For every input without a NaN on the diagonal
+// the branch taken and the order of each sum are those of the indexed form.
+ORB_G2O_FN static inline void quat_from_matrix(const double* m, double* q) {
+    double t = m[0] + m[4] + m[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t;
+        q[1] = (m[2] - m[6]) * t;
+        q[2] = (m[3] - m[1]) * t;
+    } else if (m[0] >= m[4] && m[0] >= m[8]) {  // i = 0: !(m11 > m00) && !(m22 > m00)
+        t = sqrt(m[0] - m[4] - m[8] + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[7] - m[5]) * t;
+        q[1] = (m[3] + m[1]) * t;
+        q[2] = (m[6] + m[2]) * t;
+    } else if (m[4] > m[0] && m[4] >= m[8]) {  // i = 1
+        t = sqrt(m[4] - m[8] - m[0] + 1.0);
+        q[1] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[2] - m[6]) * t;
+        q[2] = (m[7] + m[5]) * t;
+        q[0] = (m[1] + m[3]) * t;
+    } else {  // i = 2
+        t = sqrt(m[8] - m[0] - m[4] + 1.0);
+        q[2] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3] - m[1]) * t;
+        q[0] = (m[2] + m[6]) * t;
+        q[1] = (m[5] + m[7]) * t;
+    }
+}
+
+// Eigen's toRotationMatrix, row-major
+ORB_G2O_FN static inline void matrix_from_quat(const double* q, double* R) {
+    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
+    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
+    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
+}
+
+// O = hat(omega) and O2 = O * O, row-major; each entry of O2 a three-term row sum, left to right
+ORB_G2O_FN static inline __attribute__((always_inline)) void hat_sq(const double* om, double* O, double* O2) {
+    O[0] = 0, O[1] = -om[2], O[2] = om[1];
+    O[3] = om[2], O[4] = 0, O[5] = -om[0];
+    O[6] = -om[1], O[7] = om[0], O[8] = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = O[3 * i] * O[j];
+            s += O[3 * i + 1] * O[3 + j];
+            s += O[3 * i + 2] * O[6 + j];
+            O2[3 * i + j] = s;
+        }
+}
+
+// RobustKernelHuber::robustify: rho[0], rho[1]
+ORB_G2O_FN static inline __attribute__((always_inline)) void huber(double e, double delta, double dsqr, double* rho0,
+                                                                   double* rho1) {
+    if (e <= dsqr) {
+        *rho0 = e, *rho1 = 1.;
+    } else {
+        const double sqrte = sqrt(e);
+        *rho0 = 2 * sqrte * delta - dsqr;
+        *rho1 = delta / sqrte;
+    }
+}
+
+ORB_G2O_FN static inline __attribute__((always_inline)) void cswap(bool c, double& a, double& b) {
+    const double ta = a, tb = b;
+    a = c ? tb : ta;
+    b = c ? ta : tb;
+}
+
+// Eigen::LDLT of the N x N A (full symmetric storage, overwritten) and the solve of A x = b
+// (linear_solver_dense.h:104-112; Eigen is not in the reference tree: this follows Eigen 3's
+// documented algorithm).  Diagonal pivoting on the largest |a_ii|, the first of equals; the sign is
+// tracked over the pivots; false, x untouched, when the matrix is not positive (LDLT::isPositive).
+// Every loop is unrolled and every index is a compile-time constant: the pivot exchanges are
+// selects, so on the device A stays in registers.
+template <int N>
+ORB_G2O_FN static inline bool ldlt(double* A, const double* b, double* x) {
+    int tr[N];
+    int sign = 0;  // 0 zero, 1 positive semi-definite, -1 negative semi-definite, 2 indefinite
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        int p = k;
+        double big = fabs(A[(N + 1) * k]);
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            const double v = fabs(A[(N + 1) * i]);
+            const bool g = v > big;
+            big = g ? v : big;
+            p = g ? i : p;
+        }
+        tr[k] = p;
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            const bool sw = p == i;
+#pragma unroll
+            for (int j = 0; j < N; ++j) cswap(sw, A[N * k + j], A[N * i + j]);
+#pragma unroll
+            for (int j = 0; j < N; ++j) cswap(sw, A[N * j + k], A[N * j + i]);
+        }
+        double temp[N];
+#pragma unroll
+        for (int j = 0; j < k; ++j) temp[j] = A[(N + 1) * j] * A[N * k + j];
+#pragma unroll
+        for (int j = 0; j < k; ++j) A[(N + 1) * k] -= A[N * k + j] * temp[j];
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            double s = A[N * i + k];
+#pragma unroll
+            for (int j = 0; j < k; ++j) s -= A[N * i + j] * temp[j];
+            A[N * i + k] = s;
+        }
+        const double akk = A[(N + 1) * k];
+        if (fabs(akk) > 0) {
+#pragma unroll
+            for (int i = k + 1; i < N; ++i) A[N * i + k] /= akk;
+        }
+        if (sign == 1) {
+            if (akk < 0) sign = 2;
+        } else if (sign == -1) {
+            if (akk > 0) sign = 2;
+        } else if (sign == 0) {
+            if (akk > 0) sign = 1;
+            else if (akk < 0) sign = -1;
+        }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    double y[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) y[k] = b[k];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) cswap(tr[k] == i, y[k], y[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int j = 0; j < i; ++j) y[i] -= A[N * i + j] * y[j];
+    }
+    const double tol = 1.0 / DBL_MAX;
+#pragma unroll
+    for (int i = 0; i < N; ++i) y[i] = fabs(A[(N + 1) * i]) > tol ? y[i] / A[(N + 1) * i] : 0.0;
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+#pragma unroll
+        for (int j = i + 1; j < N; ++j) y[i] -= A[N * j + i] * y[j];
+    }
+#pragma unroll
+    for (int k = N - 1; k >= 0; --k) {
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) cswap(tr[k] == i, y[k], y[i]);
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = y[k];
+    return true;
+}
+
+// ---- Levenberg bookkeeping (optimization_algorithm_levenberg.cpp:61-189) ----------------------
+// The solve kernels keep H as the reduced upper triangle, row-major: N (N + 1) / 2 values `tri`.
+
+// computeLambdaInit: 1e-5 * max |h_jj|
+template <int N>
+ORB_G2O_FN static inline double lm_lambda_init(const double* tri) {
+    double mx = 0.;
+#pragma unroll
+    for (int j = 0, c = 0; j < N; c += N - j, ++j) {  // std::max(fabs(h_jj), maxDiagonal)
+        const double v = fabs(tri[c]);
+        mx = v < mx ? mx : v;
+    }
+    return 1e-5 * mx;
+}
+
+// A = H + lambda I, full symmetric storage, as the dense solver is handed it
+template <int N>
+ORB_G2O_FN static inline void lm_damped(const double* tri, double lambda, double* A) {
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int k = j; k < N; ++k) A[N * j + k] = A[N * k + j] = tri[c++];
+#pragma unroll
+    for (int j = 0; j < N; ++j) A[(N + 1) * j] += lambda;
+}
+
+// computeScale: what the decrease of chi2 is divided by to give the gain ratio rho
+template <int N>
+ORB_G2O_FN static inline double lm_scale(const double* x, double lambda, const double* b) {
+    double scale = 0.;
+#pragma unroll
+    for (int j = 0; j < N; ++j) scale += x[j] * (lambda * x[j] + b[j]);
+    scale += 1e-3;
+    return scale;
+}
+
+// After the trials of one iteration: Terminate (the trial limit, or no change at all), then
+// three iterations in a row that gained less than a thousandth of chi2
+ORB_G2O_FN static inline bool lm_stop(int qmax, double rho, double ini, double cur, int& bad_steps) {
+    if (qmax == 10 || rho == 0) return true;
+    if ((ini - cur) * 1e3 < ini) ++bad_steps;
+    else bad_steps = 0;
+    return bad_steps >= 3;
+}
+
+#ifdef __HIPCC__
+
+// One trial's verdict: accepted (true) scales lambda by 1 - (2 rho - 1)^3 clamped to [1/3, 2/3] and
+// resets ni; rejected multiplies lambda by ni and doubles ni (the caller restores its backup).
+__device__ static inline bool lm_accept(double rho, double chi2_trial, double& lambda, double& ni) {
+    if (rho > 0 && isfinite(chi2_trial)) {
+        double alpha = 1. - pow(2 * rho - 1, 3.0);
+        alpha = 2. / 3. < alpha ? 2. / 3. : alpha;           // std::min(alpha, upper)
+        const double f = 1. / 3. < alpha ? alpha : 1. / 3.;  // std::max(lower, alpha)
+        lambda *= f;
+        ni = 2;
+        return true;
+    }
+    lambda *= ni;
+    ni *= 2;
+    return false;
+}
+
+// The rotation of exp(omega) from hat_sq's O, O2 and theta = |omega| (se3quat.h:237-249,
+// sim3.h:118-128): I + O + O2 below 1e-5, Rodrigues' formula above
+__device__ static inline void rodrigues(const double* O, const double* O2, double theta, double* R) {
+    if (theta < 0.00001) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k];
+    } else {
+        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + a * O[k]) + b * O2[k];
+    }
+}
+
+constexpr int G2O_WAVES = 4;  // both optimizers run 256-thread workgroups
+
+// Sum of v[0..W) over the workgroup, in a fixed order (an xor butterfly across the wave, lane 0 of
+// each wave to its LDS row, the waves in order); every thread gets the same bits.
+template <int W, int NACC>
+__device__ __forceinline__ void block_sum(double* v, double (*s_red)[NACC]) {
+    static_assert(W <= NACC, "the LDS row holds W values");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m);
+    }
+    __syncthreads();  // the readers of the last reduction are done
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) s_red[wave][k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        double s = s_red[0][k];
+#pragma unroll
+        for (int w = 1; w < G2O_WAVES; ++w) s += s_red[w][k];
+        v[k] = s;
+    }
+}
+
+// One step of an index-ordered compaction over the workgroup: ballot + popcount prefix in the wave,
+// the wave totals through s_wtot[G2O_WAVES].  Returns the thread's output slot (-1 where !ok) and
+// advances `base`, which every thread keeps, by the step's total.  Every thread of the workgroup
+// calls it; it may be called again at once.
+__device__ __forceinline__ int compact_slot(bool ok, int* s_wtot, int& base) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) s_wtot[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int w = 0; w < G2O_WAVES; ++w) {
+        const int t = s_wtot[w];
+        if (w < wave) off += t;
+        tot += t;
+    }
+    base += tot;
+    __syncthreads();  // s_wtot may be written again
+    return ok ? off + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+}
+
+#endif  // __HIPCC__

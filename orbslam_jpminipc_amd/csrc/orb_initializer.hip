@@ -40,12 +40,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define ICHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 constexpr int IN_MAX_CAP = 8192;
 constexpr int IN_MAX_HYP = 1024;
 constexpr int IN_TILE = 64;                          // hypotheses per workgroup = lanes of the chain wave
@@ -313,11 +307,12 @@ int launch(const InitArgs& a, hipStream_t st) {
     const int tiles = (a.n_hyp + IN_TILE - 1) / IN_TILE;
     const size_t lds = (size_t)IN_TERM_BYTES + (size_t)a.cap * sizeof(float4);
     if (lds > 48 * 1024)
-        ICHK(hipFuncSetAttribute((const void*)k_init_scores, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        ORB_HIPCHK(hipFuncSetAttribute((const void*)k_init_scores, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       150 * 1024));
     hipLaunchKernelGGL(k_init_scores, dim3((unsigned)((size_t)a.P * tiles), 2), dim3(IN_THREADS), lds, st, a, tiles);
-    ICHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_init_best, dim3(a.P, 2), dim3(IN_BEST_THREADS), 0, st, a);
-    ICHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -405,11 +400,11 @@ int orb_initializer_check(const orb_keypoint_t* kps1, int n1, const orb_keypoint
             return fail(ORB_EINVAL, "initializer: matches12[" + std::to_string(i) + "] = " +
                                         std::to_string(matches12[i]) + " is outside [-1, n2)");
     int ndev = 0;
-    ICHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ICHK(hipGetDevice(&device));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
     OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
     if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ICHK(hipSetDevice(device));
+    ORB_HIPCHK(hipSetDevice(device));
     // the pair as a 2-frame batch with one pair (0, 1); staging:
     // in:  [kps 2 x cap | counts 2, f1, f2 | matches12 cap | H21 | H12 | F21]
     // out: [scores_h | scores_f | best 2 | best_score 2 | n_matches | inliers 2 x cap]
@@ -432,7 +427,7 @@ int orb_initializer_check(const orb_keypoint_t* kps1, int n1, const orb_keypoint
         std::memcpy(hp + oH12, H12, hyp);
     }
     if (F21) std::memcpy(hp + oF, F21, hyp);
-    ICHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
     uint8_t* d = C->buf;
     InitArgs a{};
     a.kps = (const orb_keypoint_t*)(d + oK);

@@ -61,12 +61,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define KCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // score += term of every lane in `mask`, lowest lane first (mask is wave-uniform).
 __device__ inline double ordered_add(double score, double term, unsigned long long mask) {
     while (mask) {
@@ -582,61 +576,61 @@ struct orb_keyframe_db {
 
     // The host waits for the last device entry point's work.
     int wait_pending() {
-        if (pending) KCHK(hipEventSynchronize(done));
+        if (pending) ORB_HIPCHK(hipEventSynchronize(done));
         pending = false;
         return ORB_OK;
     }
     // A host entry point (synchronous, on the handle's stream) begins.
     int enter_host() {
-        KCHK(hipSetDevice(device));
+        ORB_HIPCHK(hipSetDevice(device));
         return wait_pending();
     }
     // A device entry point begins / has enqueued its work on the caller's stream `s`.
     int enter_device(hipStream_t s) {
-        KCHK(hipSetDevice(device));
-        if (pending) KCHK(hipStreamWaitEvent(s, done, 0));
+        ORB_HIPCHK(hipSetDevice(device));
+        if (pending) ORB_HIPCHK(hipStreamWaitEvent(s, done, 0));
         return ORB_OK;
     }
     int leave_device(hipStream_t s) {
-        KCHK(hipEventRecord(done, s));
+        ORB_HIPCHK(hipEventRecord(done, s));
         pending = true;
         return ORB_OK;
     }
 
     int reset_device(hipStream_t s) {
-        KCHK(hipMemsetAsync(d_len, 0xFF, (size_t)maxKF * 4, s));
-        KCHK(hipMemsetAsync(d_covN, 0, (size_t)maxKF, s));
-        KCHK(hipMemsetAsync(d_reloc, 0, (size_t)maxKF * 4, s));
-        KCHK(hipMemsetAsync(d_seq, 0, (size_t)maxKF * 4, s));
-        KCHK(hipMemsetAsync(d_off, 0, (size_t)maxKF * 4, s));
+        ORB_HIPCHK(hipMemsetAsync(d_len, 0xFF, (size_t)maxKF * 4, s));
+        ORB_HIPCHK(hipMemsetAsync(d_covN, 0, (size_t)maxKF, s));
+        ORB_HIPCHK(hipMemsetAsync(d_reloc, 0, (size_t)maxKF * 4, s));
+        ORB_HIPCHK(hipMemsetAsync(d_seq, 0, (size_t)maxKF * 4, s));
+        ORB_HIPCHK(hipMemsetAsync(d_off, 0, (size_t)maxKF * 4, s));
         return ORB_OK;
     }
 
     int alloc() {
-        KCHK(hipSetDevice(device));
-        KCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        KCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        ORB_HIPCHK(hipSetDevice(device));
+        ORB_HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        ORB_HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         const size_t E = (size_t)std::max<long long>(maxEntries, 1), N = (size_t)maxKF;
         for (int b = 0; b < 2; ++b) {
-            KCHK(hipMalloc(&d_poolW[b], E * 4));
-            KCHK(hipMalloc(&d_poolV[b], E * 8));
+            ORB_HIPCHK(hipMalloc(&d_poolW[b], E * 4));
+            ORB_HIPCHK(hipMalloc(&d_poolV[b], E * 8));
         }
-        KCHK(hipMalloc(&d_off, N * 4));
-        KCHK(hipMalloc(&d_len, N * 4));
-        KCHK(hipMalloc(&d_newOff, N * 4));
-        KCHK(hipMalloc(&d_cov, N * KFDB_MAX_COV * 4));
-        KCHK(hipMalloc(&d_seq, N * 4));
-        KCHK(hipMalloc(&d_reloc, N * 4));
-        KCHK(hipMalloc(&d_covN, N));
-        KCHK(hipMalloc(&d_conn, N));
+        ORB_HIPCHK(hipMalloc(&d_off, N * 4));
+        ORB_HIPCHK(hipMalloc(&d_len, N * 4));
+        ORB_HIPCHK(hipMalloc(&d_newOff, N * 4));
+        ORB_HIPCHK(hipMalloc(&d_cov, N * KFDB_MAX_COV * 4));
+        ORB_HIPCHK(hipMalloc(&d_seq, N * 4));
+        ORB_HIPCHK(hipMalloc(&d_reloc, N * 4));
+        ORB_HIPCHK(hipMalloc(&d_covN, N));
+        ORB_HIPCHK(hipMalloc(&d_conn, N));
         while ((size_t)pstride < N) pstride <<= 1;
-        KCHK(hipMalloc(&d_qbuf, 16 + (size_t)KFDB_MAX_WORDS * 12));
+        ORB_HIPCHK(hipMalloc(&d_qbuf, 16 + (size_t)KFDB_MAX_WORDS * 12));
         resOff = (std::max(16 + (size_t)KFDB_MAX_WORDS * 12, N) + 255) & ~(size_t)255;
-        KCHK(hipHostMalloc(&h_stage, resOff + (N + 1) * 4, hipHostMallocDefault));
+        ORB_HIPCHK(hipHostMalloc(&h_stage, resOff + (N + 1) * 4, hipHostMallocDefault));
         int st = reset_device(stream);
         if (st) return st;
-        KCHK(hipMemsetAsync(d_cov, 0xFF, N * KFDB_MAX_COV * 4, stream));
-        KCHK(hipStreamSynchronize(stream));
+        ORB_HIPCHK(hipMemsetAsync(d_cov, 0xFF, N * KFDB_MAX_COV * 4, stream));
+        ORB_HIPCHK(hipStreamSynchronize(stream));
         return reserve_queries(1);
     }
 
@@ -664,17 +658,17 @@ struct orb_keyframe_db {
         qCap = 0;
         lastQ = 0;
         const size_t n = (size_t)Q * maxKF, np = (size_t)Q * pstride;
-        KCHK(hipMalloc(&d_common, n * 4));
-        KCHK(hipMalloc(&d_first, n * 4));
-        KCHK(hipMalloc(&d_score, n * 8));
-        KCHK(hipMalloc(&d_scored, n));
-        KCHK(hipMalloc(&d_si, n * 4));
-        KCHK(hipMalloc(&d_acc, n * 4));
-        KCHK(hipMalloc(&d_bestKF, n * 4));
-        KCHK(hipMalloc(&d_firstPos, n * 4));
-        KCHK(hipMalloc(&d_entry, n));
-        KCHK(hipMalloc(&d_key, np * 8));
-        KCHK(hipMalloc(&d_pay, np * 4));
+        ORB_HIPCHK(hipMalloc(&d_common, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_first, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_score, n * 8));
+        ORB_HIPCHK(hipMalloc(&d_scored, n));
+        ORB_HIPCHK(hipMalloc(&d_si, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_acc, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_bestKF, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_firstPos, n * 4));
+        ORB_HIPCHK(hipMalloc(&d_entry, n));
+        ORB_HIPCHK(hipMalloc(&d_key, np * 8));
+        ORB_HIPCHK(hipMalloc(&d_pay, np * 4));
         qCap = Q;
         return ORB_OK;
     }
@@ -692,12 +686,12 @@ struct orb_keyframe_db {
             t += len[i];
         }
         if (hi > 0) {
-            KCHK(hipMemcpyAsync(d_newOff, newOff.data(), (size_t)hi * 4, hipMemcpyHostToDevice, s));
-            KCHK(hipStreamSynchronize(s));  // newOff is a local
+            ORB_HIPCHK(hipMemcpyAsync(d_newOff, newOff.data(), (size_t)hi * 4, hipMemcpyHostToDevice, s));
+            ORB_HIPCHK(hipStreamSynchronize(s));  // newOff is a local
             hipLaunchKernelGGL(k_kfdb_compact, dim3(std::min((hi + 3) / 4, 1024)), dim3(256), 0, s, hi, d_len, d_off,
                                d_newOff, d_poolW[cur], d_poolV[cur], d_poolW[cur ^ 1], d_poolV[cur ^ 1]);
-            KCHK(hipGetLastError());
-            KCHK(hipMemcpyAsync(d_off, d_newOff, (size_t)hi * 4, hipMemcpyDeviceToDevice, s));
+            ORB_HIPCHK(hipGetLastError());
+            ORB_HIPCHK(hipMemcpyAsync(d_off, d_newOff, (size_t)hi * 4, hipMemcpyDeviceToDevice, s));
             std::copy(newOff.begin(), newOff.end(), off.begin());
         }
         cur ^= 1;
@@ -740,7 +734,7 @@ struct orb_keyframe_db {
             const int gx = srcW ? std::max(1, std::min((maxLen + 255) / 256, 8)) : 1;
             hipLaunchKernelGGL(k_kfdb_add, dim3(gx, c.n), dim3(256), 0, s, c, srcW, srcV, cap, d_poolW[cur], d_poolV[cur],
                                d_off, d_len, d_seq, d_reloc);
-            KCHK(hipGetLastError());
+            ORB_HIPCHK(hipGetLastError());
         }
         return ORB_OK;
     }
@@ -776,7 +770,7 @@ struct orb_keyframe_db {
             const int gx = std::max(1, std::min((hi + 3) / 4, std::max(8, 2048 / Q)));
             hipLaunchKernelGGL(k_kfdb_scan, dim3(gx, Q), dim3(256), (size_t)ldsCap * 12, s, d_poolW[cur], d_poolV[cur],
                                d_off, d_len, hi, d_w, d_v, d_n, cap, ldsCap, d_common, d_first, d_score, maxKF);
-            KCHK(hipGetLastError());
+            ORB_HIPCHK(hipGetLastError());
         }
         SelArgs A;
         A.hi = hi;
@@ -812,7 +806,7 @@ struct orb_keyframe_db {
             if (!loop && hi > 0) hipLaunchKernelGGL(k_kfdb_chain, dim3((hi + 255) / 256), dim3(256), 0, s, A);
             hipLaunchKernelGGL(k_kfdb_select, dim3(Q), dim3(KFDB_SEL_THREADS), 0, s, A);
         }
-        KCHK(hipGetLastError());
+        ORB_HIPCHK(hipGetLastError());
         return ORB_OK;
     }
 
@@ -835,20 +829,20 @@ struct orb_keyframe_db {
             std::memset(h_stage, 0, (size_t)hi);
             for (int i = 0; i < n_connected; ++i)
                 if (connected[i] >= 0 && connected[i] < hi) h_stage[connected[i]] = 1;
-            KCHK(hipMemcpyAsync(d_conn, h_stage, (size_t)hi, hipMemcpyHostToDevice, s));
-            KCHK(hipStreamSynchronize(s));  // the staging buffer is reused for the query
+            ORB_HIPCHK(hipMemcpyAsync(d_conn, h_stage, (size_t)hi, hipMemcpyHostToDevice, s));
+            ORB_HIPCHK(hipStreamSynchronize(s));  // the staging buffer is reused for the query
         }
         const size_t qbytes = 16 + (size_t)n * 12;
         std::memcpy(h_stage, &n, 4);
         std::memcpy(h_stage + 16, values, (size_t)n * 8);
         std::memcpy(h_stage + 16 + (size_t)n * 8, words, (size_t)n * 4);
-        KCHK(hipMemcpyAsync(d_qbuf, h_stage, qbytes, hipMemcpyHostToDevice, s));
+        ORB_HIPCHK(hipMemcpyAsync(d_qbuf, h_stage, qbytes, hipMemcpyHostToDevice, s));
         // the candidates and their count go straight to the pinned buffer: no copy back
         int32_t* res = (int32_t*)(h_stage + resOff);
         st = query(1, (const uint32_t*)(d_qbuf + 16 + (size_t)n * 8), (const double*)(d_qbuf + 16), (const int*)d_qbuf,
                    n, loop, minScore, res + 1, maxKF, res, s);
         if (st) return st;
-        KCHK(hipStreamSynchronize(s));
+        ORB_HIPCHK(hipStreamSynchronize(s));
         const int cnt = res[0];
         *n_out = cnt;
         if (cnt > out_cap)
@@ -881,10 +875,10 @@ int orb_vocabulary_score_pairs_device(const orb_vocabulary_t* v, int P, const ui
         return fail(ORB_EINVAL, "bad arguments");
     if (cap > KFDB_MAX_WORDS) return fail(ORB_ENOTSUP, "more than 8192 words in a BowVector");
     if (P == 0) return ORB_OK;
-    KCHK(hipSetDevice(orb_internal_vocabulary_device(v)));
+    ORB_HIPCHK(hipSetDevice(orb_internal_vocabulary_device(v)));
     hipLaunchKernelGGL(k_kfdb_pairs, dim3((P + 3) / 4), dim3(256), 0, (hipStream_t)stream, P, d_bow_words,
                        d_bow_values, d_bow_n, cap, d_pair_a, d_pair_b, d_score);
-    KCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -899,7 +893,7 @@ int orb_kfdb_create(const orb_vocabulary_t* voc, int max_keyframes, int64_t max_
         return fail(ORB_EINVAL, "max_keyframes must be in [1, 65536]");
     if (max_entries < 1 || max_entries > INT_MAX) return fail(ORB_EINVAL, "max_entries must be in [1, 2^31)");
     int ndev = 0;
-    KCHK(hipGetDeviceCount(&ndev));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(ORB_EINVAL, "device ordinal out of range");
     auto* db = new orb_keyframe_db();
     db->nWords = nWords;
@@ -933,7 +927,7 @@ int orb_kfdb_clear(orb_keyframe_db_t* db) {
     if (st) return st;
     st = db->reset_device(db->stream);
     if (st) return st;
-    KCHK(hipStreamSynchronize(db->stream));
+    ORB_HIPCHK(hipStreamSynchronize(db->stream));
     std::fill(db->len.begin(), db->len.end(), -1);
     std::fill(db->off.begin(), db->off.end(), 0);
     std::fill(db->seq.begin(), db->seq.end(), 0u);
@@ -964,10 +958,10 @@ int orb_kfdb_add(orb_keyframe_db_t* db, int id, const uint32_t* words, const dou
     st = db->place(1, &id, &n, nullptr, nullptr, 0, s, &offs);
     if (st) return st;
     if (n > 0) {
-        KCHK(hipMemcpyAsync(db->d_poolW[db->cur] + offs[0], words, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        KCHK(hipMemcpyAsync(db->d_poolV[db->cur] + offs[0], values, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        ORB_HIPCHK(hipMemcpyAsync(db->d_poolW[db->cur] + offs[0], words, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        ORB_HIPCHK(hipMemcpyAsync(db->d_poolV[db->cur] + offs[0], values, (size_t)n * 8, hipMemcpyHostToDevice, s));
     }
-    KCHK(hipStreamSynchronize(s));
+    ORB_HIPCHK(hipStreamSynchronize(s));
     return ORB_OK;
 }
 
@@ -982,8 +976,8 @@ int orb_kfdb_add_batch_device(orb_keyframe_db_t* db, int B, const int32_t* ids, 
     int st = db->enter_device(s);
     if (st) return st;
     std::vector<int> lens(B);
-    KCHK(hipMemcpyAsync(lens.data(), d_bow_n, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    KCHK(hipStreamSynchronize(s));
+    ORB_HIPCHK(hipMemcpyAsync(lens.data(), d_bow_n, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    ORB_HIPCHK(hipStreamSynchronize(s));
     for (int b = 0; b < B; ++b) {
         if (lens[b] < 0 || lens[b] > cap) return fail(ORB_EINVAL, "add_batch_device: d_bow_n is not in [0, cap]");
         if (lens[b] > KFDB_MAX_WORDS) return fail(ORB_ENOTSUP, "add_batch_device: more than 8192 words in a BowVector");
@@ -1010,8 +1004,8 @@ int orb_kfdb_erase(orb_keyframe_db_t* db, int id) {
     c.seq[0] = 0;
     hipLaunchKernelGGL(k_kfdb_add, dim3(1, 1), dim3(256), 0, s, c, (const uint32_t*)nullptr, (const double*)nullptr, 0,
                        db->d_poolW[db->cur], db->d_poolV[db->cur], db->d_off, db->d_len, db->d_seq, db->d_reloc);
-    KCHK(hipGetLastError());
-    KCHK(hipStreamSynchronize(s));
+    ORB_HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipStreamSynchronize(s));
     db->liveEntries -= db->len[id];
     db->len[id] = -1;
     db->off[id] = 0;
@@ -1040,8 +1034,8 @@ int orb_kfdb_set_covisible(orb_keyframe_db_t* db, int id, const int32_t* neighbo
     int st = db->enter_host();
     if (st) return st;
     hipLaunchKernelGGL(k_kfdb_set_cov, dim3(1), dim3(64), 0, s, a, db->d_cov, db->d_covN);
-    KCHK(hipGetLastError());
-    KCHK(hipStreamSynchronize(s));
+    ORB_HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipStreamSynchronize(s));
     return ORB_OK;
 }
 
@@ -1091,10 +1085,10 @@ int orb_debug_kfdb_last_query(orb_keyframe_db_t* db, int q, int32_t* common, uin
     const int n = std::min(cap, db->hi);
     if (n > 0) {
         const size_t o = (size_t)q * db->maxKF;
-        KCHK(hipMemcpy(common, db->d_common + o, (size_t)n * 4, hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(first_word, db->d_first + o, (size_t)n * 4, hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(score, db->d_score + o, (size_t)n * 8, hipMemcpyDeviceToHost));
-        KCHK(hipMemcpy(scored, db->d_scored + o, (size_t)n, hipMemcpyDeviceToHost));
+        ORB_HIPCHK(hipMemcpy(common, db->d_common + o, (size_t)n * 4, hipMemcpyDeviceToHost));
+        ORB_HIPCHK(hipMemcpy(first_word, db->d_first + o, (size_t)n * 4, hipMemcpyDeviceToHost));
+        ORB_HIPCHK(hipMemcpy(score, db->d_score + o, (size_t)n * 8, hipMemcpyDeviceToHost));
+        ORB_HIPCHK(hipMemcpy(scored, db->d_scored + o, (size_t)n, hipMemcpyDeviceToHost));
         std::copy(db->seq.begin(), db->seq.begin() + n, seq);
     }
     return n;

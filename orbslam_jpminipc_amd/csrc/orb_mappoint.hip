@@ -30,12 +30,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define DCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 __global__ void __launch_bounds__(64) k_distinctive(const int32_t* __restrict__ offsets,
                                                     const uint8_t* __restrict__ desc,
                                                     const uint8_t* __restrict__ usable, int32_t* __restrict__ bestRow,
@@ -116,7 +110,7 @@ int orb_compute_distinctive_descriptors_device(int M, const int32_t* d_offsets, 
     }
     hipLaunchKernelGGL(k_distinctive, dim3(M), dim3(64), lds, (hipStream_t)stream, d_offsets, d_desc, d_usable,
                        d_best_row, d_out_desc);
-    DCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -134,14 +128,14 @@ int orb_compute_distinctive_descriptors(int M, const int32_t* offsets, const uin
     if (R > 0 && !desc) return fail(ORB_EINVAL, "bad arguments");
     if (max_obs > DD_MAX_OBS) return fail(ORB_ENOTSUP, "more than 4000 observations of one map point");
     int ndev = 0;
-    DCHK(hipGetDeviceCount(&ndev));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(ORB_EINVAL, "device ordinal out of range");
-    DCHK(hipSetDevice(device));
+    ORB_HIPCHK(hipSetDevice(device));
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t oOff = 0, oDesc = al((size_t)(M + 1) * 4), oUse = al(oDesc + (size_t)R * 32),
                  oBest = al(oUse + (size_t)R), oOut = al(oBest + (size_t)M * 4), total = al(oOut + (size_t)M * 32);
     uint8_t* buf = nullptr;
-    DCHK(hipMalloc(&buf, total));
+    ORB_HIPCHK(hipMalloc(&buf, total));
     hipStream_t st = nullptr;
     hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
     int r = ORB_OK;

@@ -1365,12 +1365,6 @@ struct DeviceGuard {
     }
 };
 
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // A call in flight: the arena layout is planned first (offsets), then allocated + uploaded.
 struct Call {
     int device;
@@ -1408,9 +1402,9 @@ struct Call {
             const unsigned grid = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (n16 + 255) / 256));
             hipLaunchKernelGGL(k_stage_copy, dim3(grid), dim3(256), 0, ctx->stream, (uint4*)base,
                                (const uint4*)ctx->pinned, n16, ctx->pinned + (n16 << 4), base + (n16 << 4), tail);
-            HIPCHK(hipGetLastError());
+            ORB_HIPCHK(hipGetLastError());
         } else if (hi) {
-            HIPCHK(hipMemcpyAsync(base, ctx->pinned, hi, hipMemcpyHostToDevice, ctx->stream));
+            ORB_HIPCHK(hipMemcpyAsync(base, ctx->pinned, hi, hipMemcpyHostToDevice, ctx->stream));
         }
         return ORB_OK;
     }
@@ -1438,7 +1432,7 @@ struct Call {
                 *flag = 0;
                 hipLaunchKernelGGL(k_stage_out, dim3(1), dim3(256), 0, ctx->stream, ctx->pinned + lo, base + lo,
                                    (int)(hi - lo), (int*)(ctx->pinned + flagOff), seq);
-                HIPCHK(hipGetLastError());
+                ORB_HIPCHK(hipGetLastError());
                 const auto t0 = std::chrono::steady_clock::now();
                 for (int spin = 0;; ++spin) {
                     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) {
@@ -1448,12 +1442,12 @@ struct Call {
                     if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
                 }
             } else {
-                HIPCHK(hipMemcpyAsync(ctx->pinned + lo, base + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream));
+                ORB_HIPCHK(hipMemcpyAsync(ctx->pinned + lo, base + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream));
             }
         }
         // (the flag is the kernel's last write, nothing of the call runs after it; without it --
         // no results, an error, a call past the bound -- the stream is synchronised)
-        if (!seen) HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (!seen) ORB_HIPCHK(hipStreamSynchronize(ctx->stream));
         inflight = false;
         for (auto& d : pending) std::memcpy(d.first, ctx->pinned + d.second.first, d.second.second);
         pending.clear();
@@ -1527,7 +1521,7 @@ DView make_dview(const Call& C, const orb_frame_view_t* v, const ViewOffs& o, bo
 int launch_grid(const Call& C, const DView& d) {
     hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(1024), 0, C.ctx->stream, d.kps, d.n, d.minX, d.minY, d.invW,
                        d.invH, (int*)d.cellStart, (int*)d.items);
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -1589,7 +1583,7 @@ int run_job(const Call& C, const Job& J0) {
     if (useFix) {
         static std::atomic<bool> fix_attr[64] = {};
         if (!fix_attr[C.device].load()) {
-#define SET_FIX_LDS(M) HIPCHK(hipFuncSetAttribute((const void*)k_resolve_fix<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
+#define SET_FIX_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve_fix<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
             SET_FIX_LDS(M_LOCAL);
             SET_FIX_LDS(M_WINDOW);
             SET_FIX_LDS(M_F2F);
@@ -1613,7 +1607,7 @@ int run_job(const Call& C, const Job& J0) {
             default:
                 return fail(ORB_EINVAL, "matcher mode without a fixed-point resolver");
         }
-        HIPCHK(hipGetLastError());
+        ORB_HIPCHK(hipGetLastError());
         return ORB_OK;
     }
     size_t lds = 0;
@@ -1621,7 +1615,7 @@ int run_job(const Call& C, const Job& J0) {
     if (st) return st;
     static std::atomic<bool> attr_set[64] = {};
     if (!attr_set[C.device].load()) {
-#define SET_RESOLVE_LDS(M) HIPCHK(hipFuncSetAttribute((const void*)k_resolve<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
+#define SET_RESOLVE_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
         SET_RESOLVE_LDS(M_LOCAL);
         SET_RESOLVE_LDS(M_WINDOW);
         SET_RESOLVE_LDS(M_F2F);
@@ -1656,7 +1650,7 @@ int run_job(const Call& C, const Job& J0) {
         default:
             return fail(ORB_EINVAL, "matcher mode without a resolver");
     }
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -1950,7 +1944,7 @@ int orb_features_in_area(const orb_frame_view_t* view, int keyframe, int q, cons
     hipStream_t s = C.ctx->stream;
     hipLaunchKernelGGL(k_query_prep, dim3((q + 255) / 256), dim3(256), 0, s, J);
     hipLaunchKernelGGL(k_query_scan<TOPK>, dim3((q + 3) / 4), dim3(256), 0, s, J);
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     std::vector<int> cnt(q);
     if ((st = C.download(cnt.data(), jo.cnt, (size_t)q * 4)) || (st = C.sync())) return st;
     long long tot = 0;
@@ -1961,9 +1955,9 @@ int orb_features_in_area(const orb_frame_view_t* view, int keyframe, int q, cons
     out_offsets[q] = (int32_t)std::min<long long>(tot, INT_MAX);
     if (tot > capacity) return fail(ORB_ERANGE, "candidate capacity too small");
     if (tot == 0) return ORB_OK;
-    HIPCHK(hipMemcpyAsync(J.areaOff, out_offsets, (size_t)(q + 1) * 4, hipMemcpyHostToDevice, s));
+    ORB_HIPCHK(hipMemcpyAsync(J.areaOff, out_offsets, (size_t)(q + 1) * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_area_fill, dim3((q + 3) / 4), dim3(256), 0, s, J);
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     if ((st = C.download(out_indices, oOut, (size_t)tot * 4)) || (st = C.sync())) return st;
     return ORB_OK;
 }
@@ -2179,7 +2173,7 @@ int orb_search_by_sim3(const orb_frame_view_t* KF1, orb_map_points_t mp1, const 
     if ((st = C.commit())) return st;
     hipLaunchKernelGGL(k_sim3_agree, dim3(1), dim3(256), 0, C.ctx->stream, C.at<int>(o1), KF1->n, C.at<int>(o2),
                        C.at<int>(oo), C.at<int>(on));
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     int nf = 0;
     if ((st = C.download(match12, oo, m1.size() * 4)) || (st = C.download(&nf, on, 4)) || (st = C.sync())) return st;
     *n_found = nf;
@@ -2263,7 +2257,7 @@ extern "C" int orb_frame_is_in_frustum(const orb_frame_view_t* F, orb_map_points
     hipLaunchKernelGGL(k_is_in_frustum, dim3((mps.n + 255) / 256), dim3(256), 0, C.ctx->stream, d, C.at<float>(op),
                        C.at<float>(onr), C.at<float>(omn), C.at<float>(omx), mps.n, viewing_cos_limit,
                        C.at<uint8_t>(oi), C.at<float>(ox), C.at<float>(oy), C.at<int>(ol), C.at<float>(oc));
-    HIPCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     if ((st = C.download(in_view, oi, n)) || (st = C.download(proj_x, ox, n * 4)) ||
         (st = C.download(proj_y, oy, n * 4)) || (st = C.download(level, ol, n * 4)) ||
         (st = C.download(view_cos, oc, n * 4)) || (st = C.sync()))

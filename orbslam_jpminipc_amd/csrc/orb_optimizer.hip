@@ -14,9 +14,11 @@
 //                   the rho[2] term is commented out in base_edge.h:96-102
 //   Levenberg       optimization_algorithm_levenberg.cpp:61-189, update exp(x) * T
 //                   (types_six_dof_expmap.h:104-107, se3quat.h:104-110, 223-257)
-//   dense solver    linear_solver_dense.h:104-112: Eigen::LDLT, refused when not positive (Eigen is
-//                   not in the reference tree: ldlt6 follows Eigen 3's documented algorithm)
+//   dense solver    linear_solver_dense.h:104-112: Eigen::LDLT, refused when not positive
 //   four rounds     Optimizer.cc:242-276
+// The quaternion and rotation helpers, the Huber kernel, ldlt<6>, the Levenberg bookkeeping, the
+// workgroup sum and the compaction step are those of csrc/orb_g2o_math.h, shared with
+// csrc/orb_sim3opt.hip; this unit holds the SE3 state, its edge and the schedule.
 //
 // Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
 // prepare step.  Sums over edges are taken in a fixed order (thread-strided partial sums, an
@@ -44,21 +46,18 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_g2o_math.h"
 #include "orb_internal.h"
 
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-
-#define PCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int PO_MAX_CAP = 8192;
 constexpr int PO_THREADS = 256;
 constexpr int PO_WAVES = PO_THREADS / 64;
+static_assert(PO_WAVES == G2O_WAVES, "block_sum and compact_slot are written for this many waves");
 constexpr int PO_NV = 7;   // X Y Z u v invSigma2 | chi2 of the last evaluation
 constexpr int PO_NACC = 28;  // 21 of H (upper triangle), 6 of b, the robust chi2
 
@@ -92,7 +91,7 @@ struct PoArgs {
 
 __global__ void __launch_bounds__(PO_THREADS) k_po_prepare(PoArgs a) {
     __shared__ int s_wtot[PO_WAVES];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const bool direct = a.n_direct >= 0;
     const int f = direct ? 0 : a.frame_of[s];
     // an index past the frame's count is no edge, so no read leaves the batch arrays
@@ -106,18 +105,8 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_prepare(PoArgs a) {
     for (int i0 = 0; i0 < n_row; i0 += PO_THREADS) {
         const int i = i0 + tid;
         const bool ok = i < n_row && (a.has_mp ? a.has_mp[row + i] != 0 : true);
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) s_wtot[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base, tot = 0;
-#pragma unroll
-        for (int w = 0; w < PO_WAVES; ++w) {
-            const int t = s_wtot[w];
-            if (w < wave) off += t;
-            tot += t;
-        }
-        if (ok) {
-            const int o = off + __popcll(bal & ((1ull << lane) - 1ull));
+        const int o = compact_slot(ok, s_wtot, base);
+        if (o >= 0) {
             float u, v, is2;
             if (direct) {
                 u = a.obs[2 * i], v = a.obs[2 * i + 1], is2 = a.inv_sigma2[i];
@@ -131,8 +120,6 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_prepare(PoArgs a) {
             q[3 * a.cap + o] = (double)u, q[4 * a.cap + o] = (double)v, q[5 * a.cap + o] = (double)is2;
             index[o] = i;
         }
-        base += tot;
-        __syncthreads();
     }
     if (tid == 0) a.n[s] = base;
 }
@@ -141,23 +128,6 @@ struct Pose {
     double q[4];  // x y z w
     double t[3];
 };
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// Eigen's Quaternion * Vector3: v + w * 2(q x v) + q x 2(q x v)
-__device__ __forceinline__ void rotate(const double* q, const double* v, double* o) {
-    double uv[3], c[3];
-    cross3(q, v, uv);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
-    cross3(q, uv, c);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = v[k] + q[3] * uv[k] + c[k];
-}
 
 __device__ __forceinline__ void normalize_rotation(Pose& p) {  // se3quat.h:280-285
     if (p.q[3] < 0) {
@@ -169,69 +139,21 @@ __device__ __forceinline__ void normalize_rotation(Pose& p) {  // se3quat.h:280-
     for (int k = 0; k < 4; ++k) p.q[k] /= n;
 }
 
-// Eigen's Quaterniond(Matrix3d), m row-major
-__device__ void quat_from_matrix(const double* m, double* q) {
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else {
-        int i = 0;
-        if (m[4] > m[0]) i = 1;
-        if (m[8] > m[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
-        q[i] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
-        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
-        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
-    }
-}
-
-// Eigen's toRotationMatrix, row-major
-__device__ void matrix_from_quat(const double* q, double* R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-}
-
 // VertexSE3Expmap::oplusImpl: exp(x) * T with x = (omega, upsilon)
 __device__ Pose exp_update(const double* x, const Pose& T) {
     const double* om = x;
     const double* up = x + 3;
     const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
-    double O2[9], R[9], V[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s = O[3 * i] * O[j];
-            s += O[3 * i + 1] * O[3 + j];
-            s += O[3 * i + 2] * O[6 + j];
-            O2[3 * i + j] = s;
-        }
+    double O[9], O2[9], R[9], V[9];
+    hat_sq(om, O, O2);
+    rodrigues(O, O2, theta, R);
     if (theta < 0.00001) {  // se3quat.h:237-243
 #pragma unroll
-        for (int k = 0; k < 9; ++k) V[k] = R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k];
+        for (int k = 0; k < 9; ++k) V[k] = R[k];
     } else {
-        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta),
-                     c = (theta - sin(theta)) / pow(theta, 3.0);
+        const double b = (1 - cos(theta)) / (theta * theta), c = (theta - sin(theta)) / pow(theta, 3.0);
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const double I = k % 4 == 0 ? 1.0 : 0.0;
-            R[k] = (I + a * O[k]) + b * O2[k];
-            V[k] = (I + b * O[k]) + c * O2[k];
-        }
+        for (int k = 0; k < 9; ++k) V[k] = ((k % 4 == 0 ? 1.0 : 0.0) + b * O[k]) + c * O2[k];
     }
     Pose e;
     quat_from_matrix(R, e.q);
@@ -249,11 +171,7 @@ __device__ Pose exp_update(const double* x, const Pose& T) {
     rotate(e.q, T.t, rt);
 #pragma unroll
     for (int k = 0; k < 3; ++k) r.t[k] += rt[k];
-    const double *a = e.q, *b = T.q;
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    quat_mul(e.q, T.q, r.q);
     normalize_rotation(r);
     return r;
 }
@@ -274,104 +192,6 @@ __device__ __forceinline__ double edge_chi2(const Pose& T, const Cam& c, const d
     err[1] = q[4 * cap + e] - ((Xc[1] / Xc[2]) * c.fy + c.cy);
     const double s = q[5 * cap + e];
     return err[0] * (s * err[0]) + err[1] * (s * err[1]);
-}
-
-// RobustKernelHuber::robustify: rho[0], rho[1]
-__device__ __forceinline__ void huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
-    if (e <= dsqr) {
-        *rho0 = e, *rho1 = 1.;
-    } else {
-        const double sqrte = sqrt(e);
-        *rho0 = 2 * sqrte * delta - dsqr;
-        *rho1 = delta / sqrte;
-    }
-}
-
-// Sum of v[0..W) over the workgroup, in a fixed order; every thread gets the same bits.
-template <int W>
-__device__ __forceinline__ void block_sum(double* v, double (*s_red)[PO_NACC]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m);
-    }
-    __syncthreads();  // the readers of the last reduction are done
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) s_red[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        double s = s_red[0][k];
-#pragma unroll
-        for (int w = 1; w < PO_WAVES; ++w) s += s_red[w][k];
-        v[k] = s;
-    }
-}
-
-// Eigen::LDLT of the 6 x 6 A (full symmetric storage, overwritten) and the solve of A x = b:
-// diagonal pivoting on the largest |a_ii|, the sign tracked over the pivots; false (x untouched)
-// when the matrix is not positive (LDLT::isPositive, linear_solver_dense.h:108).
-__device__ bool ldlt6(double* A, const double* b, double* x) {
-    int tr[6];
-    int sign = 0;  // 0 zero, 1 positive semi-definite, -1 negative semi-definite, 2 indefinite
-    for (int k = 0; k < 6; ++k) {
-        int p = k;
-        double big = fabs(A[7 * k]);
-        for (int i = k + 1; i < 6; ++i)
-            if (fabs(A[7 * i]) > big) big = fabs(A[7 * i]), p = i;
-        tr[k] = p;
-        if (p != k) {
-            for (int j = 0; j < 6; ++j) {
-                const double t = A[6 * k + j];
-                A[6 * k + j] = A[6 * p + j], A[6 * p + j] = t;
-            }
-            for (int j = 0; j < 6; ++j) {
-                const double t = A[6 * j + k];
-                A[6 * j + k] = A[6 * j + p], A[6 * j + p] = t;
-            }
-        }
-        double temp[6];
-        for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
-        for (int j = 0; j < k; ++j) A[7 * k] -= A[6 * k + j] * temp[j];
-        for (int i = k + 1; i < 6; ++i) {
-            double s = A[6 * i + k];
-            for (int j = 0; j < k; ++j) s -= A[6 * i + j] * temp[j];
-            A[6 * i + k] = s;
-        }
-        const double akk = A[7 * k];
-        if (fabs(akk) > 0)
-            for (int i = k + 1; i < 6; ++i) A[6 * i + k] /= akk;
-        if (sign == 1) {
-            if (akk < 0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[6];
-    for (int k = 0; k < 6; ++k) y[k] = b[k];
-    for (int k = 0; k < 6; ++k) {
-        const double t = y[k];
-        y[k] = y[tr[k]], y[tr[k]] = t;
-    }
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < i; ++j) y[i] -= A[6 * i + j] * y[j];
-    const double tol = 1.0 / DBL_MAX;
-    for (int i = 0; i < 6; ++i) y[i] = fabs(A[7 * i]) > tol ? y[i] / A[7 * i] : 0.0;
-    for (int i = 5; i >= 0; --i)
-        for (int j = i + 1; j < 6; ++j) y[i] -= A[6 * j + i] * y[j];
-    for (int k = 5; k >= 0; --k) {
-        const double t = y[k];
-        y[k] = y[tr[k]], y[tr[k]] = t;
-    }
-    for (int k = 0; k < 6; ++k) x[k] = y[k];
-    return true;
 }
 
 __global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
@@ -448,27 +268,12 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
                 acc[27] += rho0;
             }
             block_sum<PO_NACC>(acc, s_red);
-            double H[36], b[6];
-            {
-                int c = 0;
-#pragma unroll
-                for (int j = 0; j < 6; ++j)
-#pragma unroll
-                    for (int k = j; k < 6; ++k) H[6 * j + k] = H[6 * k + j] = acc[c++];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) b[j] = acc[21 + j];
-            }
+            // acc stays as the system: H's upper triangle in acc[0..21), b in acc[21..27)
+            const double* b = acc + 21;
             double cur = acc[27];
-            double temp = cur;
             const double ini = cur;
-            if (it == 0) {  // computeLambdaInit
-                double mx = 0.;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) {  // std::max(fabs(h_jj), maxDiagonal)
-                    const double v = fabs(H[7 * j]);
-                    mx = v < mx ? mx : v;
-                }
-                lambda = 1e-5 * mx;
+            if (it == 0) {
+                lambda = lm_lambda_init<6>(acc);
                 ni = 2.;
                 bad_steps = 0;
             }
@@ -479,11 +284,8 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
                 if (!again) break;
                 const Pose backup = T;
                 double A[36];
-#pragma unroll
-                for (int k = 0; k < 36; ++k) A[k] = H[k];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) A[7 * j] += lambda;
-                const bool ok2 = ldlt6(A, b, x);
+                lm_damped<6>(acc, lambda, A);
+                const bool ok2 = ldlt<6>(A, b, x);
                 T = exp_update(x, T);
                 double t1[1] = {0.};
                 for (int e = tid; e < n; e += PO_THREADS) {
@@ -495,37 +297,16 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
                     t1[0] += rho0;
                 }
                 block_sum<1>(t1, s_red);
-                temp = t1[0];
-                if (!ok2) temp = DBL_MAX;
-                rho = cur - temp;
-                double scale = 0.;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) scale += x[j] * (lambda * x[j] + b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(temp)) {
-                    double alpha = 1. - pow(2 * rho - 1, 3.0);
-                    alpha = 2. / 3. < alpha ? 2. / 3. : alpha;           // std::min(alpha, upper)
-                    const double f = 1. / 3. < alpha ? alpha : 1. / 3.;  // std::max(lower, alpha)
-                    lambda *= f;
-                    ni = 2;
-                    cur = temp;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    T = backup;
-                }
+                const double temp = ok2 ? t1[0] : DBL_MAX;
+                rho = (cur - temp) / lm_scale<6>(x, lambda, b);
+                if (lm_accept(rho, temp, lambda, ni)) cur = temp;
+                else T = backup;
                 ++qmax;
                 ++trials;
                 again = rho < 0 && qmax < 10;  // a NaN rho leaves the loop
             }
             last_chi = cur;
-            if (qmax == 10 || rho == 0) stop = true;  // Terminate
-            if (!stop) {
-                if ((ini - cur) * 1e3 < ini) ++bad_steps;
-                else bad_steps = 0;
-                if (bad_steps >= 3) stop = true;
-            }
+            stop = lm_stop(qmax, rho, ini, cur, bad_steps);
         }
         // classification (Optimizer.cc:251-272)
         __syncthreads();
@@ -578,22 +359,11 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_solve(PoArgs a) {
 int launch(PoArgs a, hipStream_t st) {
     a.delta = (double)(float)std::sqrt(5.991);
     hipLaunchKernelGGL(k_po_prepare, dim3(a.S), dim3(PO_THREADS), 0, st, a);
-    PCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_po_solve, dim3(a.S), dim3(PO_THREADS), 0, st, a);
-    PCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
-
-int check_camera(const char* who, const float* K) {
-    static const char* const name[4] = {"fx", "fy", "cx", "cy"};
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(K[k]) || (k < 2 && K[k] == 0.0f))
-            return fail(ORB_EINVAL, std::string(who) + ": " + name[k] + " = " + std::to_string(K[k]) +
-                                        (k < 2 ? " must be finite and not 0" : " must be finite"));
-    return ORB_OK;
-}
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -608,16 +378,16 @@ int orb_pose_optimization(int n, const float* p3d, const float* obs, const float
         return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (n > PO_MAX_CAP) return fail(ORB_ENOTSUP, std::string(who) + ": more than 8192 keypoints");
     const float K[4] = {fx, fy, cx, cy};
-    if (int r = check_camera(who, K)) return r;
+    if (int r = orb_check_camera(who, "", K)) return r;
     for (int k = 0; k < 12; ++k)
         if (!std::isfinite(pose_in[k]))
             return fail(ORB_EINVAL, std::string(who) + ": pose_in[" + std::to_string(k) + "] is not finite");
     int ndev = 0;
-    PCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) PCHK(hipGetDevice(&device));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
     OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
     if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    PCHK(hipSetDevice(device));
+    ORB_HIPCHK(hipSetDevice(device));
     const int cap = std::max(n, 1);
     // staging: in  [p3d | obs | inv_sigma2 | has_mp | pose_in]
     //          out [pose f64 | info | pose f32 | n_inliers | outlier]   then the scratch (device only)
@@ -636,7 +406,7 @@ int orb_pose_optimization(int n, const float* p3d, const float* obs, const float
         if (has_mp) std::memcpy(hp + oH, has_mp, (size_t)n);
     }
     std::memcpy(hp + oT, pose_in, 48);
-    PCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
     uint8_t* d = C->buf;
     PoArgs a{};
     a.n_direct = n;
@@ -684,7 +454,7 @@ int orb_pose_optimization_batch_device(const orb_keypoint_t* d_kps, const int32_
     if (S > 65535) return fail(ORB_ENOTSUP, std::string(who) + ": more than 65535 problems per call");
     if (!inv_level_sigma2 || n_levels < 1 || n_levels > ORB_MAX_VIEW_LEVELS)
         return fail(ORB_EINVAL, std::string(who) + ": n_levels must be in [1, 16]");
-    if (int r = check_camera(who, K4)) return r;
+    if (int r = orb_check_camera(who, "", K4)) return r;
     if (S == 0) return ORB_OK;
     if (!d_kps || !d_counts || !d_frame_of || !d_mp_pos || !d_has_mp || !d_pose_in || !d_pose_out || !d_outlier ||
         !d_n_inliers)

@@ -26,12 +26,6 @@ namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define PCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 }  // namespace
 
 struct orb_pipeline {
@@ -132,14 +126,14 @@ int orb_pipeline_extract_undistort_and_match(orb_pipeline_t* p, int B, const uin
     const bool undistort = K4 != nullptr;
     if (undistort && (!dist4 || !d_kps_un)) return fail(ORB_EINVAL, "camera given without coefficients / mvKeysUn");
     if (B > p->maxBatch) return fail(ORB_EINVAL, "B exceeds max_batch");
-    PCHK(hipSetDevice(p->device));
+    ORB_HIPCHK(hipSetDevice(p->device));
     const hipStream_t caller = (hipStream_t)stream;
     const int S = std::min(p->S, B), cap = p->cap;
-    PCHK(hipEventRecord(p->start, caller));
+    ORB_HIPCHK(hipEventRecord(p->start, caller));
     for (int c = 0; c < S; ++c) {
         const int b0 = (int)((long long)B * c / S), b1 = (int)((long long)B * (c + 1) / S), n = b1 - b0;
         const hipStream_t s = p->streams[c];
-        PCHK(hipStreamWaitEvent(s, p->start, 0));
+        ORB_HIPCHK(hipStreamWaitEvent(s, p->start, 0));
         int st = orb_extract_batch_device(p->ext[c], n, d_imgs + (long long)b0 * frame_pitch, w, hgt, stride,
                                           frame_pitch, d_kps + (long long)b0 * cap, d_desc + (long long)b0 * cap * 32,
                                           d_counts + b0, s);
@@ -148,11 +142,11 @@ int orb_pipeline_extract_undistort_and_match(orb_pipeline_t* p, int B, const uin
         if (undistort && (st = orb_undistort_keypoints_batch_device(d_kps + (long long)b0 * cap, d_counts + b0, cap, n,
                                                                     K4, dist4, d_kps_un + (long long)b0 * cap, s)))
             return st;
-        PCHK(hipEventRecord(p->extracted[c], s));
+        ORB_HIPCHK(hipEventRecord(p->extracted[c], s));
     }
     // every pair once the chunks are extracted, on the caller's stream: a matcher work-group
     // takes most of a CU's LDS, so matching beside the extraction slowed both (measured)
-    for (int c = 0; c < S; ++c) PCHK(hipStreamWaitEvent(caller, p->extracted[c], 0));
+    for (int c = 0; c < S; ++c) ORB_HIPCHK(hipStreamWaitEvent(caller, p->extracted[c], 0));
     if (B > 1) {
         int st = orb_search_for_initialization_batch_device(undistort ? d_kps_un : d_kps, d_desc, d_counts, cap, B - 1,
                                                             p->d_iota,

@@ -13,8 +13,12 @@
 //                   (types_seven_dof_expmap.h:138-145, 160-167); oplusImpl 60-69
 //   Jacobian        BaseBinaryEdge::linearizeOplus, numeric (base_binary_edge.hpp:131-205): central
 //                   differences at 1e-9 through oplus, restated literally
-//   quadratic form, Huber, Levenberg, dense solver: as csrc/orb_optimizer.hip, with dimension 7
+//   quadratic form  base_binary_edge.hpp:91-113 with RobustKernelHuber, as §13
+//   Levenberg       optimization_algorithm_levenberg.cpp:61-189, dense solver linear_solver_dense.h:104-112
 //   schedule        Optimizer.cc:1857-1916
+// The quaternion and rotation helpers, the Huber kernel, ldlt<7>, the Levenberg bookkeeping, the
+// workgroup sum and the compaction step are those of csrc/orb_g2o_math.h, shared with
+// csrc/orb_optimizer.hip; this unit holds the Sim3 state, its two edges and the schedule.
 //
 // Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
 // prepare step (the batch form's camera-frame points are the float row sums of §12 first).  Sums
@@ -43,21 +47,18 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_g2o_math.h"
 #include "orb_internal.h"
 
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-
-#define SCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int S3_MAX_CAP = 8192;
 constexpr int S3_THREADS = 256;
 constexpr int S3_WAVES = S3_THREADS / 64;
+static_assert(S3_WAVES == G2O_WAVES, "block_sum and compact_slot are written for this many waves");
 constexpr int S3_NV = 14;    // X1c(3) X2c(3) obs1(2) obs2(2) info1 info2 | chi2 of e12, e21 at their last evaluation
 constexpr int S3_NACC = 36;  // 28 of H (upper triangle), 7 of b, the robust chi2
 constexpr int S3_NST = 15;   // the estimate and its 14 perturbations
@@ -108,7 +109,7 @@ __device__ __forceinline__ void gemm3_add(const float* T, const float* X, float*
 
 __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
     __shared__ int s_wtot[S3_WAVES];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     const bool direct = a.n_direct >= 0;
     const int cap = a.cap;
     int fa = 0, fb = 0, n_row, nb = 0;
@@ -141,18 +142,8 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
                 if (ok && a.mp_bad) ok = !a.mp_bad[(size_t)fa * cap + i] && !a.mp_bad[(size_t)fb * cap + m];
             }
         }
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) s_wtot[wave] = __popcll(bal);
-        __syncthreads();
-        int off = base, tot = 0;
-#pragma unroll
-        for (int w = 0; w < S3_WAVES; ++w) {
-            const int t = s_wtot[w];
-            if (w < wave) off += t;
-            tot += t;
-        }
-        if (ok) {
-            const int o = off + __popcll(bal & ((1ull << lane) - 1ull));
+        const int o = compact_slot(ok, s_wtot, base);
+        if (o >= 0) {
             float X1[3], X2[3], o1[2], o2[2], w1, w2;
             if (direct) {
 #pragma unroll
@@ -177,8 +168,6 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
             q[(size_t)10 * cap + o] = (double)w1, q[(size_t)11 * cap + o] = (double)w2;
             index[o] = i;
         }
-        base += tot;
-        __syncthreads();
     }
     if (tid == 0) a.n[s] = base;
 }
@@ -188,68 +177,6 @@ struct Sim3 {
     double t[3];
     double s;
 };
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// Eigen's Quaternion * Vector3: v + w * 2(q x v) + q x 2(q x v)
-__device__ __forceinline__ void rotate(const double* q, const double* v, double* o) {
-    double uv[3], c[3];
-    cross3(q, v, uv);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
-    cross3(q, uv, c);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = v[k] + q[3] * uv[k] + c[k];
-}
-
-// Eigen's Quaterniond(Matrix3d), m row-major
-__device__ void quat_from_matrix(const double* m, double* q) {
-    double t = m[0] + m[4] + m[8];
-    if (t > 0) {
-        t = sqrt(t + 1.0);
-        q[3] = 0.5 * t;
-        t = 0.5 / t;
-        q[0] = (m[7] - m[5]) * t;
-        q[1] = (m[2] - m[6]) * t;
-        q[2] = (m[3] - m[1]) * t;
-    } else if (m[0] >= m[4] && m[0] >= m[8]) {  // i = 0: !(m11 > m00) && !(m22 > m00)
-        t = sqrt(m[0] - m[4] - m[8] + 1.0);
-        q[0] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[7] - m[5]) * t;
-        q[1] = (m[3] + m[1]) * t;
-        q[2] = (m[6] + m[2]) * t;
-    } else if (m[4] > m[0] && m[4] >= m[8]) {  // i = 1
-        t = sqrt(m[4] - m[8] - m[0] + 1.0);
-        q[1] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[2] - m[6]) * t;
-        q[2] = (m[7] + m[5]) * t;
-        q[0] = (m[1] + m[3]) * t;
-    } else {  // i = 2
-        t = sqrt(m[8] - m[0] - m[4] + 1.0);
-        q[2] = 0.5 * t;
-        t = 0.5 / t;
-        q[3] = (m[3] - m[1]) * t;
-        q[0] = (m[2] + m[6]) * t;
-        q[1] = (m[5] + m[7]) * t;
-    }
-}
-
-// Eigen's toRotationMatrix, row-major
-__device__ void matrix_from_quat(const double* q, double* R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-    R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-}
 
 __device__ __forceinline__ void sim3_map(const Sim3& S, const double* X, double* o) {  // s * (r * xyz) + t
     double r[3];
@@ -274,19 +201,10 @@ __device__ Sim3 oplus(const double* u, const Sim3& T) {
     const double* up = u + 3;
     const double sigma = u[6];
     const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
     Sim3 E;
     E.s = exp(sigma);
-    double O2[9], R[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s = O[3 * i] * O[j];
-            s += O[3 * i + 1] * O[3 + j];
-            s += O[3 * i + 2] * O[6 + j];
-            O2[3 * i + j] = s;
-        }
+    double O[9], O2[9], R[9];
+    hat_sq(om, O, O2);
     const double eps = 0.00001;
     double A, B, C;
     const bool small_theta = theta < eps;
@@ -316,14 +234,7 @@ __device__ Sim3 oplus(const double* u, const Sim3& T) {
             B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
         }
     }
-    if (small_theta) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + O[k]) + O2[k];
-    } else {
-        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + a * O[k]) + b * O2[k];
-    }
+    rodrigues(O, O2, theta, R);
     quat_from_matrix(R, E.q);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {  // t = (A * Omega + B * Omega2 + C * I) * upsilon
@@ -337,11 +248,7 @@ __device__ Sim3 oplus(const double* u, const Sim3& T) {
     }
     // Sim3::operator* (sim3.h:266-272)
     Sim3 r;
-    const double *a = E.q, *b = T.q;
-    r.q[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    r.q[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    r.q[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    r.q[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+    quat_mul(E.q, T.q, r.q);
     double rt[3];
     rotate(E.q, T.t, rt);
 #pragma unroll
@@ -357,133 +264,6 @@ __device__ __forceinline__ void edge_error(const Sim3& M, const double* K, const
     sim3_map(M, X, P);
     e[0] = obs[0] - ((P[0] / P[2]) * K[0] + K[2]);
     e[1] = obs[1] - ((P[1] / P[2]) * K[1] + K[3]);
-}
-
-// RobustKernelHuber::robustify: rho[0], rho[1]
-__device__ __forceinline__ void huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
-    if (e <= dsqr) {
-        *rho0 = e, *rho1 = 1.;
-    } else {
-        const double sqrte = sqrt(e);
-        *rho0 = 2 * sqrte * delta - dsqr;
-        *rho1 = delta / sqrte;
-    }
-}
-
-// Sum of v[0..W) over the workgroup, in a fixed order; every thread gets the same bits.
-template <int W>
-__device__ __forceinline__ void block_sum(double* v, double (*s_red)[S3_NACC]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m);
-    }
-    __syncthreads();  // the readers of the last reduction are done
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) s_red[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        double s = s_red[0][k];
-#pragma unroll
-        for (int w = 1; w < S3_WAVES; ++w) s += s_red[w][k];
-        v[k] = s;
-    }
-}
-
-// Eigen::LDLT of the 7 x 7 A (full symmetric storage, overwritten) and the solve of A x = b, as
-// ldlt6 of orb_optimizer.hip (diagonal pivoting on the largest |a_ii|, the sign tracked over the
-// pivots; false, x untouched, when the matrix is not positive).  Every loop is unrolled and every
-// index is a compile-time constant: the pivot exchanges are selects, so A stays in registers.
-__device__ __forceinline__ void cswap(bool c, double& a, double& b) {
-    const double ta = a, tb = b;
-    a = c ? tb : ta;
-    b = c ? ta : tb;
-}
-
-__device__ bool ldlt7(double* A, const double* b, double* x) {
-    constexpr int N = 7;
-    int tr[N];
-    int sign = 0;  // 0 zero, 1 positive semi-definite, -1 negative semi-definite, 2 indefinite
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        int p = k;
-        double big = fabs(A[(N + 1) * k]);
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            const double v = fabs(A[(N + 1) * i]);
-            const bool g = v > big;
-            big = g ? v : big;
-            p = g ? i : p;
-        }
-        tr[k] = p;
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            const bool sw = p == i;
-#pragma unroll
-            for (int j = 0; j < N; ++j) cswap(sw, A[N * k + j], A[N * i + j]);
-#pragma unroll
-            for (int j = 0; j < N; ++j) cswap(sw, A[N * j + k], A[N * j + i]);
-        }
-        double temp[N];
-#pragma unroll
-        for (int j = 0; j < k; ++j) temp[j] = A[(N + 1) * j] * A[N * k + j];
-#pragma unroll
-        for (int j = 0; j < k; ++j) A[(N + 1) * k] -= A[N * k + j] * temp[j];
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) {
-            double s = A[N * i + k];
-#pragma unroll
-            for (int j = 0; j < k; ++j) s -= A[N * i + j] * temp[j];
-            A[N * i + k] = s;
-        }
-        const double akk = A[(N + 1) * k];
-        if (fabs(akk) > 0) {
-#pragma unroll
-            for (int i = k + 1; i < N; ++i) A[N * i + k] /= akk;
-        }
-        if (sign == 1) {
-            if (akk < 0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) y[k] = b[k];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) cswap(tr[k] == i, y[k], y[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-#pragma unroll
-        for (int j = 0; j < i; ++j) y[i] -= A[N * i + j] * y[j];
-    }
-    const double tol = 1.0 / DBL_MAX;
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = fabs(A[(N + 1) * i]) > tol ? y[i] / A[(N + 1) * i] : 0.0;
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-#pragma unroll
-        for (int j = i + 1; j < N; ++j) y[i] -= A[N * j + i] * y[j];
-    }
-#pragma unroll
-    for (int k = N - 1; k >= 0; --k) {
-#pragma unroll
-        for (int i = k + 1; i < N; ++i) cswap(tr[k] == i, y[k], y[i]);
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) x[k] = y[k];
-    return true;
 }
 
 // One edge's share of a build pass: error at M[0], the numeric Jacobian over M[1..14]
@@ -597,16 +377,9 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_solve(S3Args a) {
             // acc stays as the system: H's upper triangle in acc[0..28), b in acc[28..35)
             const double* b = acc + 28;
             double cur = acc[35];
-            double temp = cur;
             const double ini = cur;
-            if (it == 0) {  // computeLambdaInit
-                double mx = 0.;
-#pragma unroll
-                for (int j = 0, c = 0; j < 7; c += 7 - j, ++j) {  // std::max(fabs(h_jj), maxDiagonal)
-                    const double v = fabs(acc[c]);
-                    mx = v < mx ? mx : v;
-                }
-                lambda = 1e-5 * mx;
+            if (it == 0) {
+                lambda = lm_lambda_init<7>(acc);
                 ni = 2.;
                 bad_steps = 0;
             }
@@ -618,16 +391,8 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_solve(S3Args a) {
                 if (!again) break;
                 const Sim3 backup = T;
                 double A[49];
-                {
-                    int c = 0;
-#pragma unroll
-                    for (int j = 0; j < 7; ++j)
-#pragma unroll
-                        for (int k = j; k < 7; ++k) A[7 * j + k] = A[7 * k + j] = acc[c++];
-                }
-#pragma unroll
-                for (int j = 0; j < 7; ++j) A[8 * j] += lambda;
-                const bool ok2 = ldlt7(A, b, x);
+                lm_damped<7>(acc, lambda, A);
+                const bool ok2 = ldlt<7>(A, b, x);
                 T = oplus(x, T);
                 const Sim3 Ti = sim3_inverse(T);
                 double t1[1] = {0.};
@@ -652,37 +417,16 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_solve(S3Args a) {
                     t1[0] += rho0;
                 }
                 block_sum<1>(t1, s_red);
-                temp = t1[0];
-                if (!ok2) temp = DBL_MAX;
-                rho = cur - temp;
-                double scale = 0.;
-#pragma unroll
-                for (int j = 0; j < 7; ++j) scale += x[j] * (lambda * x[j] + b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(temp)) {
-                    double alpha = 1. - pow(2 * rho - 1, 3.0);
-                    alpha = 2. / 3. < alpha ? 2. / 3. : alpha;           // std::min(alpha, upper)
-                    const double f = 1. / 3. < alpha ? alpha : 1. / 3.;  // std::max(lower, alpha)
-                    lambda *= f;
-                    ni = 2;
-                    cur = temp;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    T = backup;
-                }
+                const double temp = ok2 ? t1[0] : DBL_MAX;
+                rho = (cur - temp) / lm_scale<7>(x, lambda, b);
+                if (lm_accept(rho, temp, lambda, ni)) cur = temp;
+                else T = backup;
                 ++qmax;
                 ++trials;
                 again = rho < 0 && qmax < 10;  // a NaN rho leaves the loop
             }
             last_chi = cur;
-            if (qmax == 10 || rho == 0) stop = true;  // Terminate
-            if (!stop) {
-                if ((ini - cur) * 1e3 < ini) ++bad_steps;
-                else bad_steps = 0;
-                if (bad_steps >= 3) stop = true;
-            }
+            stop = lm_stop(qmax, rho, ini, cur, bad_steps);
         }
         // classification (Optimizer.cc:1862-1879, 1896-1910) on the chi2 of the last evaluation; each
         // thread reads what it wrote
@@ -747,18 +491,9 @@ int launch(S3Args a, float th2, hipStream_t st) {
     a.delta = (double)std::sqrt(th2);  // const float deltaHuber = sqrt(th2)
     a.th2 = (double)th2;
     hipLaunchKernelGGL(k_s3_prepare, dim3(a.S), dim3(S3_THREADS), 0, st, a);
-    SCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_s3_solve, dim3(a.S), dim3(S3_THREADS), 0, st, a);
-    SCHK(hipGetLastError());
-    return ORB_OK;
-}
-
-int check_camera(const char* who, const char* which, const float* K) {
-    static const char* const name[4] = {"fx", "fy", "cx", "cy"};
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(K[k]) || (k < 2 && K[k] == 0.0f))
-            return fail(ORB_EINVAL, std::string(who) + ": " + which + " " + name[k] + " = " + std::to_string(K[k]) +
-                                        (k < 2 ? " must be finite and not 0" : " must be finite"));
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -767,8 +502,6 @@ int check_th2(const char* who, float th2) {
         return fail(ORB_EINVAL, std::string(who) + ": th2 = " + std::to_string(th2) + " must be finite and not negative");
     return ORB_OK;
 }
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -783,18 +516,18 @@ int orb_optimize_sim3(int n, const float* x3dc1, const float* x3dc2, const float
         !sim3_in)
         return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (n > S3_MAX_CAP) return fail(ORB_ENOTSUP, std::string(who) + ": more than 8192 slots");
-    if (int r = check_camera(who, "K1", K1)) return r;
-    if (int r = check_camera(who, "K2", K2)) return r;
+    if (int r = orb_check_camera(who, "K1", K1)) return r;
+    if (int r = orb_check_camera(who, "K2", K2)) return r;
     if (int r = check_th2(who, th2)) return r;
     for (int k = 0; k < 13; ++k)
         if (!std::isfinite(sim3_in[k]))
             return fail(ORB_EINVAL, std::string(who) + ": sim3_in[" + std::to_string(k) + "] is not finite");
     int ndev = 0;
-    SCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) SCHK(hipGetDevice(&device));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
     OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
     if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    SCHK(hipSetDevice(device));
+    ORB_HIPCHK(hipSetDevice(device));
     const int cap = std::max(n, 1);
     const size_t N = (size_t)n;
     // staging: in  [x1 | x2 | obs1 | obs2 | w1 | w2 | usable | sim3_in]
@@ -817,7 +550,7 @@ int orb_optimize_sim3(int n, const float* x3dc1, const float* x3dc2, const float
         if (usable) std::memcpy(hp + oU, usable, N);
     }
     std::memcpy(hp + oT, sim3_in, 52);
-    SCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
     uint8_t* d = C->buf;
     S3Args a{};
     a.n_direct = n;
@@ -866,7 +599,7 @@ int orb_optimize_sim3_batch_device(const orb_keypoint_t* d_kps, const int32_t* d
     if (S > 65535) return fail(ORB_ENOTSUP, std::string(who) + ": more than 65535 problems per call");
     if (!level_sigma2 || !inv_level_sigma2 || nlevels < 1 || nlevels > ORB_MAX_VIEW_LEVELS)
         return fail(ORB_EINVAL, std::string(who) + ": nlevels must be in [1, 16]");
-    if (int r = check_camera(who, "K", K)) return r;
+    if (int r = orb_check_camera(who, "K", K)) return r;
     if (int r = check_th2(who, th2)) return r;
     if (S == 0) return ORB_OK;
     if (!d_kps || !d_counts || !d_pair_a || !d_pair_b || !d_match || !d_mp_pos || !d_pose || !d_sim3_in)

@@ -49,12 +49,7 @@
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-
-#define SCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int CS_MAX_CAP = 8192;
 constexpr int CS_MAX_HYP = 1024;
@@ -357,13 +352,13 @@ __global__ void __launch_bounds__(CS_SEL_THREADS) k_cons_select(ConsArgs a) {
 template <int MODEL, class HT>
 int launch(const ConsArgs& a, const HT* HA, const HT* HB, hipStream_t st) {
     hipLaunchKernelGGL((k_cons_prepare<MODEL>), dim3(a.S), dim3(CS_PREP_THREADS), 0, st, a);
-    SCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     const int tiles = (a.n_hyp + CS_TILE - 1) / CS_TILE;
     const int zg = (std::max(a.W, 1) + CS_WAVES - 1) / CS_WAVES;
     hipLaunchKernelGGL((k_cons_score<MODEL, HT>), dim3(a.S, tiles, zg), dim3(CS_THREADS), 0, st, a, HA, HB);
-    SCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL((k_cons_select<MODEL>), dim3(a.S), dim3(CS_SEL_THREADS), 0, st, a);
-    SCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -387,19 +382,17 @@ int check_sigma2(const char* who, const float* s2, int n, bool sim3) {
     return ORB_OK;
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // One solver from compact host arrays: the common part of the two host entry points.  in[k]: the
 // k-th input array with in_bytes[k] bytes (4 correspondence arrays, then the 2 hypothesis arrays).
 template <int MODEL, class HT>
 int run_host(ConsArgs a, const void* const* in, const size_t* in_bytes, int n, int32_t* counts, uint64_t* masks,
              int32_t* best_at, int32_t* first, int best_in, int device) {
     int ndev = 0;
-    SCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) SCHK(hipGetDevice(&device));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
     OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
     if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    SCHK(hipSetDevice(device));
+    ORB_HIPCHK(hipSetDevice(device));
     const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
     constexpr int NV = MODEL == PNP ? NV_PNP : NV_SIM3;
     // staging: in  [c0 | c1 | c2 | c3 | HA | HB | best_in]
@@ -418,7 +411,7 @@ int run_host(ConsArgs a, const void* const* in, const size_t* in_bytes, int n, i
     for (int k = 0; k < 6; ++k)
         if (in_bytes[k]) std::memcpy(hp + o_in[k], in[k], in_bytes[k]);
     std::memcpy(hp + o_in[6], &best_in, 4);
-    SCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
     uint8_t* d = C->buf;
     a.c0 = (const float*)(d + o_in[0]);
     a.c1 = (const float*)(d + o_in[1]);

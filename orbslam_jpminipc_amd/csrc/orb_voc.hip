@@ -238,12 +238,6 @@ __global__ void __launch_bounds__(256) k_voc_bow(const uint32_t* __restrict__ wo
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-#define VCHK(expr)                                                                                \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 int pow2_at_least(int n) {
     int p = 256;
     while (p < n) p <<= 1;
@@ -314,16 +308,16 @@ struct orb_vocabulary {
         nNodes = N;
         nWords = words;
         maxDepth = std::max(height, 1);
-        VCHK(hipSetDevice(device));
-        VCHK(hipMalloc(&d_slotDesc, sdesc.size() * sizeof(uint4)));
-        VCHK(hipMalloc(&d_slotInfo, sinfo.size() * sizeof(uint4)));
-        VCHK(hipMalloc(&d_word, (size_t)N * 4));
-        VCHK(hipMalloc(&d_weight, (size_t)N * 8));
-        VCHK(hipMemcpy(d_slotDesc, sdesc.data(), sdesc.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        VCHK(hipMemcpy(d_slotInfo, sinfo.data(), sinfo.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        VCHK(hipMemcpy(d_word, wid.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-        VCHK(hipMemcpy(d_weight, wt.data(), (size_t)N * 8, hipMemcpyHostToDevice));
-        VCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        ORB_HIPCHK(hipSetDevice(device));
+        ORB_HIPCHK(hipMalloc(&d_slotDesc, sdesc.size() * sizeof(uint4)));
+        ORB_HIPCHK(hipMalloc(&d_slotInfo, sinfo.size() * sizeof(uint4)));
+        ORB_HIPCHK(hipMalloc(&d_word, (size_t)N * 4));
+        ORB_HIPCHK(hipMalloc(&d_weight, (size_t)N * 8));
+        ORB_HIPCHK(hipMemcpy(d_slotDesc, sdesc.data(), sdesc.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        ORB_HIPCHK(hipMemcpy(d_slotInfo, sinfo.data(), sinfo.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        ORB_HIPCHK(hipMemcpy(d_word, wid.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+        ORB_HIPCHK(hipMemcpy(d_weight, wt.data(), (size_t)N * 8, hipMemcpyHostToDevice));
+        ORB_HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         return ORB_OK;
     }
 };
@@ -341,7 +335,7 @@ int check_header(int k, int L, int scoring, int weighting) {
 
 int check_device(int device) {
     int ndev = 0;
-    VCHK(hipGetDeviceCount(&ndev));
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(ORB_EINVAL, "device ordinal out of range");
     return ORB_OK;
 }
@@ -393,7 +387,7 @@ int launch_bow(const orb_vocabulary_t* v, int B, const int32_t* d_counts, int ca
     hipLaunchKernelGGL(k_voc_bow, dim3(B), dim3(256), lds, st, d_word, d_weight, d_node, d_counts, cap, P,
                        v->scoring, v->weighting, d_bow_words, d_bow_values, d_bow_n, d_fv_nodes, d_fv_offsets,
                        d_fv_features, d_fv_n);
-    VCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -519,9 +513,9 @@ int orb_vocabulary_transform_features_device(const orb_vocabulary_t* v, int n, c
     int st = check_transform_args(v, d_desc);
     if (st) return st;
     if (n == 0) return ORB_OK;
-    VCHK(hipSetDevice(v->device));
+    ORB_HIPCHK(hipSetDevice(v->device));
     launch_descend(v, d_desc, nullptr, n, n, levelsup, d_word, d_weight, d_node, (hipStream_t)stream);
-    VCHK(hipGetLastError());
+    ORB_HIPCHK(hipGetLastError());
     return ORB_OK;
 }
 
@@ -537,7 +531,7 @@ int orb_vocabulary_transform_batch_device(const orb_vocabulary_t* v, int B, cons
     if (cap > VOC_MAX_FEATURES) return fail(ORB_ENOTSUP, "more than 8192 features per frame");
     int st = check_transform_args(v, d_desc);
     if (st) return st;
-    VCHK(hipSetDevice(v->device));
+    ORB_HIPCHK(hipSetDevice(v->device));
     const hipStream_t s = (hipStream_t)stream;
     launch_descend(v, d_desc, d_counts, cap, (long long)B * cap, levelsup, d_feat_word, d_feat_weight, d_feat_node,
                    s);
@@ -557,7 +551,7 @@ int orb_vocabulary_transform(orb_vocabulary_t* v, const uint8_t* desc, int n, in
     fv_offsets[0] = 0;
     if (v->nWords == 0 || n == 0) return ORB_OK;  // empty(): v.clear(), fv.clear(), return
     std::lock_guard<std::mutex> lock(v->mu);
-    VCHK(hipSetDevice(v->device));
+    ORB_HIPCHK(hipSetDevice(v->device));
     // scratch: desc | word | weight | node | bow words | values | fv nodes | offsets | features | counts | n
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t oDesc = 0, oWord = al(oDesc + (size_t)n * 32), oWt = al(oWord + (size_t)n * 4),
@@ -568,31 +562,31 @@ int orb_vocabulary_transform(orb_vocabulary_t* v, const uint8_t* desc, int n, in
         (void)hipFree(v->d_scratch);
         v->d_scratch = nullptr;
         v->scratchCap = 0;
-        VCHK(hipMalloc(&v->d_scratch, total));
+        ORB_HIPCHK(hipMalloc(&v->d_scratch, total));
         v->scratchCap = total;
     }
     uint8_t* S = v->d_scratch;
     const hipStream_t st = v->stream;
     const int32_t cnt = n;
-    VCHK(hipMemcpyAsync(S + oDesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, st));
-    VCHK(hipMemcpyAsync(S + oCnt, &cnt, 4, hipMemcpyHostToDevice, st));
+    ORB_HIPCHK(hipMemcpyAsync(S + oDesc, desc, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    ORB_HIPCHK(hipMemcpyAsync(S + oCnt, &cnt, 4, hipMemcpyHostToDevice, st));
     int r = orb_vocabulary_transform_batch_device(
         v, 1, S + oDesc, (const int32_t*)(S + oCnt), n, levelsup, (uint32_t*)(S + oWord), (double*)(S + oWt),
         (uint32_t*)(S + oNode), (uint32_t*)(S + oBw), (double*)(S + oBv), (int32_t*)(S + oN), (uint32_t*)(S + oFn),
         (int32_t*)(S + oFo), (int32_t*)(S + oFf), (int32_t*)(S + oN + 4), st);
     if (r) return r;
     int32_t nn[2] = {0, 0};
-    VCHK(hipMemcpyAsync(nn, S + oN, 8, hipMemcpyDeviceToHost, st));
-    VCHK(hipStreamSynchronize(st));
+    ORB_HIPCHK(hipMemcpyAsync(nn, S + oN, 8, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipStreamSynchronize(st));
     const int bn = nn[0], fn = nn[1];
-    VCHK(hipMemcpyAsync(bow_words, S + oBw, (size_t)bn * 4, hipMemcpyDeviceToHost, st));
-    VCHK(hipMemcpyAsync(bow_values, S + oBv, (size_t)bn * 8, hipMemcpyDeviceToHost, st));
-    VCHK(hipMemcpyAsync(fv_nodes, S + oFn, (size_t)fn * 4, hipMemcpyDeviceToHost, st));
-    VCHK(hipMemcpyAsync(fv_offsets, S + oFo, (size_t)(fn + 1) * 4, hipMemcpyDeviceToHost, st));
-    VCHK(hipStreamSynchronize(st));
+    ORB_HIPCHK(hipMemcpyAsync(bow_words, S + oBw, (size_t)bn * 4, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipMemcpyAsync(bow_values, S + oBv, (size_t)bn * 8, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipMemcpyAsync(fv_nodes, S + oFn, (size_t)fn * 4, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipMemcpyAsync(fv_offsets, S + oFo, (size_t)(fn + 1) * 4, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipStreamSynchronize(st));
     const int nfeat = fv_offsets[fn];
-    VCHK(hipMemcpyAsync(fv_features, S + oFf, (size_t)nfeat * 4, hipMemcpyDeviceToHost, st));
-    VCHK(hipStreamSynchronize(st));
+    ORB_HIPCHK(hipMemcpyAsync(fv_features, S + oFf, (size_t)nfeat * 4, hipMemcpyDeviceToHost, st));
+    ORB_HIPCHK(hipStreamSynchronize(st));
     *bow_n = bn;
     *fv_n = fn;
     return ORB_OK;
