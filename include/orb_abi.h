@@ -618,9 +618,10 @@ int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_
 /* PnPsolver::CheckInliers (reference src/PnPsolver.cc:280-311) and Sim3Solver::CheckInliers
  * (src/Sim3Solver.cc:335-359) for all RANSAC hypotheses of a solver at once, with the
  * per-correspondence set-up of the two constructors and the keep-the-best rule of the two
- * iterate() loops.  The hypotheses are the caller's: EPnP compute_pose (cvSVD), Refine's pose and
- * Sim3Solver::computeT (cv::eigen) stay on the host, as do the random minimal sets and the
- * iteration counters.  Counts and masks are the reference's bit for bit: a NaN
+ * iterate() loops.  In these four entry points the hypotheses are the caller's.  For PnP, EPnP
+ * compute_pose (cvSVD) and Refine's pose stay on the host, as do the random minimal sets and the
+ * iteration counters; for Sim3, computeT and the minimal sets run on the device in the
+ * orb_sim3_ransac entry points below.  Counts and masks are the reference's bit for bit: a NaN
  * error is an outlier, a point behind the camera is not excluded.
  * Correspondence i of hypothesis h is bit i % 64 of word i / 64 of the h-th mask row (W words per
  * row); bits past n are zero.
@@ -694,6 +695,55 @@ int orb_sim3_check_inliers_batch_device(const orb_keypoint_t* d_kps, const int32
                                         const int32_t* d_best_in, int32_t* d_n, int32_t* d_index,
                                         int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
                                         int32_t* d_first_accept, void* stream);
+
+/* ---- Sim3Solver: the hypotheses and the whole RANSAC (GPU: csrc/orb_solvers.hip) */
+/* The minimal sets of Sim3Solver::iterate (Sim3Solver.cc:163-177) and Horn's closed form
+ * (Sim3Solver::computeT, 226-332, with centroid, 215-224), one lane per hypothesis, restated in the
+ * reference's float pattern with OpenCV 2.4's primitives as DESIGN.md §15 reads them (cv::eigen is
+ * JacobiImpl_<float>).  Nothing is repaired: a set whose best quaternion is exactly (+-1, 0, 0, 0)
+ * gives a NaN hypothesis, which scores 0 inliers; a set may hold one correspondence twice.
+ * Draws: either `sets`, n_hyp x 3 indices into the n correspondences, or `rand31`, n_hyp x 3 values
+ * as rand() returned them, 0 <= r < 2^31; draw i of a set is RandomInt(0, size - 1) = (r * size) >>
+ * 31 on the list of size n - i, and the drawn value, not the position, is overwritten with the
+ * list's last entry, as the reference does.  The package owns no random generator.
+ * A Sim3 is 13 floats: mR12i row-major, mt12i, ms12i (the layout of orb_optimize_sim3's sim3_in).
+ *
+ * computeT alone, host buffers, synchronous.  x3dc1 / x3dc2 n x 3.  Outputs, each may be NULL: T12 /
+ * T21 n_hyp x 12 (rows 0-2 of mT12i / mT21i), sim3 n_hyp x 13, quat n_hyp x 4 (row 0 of cv::eigen's
+ * eigenvectors), sets_out n_hyp x 3.  ORB_EINVAL: both or neither of sets / rand31, a set index
+ * outside [0, n), a rand31 value outside [0, 2^31), n < 1, or n < 3 with rand31. */
+int orb_sim3_compute_hypotheses(int n, const float* x3dc1, const float* x3dc2, int n_hyp, const int32_t* sets,
+                                const int32_t* rand31, float* T12, float* T21, float* sim3, float* quat,
+                                int32_t* sets_out, int device);
+/* One Sim3Solver::iterate(n_hyp, ...) without its early return, host buffers, synchronous: the
+ * arguments and outputs of orb_sim3_check_inliers with the draws in place of T12 / T21, which are
+ * generated, scored and selected in one stream-ordered chain.  Further outputs, each may be NULL: T12,
+ * T21, sim3, sets_out as above and accepted (13 floats): the Sim3 of hypothesis first_accept, or of
+ * best_at[n_hyp - 1] when nothing was accepted (mBestRotation / mBestTranslation / mBestScale either
+ * way); NaN when the best is still the earlier calls' (best_at[n_hyp - 1] < 0).  n < min_inliers is
+ * bNoMore (Sim3Solver.cc:146-150): nothing is generated, the hypothesis and set rows are zeros, the
+ * counts 0, first_accept -1.  ORB_EINVAL as above and for min_inliers < 3. */
+int orb_sim3_ransac(int n, const float* x3dc1, const float* x3dc2, const float* sigma2_1, const float* sigma2_2,
+                    const float* K1, const float* K2, int n_hyp, const int32_t* sets, const int32_t* rand31,
+                    int min_inliers, int best_in, int32_t* counts, uint64_t* masks, int32_t* best_at,
+                    int32_t* first_accept, float* T12, float* T21, float* sim3, int32_t* sets_out, float* accepted,
+                    int device);
+/* S Sim3Solvers on device-resident data: the arguments of orb_sim3_check_inliers_batch_device with
+ * d_rand31 (S x n_hyp x 3 int32) in place of d_T12 / d_T21; the draws are mapped to sets on the
+ * device, where each solver's n is.  A negative d_rand31 value is clamped to 0 (the host forms refuse
+ * it).  Further outputs, each may be NULL: d_T12 / d_T21 S x n_hyp x 12, d_sim3 S x n_hyp x 13,
+ * d_sets_out S x n_hyp x 3, d_accepted S x 13 (as `accepted` above; the layout
+ * orb_optimize_sim3_batch_device takes as d_sim3_in) and d_accepted_mask S x W, the accepted
+ * hypothesis's mask row: what iterate returns in vbInliers before the scatter through mvnIndices1
+ * (zeros where d_accepted is NaN).  Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                 const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                 const float* d_mp_pos, const uint8_t* d_mp_bad, const float* d_pose,
+                                 const float* level_sigma2, int nlevels, const float* K, int n_hyp,
+                                 const int32_t* d_rand31, int min_inliers, const int32_t* d_best_in, int32_t* d_n,
+                                 int32_t* d_index, int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                 int32_t* d_first_accept, float* d_T12, float* d_T21, float* d_sim3,
+                                 int32_t* d_sets_out, float* d_accepted, uint64_t* d_accepted_mask, void* stream);
 
 /* ---- Optimizer: motion-only pose optimisation (GPU: csrc/orb_optimizer.hip) ----------- */
 /* Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285) with the parts of g2o

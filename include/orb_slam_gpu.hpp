@@ -554,9 +554,10 @@ private:
     int device_;
 };
 
-// The consensus half of ORB_SLAM::Sim3Solver (Sim3Solver.cc:37-207, 335-418): the caller draws the
-// minimal sets and runs computeT for a block of iterations (5 at a time, LoopClosing.cc:314) and
-// hands rows 0-2 of mT12i / mT21i over.
+// ORB_SLAM::Sim3Solver (Sim3Solver.cc:37-213, 335-418).  iterate(nIterations, bNoMore, vbInliers,
+// nInliers, rand31) / find run whole iterations on the device, minimal sets and computeT included,
+// from the values of rand() that the caller hands over (three per iteration; the class owns no
+// random generator).  The older iterate(vT12, vT21, ...) scores hypotheses the caller made.
 class Sim3Solver {
 public:
     // Sim3Solver(pKF1, pKF2, vpMatched12) (Sim3Solver.cc:37-112) over PODs, one entry per kept
@@ -618,10 +619,76 @@ public:
         return first;
     }
 
+    // iterate(nIterations, bNoMore, vbInliers, nInliers) (Sim3Solver.cc:140-207).  rand31: the values
+    // rand() would return, 0 <= r < 2^31, three per iteration; min(nIterations, mRansacMaxIts -
+    // mnIterations) iterations are run and rand31 must hold that many triples.  Returns true with
+    // the accepted transform in mBest* (GetEstimated*) where the reference returns mBestT12, false
+    // where it returns an empty Mat.  randUsed (may be NULL): the number of values consumed, 3 per
+    // iteration taken as run.  mRansacMinInliers >= 3.
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers,
+                 const std::vector<int32_t>& rand31, size_t* randUsed = nullptr) {
+        bNoMore = false;
+        vbInliers.assign((size_t)mN1, false);
+        nInliers = 0;
+        if (randUsed) *randUsed = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        const int k = std::min(nIterations, mRansacMaxIts - mnIterations);
+        if (k > 0) {
+            if (rand31.size() < (size_t)k * 3) throw std::runtime_error("orb: rand31 must hold 3 values per iteration");
+            const int W = (N + 63) / 64;
+            std::vector<int32_t> counts((size_t)k), best_at((size_t)k);
+            std::vector<uint64_t> masks((size_t)k * W + 1);
+            std::vector<float> sim3((size_t)k * 13);
+            int32_t first = -1;
+            orb_check(orb_sim3_ransac(N, mvX3Dc1.data(), mvX3Dc2.data(), mvSigma2_1.data(), mvSigma2_2.data(), mK1, mK2, k,
+                                      nullptr, rand31.data(), mRansacMinInliers, mnBestInliers, counts.data(),
+                                      masks.data(), best_at.data(), &first, nullptr, nullptr, sim3.data(), nullptr,
+                                      nullptr, device_));
+            const int last = first >= 0 ? first : k - 1;
+            mnIterations += last + 1;
+            if (randUsed) *randUsed = (size_t)(last + 1) * 3;
+            const int holder = best_at[(size_t)last];
+            if (holder >= 0) {
+                mnBest = holder;
+                mnBestInliers = counts[(size_t)holder];
+                mvbBestInliers.assign((size_t)N, false);
+                for (int i = 0; i < N; ++i)
+                    mvbBestInliers[(size_t)i] = (masks[(size_t)holder * W + (i >> 6)] >> (i & 63)) & 1;
+                std::copy(sim3.begin() + (size_t)holder * 13, sim3.begin() + (size_t)holder * 13 + 9, mBestRotation);
+                std::copy(sim3.begin() + (size_t)holder * 13 + 9, sim3.begin() + (size_t)holder * 13 + 12, mBestTranslation);
+                mBestScale = sim3[(size_t)holder * 13 + 12];
+            }
+            if (first >= 0) {
+                nInliers = counts[(size_t)first];
+                for (int i = 0; i < N; ++i)
+                    if (mvbBestInliers[(size_t)i]) vbInliers[mvnIndices1[(size_t)i]] = true;
+                return true;
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return false;
+    }
+
+    // find (Sim3Solver.cc:209-213): iterate(mRansacMaxIts, ...)
+    bool find(std::vector<bool>& vbInliers12, int& nInliers, const std::vector<int32_t>& rand31,
+              size_t* randUsed = nullptr) {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers, rand31, randUsed);
+    }
+
+    // mBestRotation (row-major 3 x 3), mBestTranslation, mBestScale of the iterations so far
+    const float* GetEstimatedRotation() const { return mBestRotation; }
+    const float* GetEstimatedTranslation() const { return mBestTranslation; }
+    float GetEstimatedScale() const { return mBestScale; }
+
     std::vector<float> mvX3Dc1, mvX3Dc2, mvSigma2_1, mvSigma2_2;
     std::vector<size_t> mvnIndices1;
     std::vector<bool> mvbBestInliers;
     float mK1[4], mK2[4];
+    float mBestRotation[9] = {0}, mBestTranslation[3] = {0}, mBestScale = 0;
     int mnIterations, mnBestInliers, mnBest;
     int mRansacMinInliers, mRansacMaxIts;
     int N, mN1;

@@ -4,8 +4,9 @@
 // (src/Sim3Solver.cc:335-359, with Project 377-398) for every hypothesis of a solver at once, the
 // per-correspondence set-up of the two constructors (PnPsolver.cc:40-82, 126-128;
 // Sim3Solver.cc:37-112) and the keep-the-best rules of the two iterate() loops (PnPsolver.cc:181-196,
-// Sim3Solver.cc:183-200).  The hypotheses themselves (EPnP compute_pose, Horn's computeT) and the
-// random minimal sets are the caller's.
+// Sim3Solver.cc:183-200).  PnP's hypotheses (EPnP compute_pose) and minimal sets are the caller's;
+// Sim3's are made here from the caller's rand() values: the minimal sets of Sim3Solver::iterate
+// (Sim3Solver.cc:163-177) and Horn's closed form, Sim3Solver::computeT (215-332), DESIGN.md §15.
 //
 // Arithmetic: the TU is built -ffp-contract=off and the fused multiply-adds that g++ -O3
 // -march=native makes of the reference's own translation units are written out
@@ -35,6 +36,11 @@
 //   k_cons_select<M>   one workgroup per solver: prefix maxima over the <= 1024 counts give the
 //                      running best, its holder after every iteration and the first qualifying /
 //                      accepted iteration.
+//   k_sim3_hypotheses  one lane per (solver, hypothesis), between prepare and score: the three
+//                      draws mapped to indices, the three correspondences gathered from the SoA
+//                      scratch, computeT in registers (cv::eigen as JacobiImpl_<float> with every
+//                      array index a compile-time constant: no scratch memory), T12 / T21 written.
+//   k_sim3_accepted    one workgroup per solver: the Sim3 and mask row of the accepted hypothesis.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -349,10 +355,379 @@ __global__ void __launch_bounds__(CS_SEL_THREADS) k_cons_select(ConsArgs a) {
     if (h == 0 && a.first) a.first[s] = s_first == INT_MAX ? -1 : s_first;
 }
 
+// ---- Sim3Solver: the hypotheses (Sim3Solver.cc:163-177, 215-332) -----------------------
+struct HypArgs {
+    const int32_t* rand31;  // S x n_hyp x 3 values of rand(), or
+    const int32_t* sets;    // S x n_hyp x 3 indices: exactly one of the two
+    float* T12;             // outputs, each may be NULL
+    float* T21;
+    float* sim3;
+    float* quat;
+    int32_t* sets_out;
+};
+
+// The symmetric 4x4 of cv::eigen in registers: U the upper triangle (0,1) (0,2) (0,3) (1,2) (1,3)
+// (2,3), W the diagonal, V the eigenvectors as rows, indR / indC JacobiImpl_'s pivot indices.  Every
+// array index is a constant after unrolling; a runtime index is a chain of selects.
+struct Jac4 {
+    float U[6], W[4], V[16];
+    int indR[3], indC[4];
+};
+__host__ __device__ constexpr int jac_up(int i, int j) { return i == 0 ? j - 1 : (i == 1 ? j + 1 : 5); }
+// A[r][c], r < c, at a runtime index: the six candidates masked by the index and OR-ed.  (A chain of
+// selects over J.U[] is folded by the compiler into one load at a selected address, which keeps U in
+// scratch memory.)
+__device__ __forceinline__ unsigned jac_pick(int p, int P, float v) { return p == P ? __float_as_uint(v) : 0u; }
+__device__ __forceinline__ float jac_get(const Jac4& J, int r, int c) {
+    const int p = r == 0 ? c - 1 : (r == 1 ? c + 1 : 5);
+    return __uint_as_float(jac_pick(p, 0, J.U[0]) | jac_pick(p, 1, J.U[1]) | jac_pick(p, 2, J.U[2]) |
+                           jac_pick(p, 3, J.U[3]) | jac_pick(p, 4, J.U[4]) | jac_pick(p, 5, J.U[5]));
+}
+// lapack.cpp's own hypot
+__device__ __forceinline__ float jac_hypot(float a, float b) {
+    a = fabsf(a);
+    b = fabsf(b);
+    if (a > b) {
+        b /= a;
+        return a * sqrtf(1 + b * b);
+    }
+    if (b > 0) {
+        a /= b;
+        return b * sqrtf(1 + a * a);
+    }
+    return 0;
+}
+// indR[IDX] = the first largest |A[IDX][i]|, i > IDX; indC[IDX] = the first largest |A[i][IDX]|, i < IDX.
+// The loops of JacobiImpl_ are written out through templates so that every index is a constant
+// before the first scalar-replacement pass: a loop-indexed J.U[] would keep J in scratch memory.
+template <int IDX, int I>
+__device__ __forceinline__ void jac_scan_row(const Jac4& J, float& mv, int& m) {
+    if constexpr (I >= IDX + 2 && I < 4) {
+        const float val = fabsf(J.U[jac_up(IDX, I)]);
+        if (mv < val) mv = val, m = I;
+    }
+}
+template <int IDX, int I>
+__device__ __forceinline__ void jac_scan_col(const Jac4& J, float& mv, int& m) {
+    if constexpr (I >= 1 && I < IDX) {
+        const float val = fabsf(J.U[jac_up(I, IDX)]);
+        if (mv < val) mv = val, m = I;
+    }
+}
+template <int IDX>
+__device__ __forceinline__ void jac_scan(Jac4& J) {
+    if constexpr (IDX < 3) {
+        int m = IDX + 1;
+        float mv = fabsf(J.U[jac_up(IDX, IDX + 1)]);
+        jac_scan_row<IDX, 2>(J, mv, m);
+        jac_scan_row<IDX, 3>(J, mv, m);
+        J.indR[IDX] = m;
+    }
+    if constexpr (IDX > 0) {
+        int m = 0;
+        float mv = fabsf(J.U[jac_up(0, IDX)]);
+        jac_scan_col<IDX, 1>(J, mv, m);
+        jac_scan_col<IDX, 2>(J, mv, m);
+        J.indC[IDX] = m;
+    }
+}
+__device__ __forceinline__ void jac_rot(float& v0, float& v1, float c, float s) {
+    const float a0 = v0, b0 = v1;
+    v0 = a0 * c - b0 * s;
+    v1 = a0 * s + b0 * c;
+}
+// rows and columns K and L at index I (i < k, k < i < l, l < i in JacobiImpl_'s three loops)
+template <int K, int L, int I>
+__device__ __forceinline__ void jac_rot_at(Jac4& J, float c, float s) {
+    if constexpr (I < K) jac_rot(J.U[jac_up(I, K)], J.U[jac_up(I, L)], c, s);
+    else if constexpr (I > K && I < L) jac_rot(J.U[jac_up(K, I)], J.U[jac_up(I, L)], c, s);
+    else if constexpr (I > L) jac_rot(J.U[jac_up(K, I)], J.U[jac_up(L, I)], c, s);
+}
+// one rotation on the pivot p = A[K][L]
+template <int K, int L>
+__device__ __forceinline__ void jac_rotate(Jac4& J, float p) {
+    const float y = (float)((double)(J.W[L] - J.W[K]) * 0.5);
+    float t = fabsf(y) + jac_hypot(p, y);
+    float s = jac_hypot(p, t);
+    const float c = t / s;
+    s = p / s;
+    t = (p / t) * p;
+    if (y < 0) s = -s, t = -t;
+    J.U[jac_up(K, L)] = 0;
+    J.W[K] -= t;
+    J.W[L] += t;
+    jac_rot_at<K, L, 0>(J, c, s);
+    jac_rot_at<K, L, 1>(J, c, s);
+    jac_rot_at<K, L, 2>(J, c, s);
+    jac_rot_at<K, L, 3>(J, c, s);
+    jac_rot(J.V[4 * K], J.V[4 * L], c, s);
+    jac_rot(J.V[4 * K + 1], J.V[4 * L + 1], c, s);
+    jac_rot(J.V[4 * K + 2], J.V[4 * L + 2], c, s);
+    jac_rot(J.V[4 * K + 3], J.V[4 * L + 3], c, s);
+    jac_scan<K>(J);
+    jac_scan<L>(J);
+}
+__device__ __forceinline__ float sel4(int m, float v0, float v1, float v2, float v3) {
+    float v = v0;
+    v = m == 1 ? v1 : v;
+    v = m == 2 ? v2 : v;
+    v = m == 3 ? v3 : v;
+    return v;
+}
+// the second half of the pivot search: column I's largest entry against the best so far
+template <int I>
+__device__ __forceinline__ void jac_pivot_col(const Jac4& J, float& mv, int& k, int& l) {
+    const float val = fabsf(jac_get(J, J.indC[I], I));
+    if (mv < val) mv = val, k = J.indC[I], l = I;
+}
+
+// cv::eigen(N, eval, evec) of the symmetric 4x4 CV_32F whose upper triangle and diagonal are in J:
+// q = row 0 of evec.  The descending sort swaps rows 0 and m, the first largest eigenvalue; the later
+// swaps leave row 0 alone, so row 0 is row m before the sort.
+__device__ __forceinline__ void jac_eigen_row0(Jac4& J, float* q) {
+    J.V[0] = 1, J.V[1] = 0, J.V[2] = 0, J.V[3] = 0;
+    J.V[4] = 0, J.V[5] = 1, J.V[6] = 0, J.V[7] = 0;
+    J.V[8] = 0, J.V[9] = 0, J.V[10] = 1, J.V[11] = 0;
+    J.V[12] = 0, J.V[13] = 0, J.V[14] = 0, J.V[15] = 1;
+    J.indC[0] = 0;
+    jac_scan<0>(J);
+    jac_scan<1>(J);
+    jac_scan<2>(J);
+    jac_scan<3>(J);
+    for (int iters = 0; iters < 4 * 4 * 30; ++iters) {
+        int k = 0;
+        float mv = fabsf(jac_get(J, 0, J.indR[0]));
+        float val = fabsf(jac_get(J, 1, J.indR[1]));
+        if (mv < val) mv = val, k = 1;
+        val = fabsf(J.U[5]);  // indR[2] is 3
+        if (mv < val) mv = val, k = 2;
+        int l = k == 0 ? J.indR[0] : (k == 1 ? J.indR[1] : 3);
+        jac_pivot_col<1>(J, mv, k, l);
+        jac_pivot_col<2>(J, mv, k, l);
+        jac_pivot_col<3>(J, mv, k, l);
+        const float p = jac_get(J, k, l);
+        if (fabsf(p) <= 1.1920928955078125e-7f) break;  // FLT_EPSILON
+        switch (4 * k + l) {
+            case 1: jac_rotate<0, 1>(J, p); break;
+            case 2: jac_rotate<0, 2>(J, p); break;
+            case 3: jac_rotate<0, 3>(J, p); break;
+            case 6: jac_rotate<1, 2>(J, p); break;
+            case 7: jac_rotate<1, 3>(J, p); break;
+            default: jac_rotate<2, 3>(J, p); break;
+        }
+    }
+    int m = 0;
+    float wm = J.W[0];
+    if (wm < J.W[1]) wm = J.W[1], m = 1;
+    if (wm < J.W[2]) wm = J.W[2], m = 2;
+    if (wm < J.W[3]) wm = J.W[3], m = 3;
+    q[0] = sel4(m, J.V[0], J.V[4], J.V[8], J.V[12]);
+    q[1] = sel4(m, J.V[1], J.V[5], J.V[9], J.V[13]);
+    q[2] = sel4(m, J.V[2], J.V[6], J.V[10], J.V[14]);
+    q[3] = sel4(m, J.V[3], J.V[7], J.V[11], J.V[15]);
+}
+
+// m = alpha * m assigned (convertTo -> cvtScale_<float, float, float>): scale and shift as floats
+__device__ __forceinline__ float cvt_scale(float v, double alpha) {
+    const float scale = (float)alpha, shift = (float)0.0;
+    return v * scale + shift;
+}
+__device__ __forceinline__ float gemm_out(float t, double alpha, float c, double beta) {
+    return (float)((double)t * alpha + (double)c * beta);
+}
+// Sim3Solver::centroid of a 3x3 (row-major, a correspondence per column)
+__device__ __forceinline__ void centroid3(const float* P, float* Pr, float* C) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        float a0 = P[3 * r], a1 = P[3 * r + 1];  // cv::reduce: (s0 + s2) + s1
+        a0 = a0 + P[3 * r + 2];
+        a0 = a0 + a1;
+        C[r] = cvt_scale(a0, 1. / (double)3);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Pr[k] = P[k] - C[k / 3];
+}
+// DUtils::Random::RandomInt(0, size - 1) on rand()'s value r: int(((double)r / 2^31) * size), which
+// for 0 <= r < 2^31 and size <= 8192 is (r * size) >> 31
+__device__ __forceinline__ int random_int(int r, int size) { return (int)(((long long)r * (long long)size) >> 31); }
+
+// One lane per (solver, hypothesis), after k_cons_prepare<SIM3>.
+__global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
+    const int s = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= a.n_hyp) return;
+    const size_t g = (size_t)s * a.n_hyp + h;
+    const int n = a.n[s], cap = a.cap;
+    float T12[12], T21[12], R[9], t12[3], q[4], ms12i = 0;
+    int idx[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 12; ++k) T12[k] = T21[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = 0;
+    t12[0] = t12[1] = t12[2] = q[0] = q[1] = q[2] = q[3] = 0;
+    // N < mRansacMinInliers: bNoMore, nothing is generated (Sim3Solver.cc:146-150); n >= 3 otherwise
+    if (n >= a.min_inliers && n >= (y.sets ? 1 : 3)) {
+        if (y.sets) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) idx[i] = min(max(y.sets[3 * g + i], 0), n - 1);
+        } else {
+            // vAvailableIndices starts as the identity; [idx] = back(), pop_back() with idx the value
+            // drawn (Sim3Solver.cc:175-176).  Two entries at most differ from the identity.
+            const int r0 = max(y.rand31[3 * g], 0), r1 = max(y.rand31[3 * g + 1], 0), r2 = max(y.rand31[3 * g + 2], 0);
+            idx[0] = random_int(r0, n);                 // [idx0] = n - 1
+            const int rb = random_int(r1, n - 1);
+            idx[1] = rb == idx[0] ? n - 1 : rb;
+            const int back2 = (n - 2 == idx[0]) ? n - 1 : n - 2;  // [idx1] = back(), the entry at n - 2
+            const int rc = random_int(r2, n - 2);
+            idx[2] = rc == idx[1] ? back2 : (rc == idx[0] ? n - 1 : rc);
+        }
+        const float* x = a.soa + (size_t)s * NV_SIM3 * cap;
+        float P1[9], P2[9], Pr1[9], Pr2[9], O1[3], O2[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                P1[3 * r + i] = x[(size_t)r * cap + idx[i]];
+                P2[3 * r + i] = x[(size_t)(3 + r) * cap + idx[i]];
+            }
+        centroid3(P1, Pr1, O1);
+        centroid3(P2, Pr2, O2);
+        // M = Pr2*Pr1.t() (GEMM_2_T: GEMMSingleMul<float, double>)
+        float M[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double s0 = 0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) s0 += (double)Pr2[3 * i + k] * (double)Pr1[3 * j + k];
+                s0 = (((s0 + 0.0) + 0.0) + 0.0) * 1.0;
+                M[3 * i + j] = (float)s0;
+            }
+        Jac4 J;
+        J.W[0] = M[0] + M[4] + M[8];    // N11
+        J.U[0] = M[5] - M[7];           // N12
+        J.U[1] = M[6] - M[2];           // N13
+        J.U[2] = M[1] - M[3];           // N14
+        J.W[1] = M[0] - M[4] - M[8];    // N22
+        J.U[3] = M[1] + M[3];           // N23
+        J.U[4] = M[6] + M[2];           // N24
+        J.W[2] = -M[0] + M[4] - M[8];   // N33
+        J.U[5] = M[5] + M[7];           // N34
+        J.W[3] = -M[0] - M[4] + M[8];   // N44
+        jac_eigen_row0(J, q);
+        float vec[3] = {q[1], q[2], q[3]};
+        double nrm = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nrm += (double)vec[k] * (double)vec[k];
+        nrm = sqrt(nrm);
+        const double ang = atan2(nrm, (double)q[0]);
+        const double alpha = (2 * ang) * (1. / nrm);  // 2*ang*vec/norm(vec)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) vec[k] = cvt_scale(vec[k], alpha);
+        {  // cvRodrigues2
+            double rx = vec[0], ry = vec[1], rz = vec[2];
+            const double theta = sqrt(rx * rx + ry * ry + rz * rz);
+            if (theta < 2.2204460492503131e-16) {  // DBL_EPSILON
+#pragma unroll
+                for (int k = 0; k < 9; ++k) R[k] = k % 4 == 0 ? 1.0f : 0.0f;
+            } else {
+                const double c = cos(theta), sn = sin(theta), c1 = 1. - c;
+                const double itheta = theta ? 1. / theta : 0.;
+                rx *= itheta, ry *= itheta, rz *= itheta;
+                const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
+                const double r_x[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
+#pragma unroll
+                for (int k = 0; k < 9; ++k) R[k] = (float)(c * (k % 4 == 0 ? 1.0 : 0.0) + c1 * rrt[k] + sn * r_x[k]);
+            }
+        }
+        // P3 = mR12i*Pr2, nom = Pr1.dot(P3) (unrolled by 4), den = the double sum of P3's float squares
+        float P3[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float t = R[3 * i] * Pr2[j] + R[3 * i + 1] * Pr2[3 + j] + R[3 * i + 2] * Pr2[6 + j];
+                P3[3 * i + j] = gemm_out(t, 1.0, 0.0f, 0.0);
+            }
+        double nom = 0;
+        nom += (double)Pr1[0] * P3[0] + (double)Pr1[1] * P3[1] + (double)Pr1[2] * P3[2] + (double)Pr1[3] * P3[3];
+        nom += (double)Pr1[4] * P3[4] + (double)Pr1[5] * P3[5] + (double)Pr1[6] * P3[6] + (double)Pr1[7] * P3[7];
+        nom += (double)Pr1[8] * P3[8];
+        double den = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) den += (double)(P3[k] * P3[k]);
+        ms12i = (float)(nom / den);
+        // mt12i = O1 - ms12i*mR12i*O2: one gemm, alpha = -ms12i, C = O1, beta = 1
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float t = R[3 * i] * O2[0] + R[3 * i + 1] * O2[1] + R[3 * i + 2] * O2[2];
+            t12[i] = gemm_out(t, -(double)ms12i, O1[i], 1.0);
+        }
+        // sR = ms12i*mR12i; sRinv = (1.0/ms12i)*mR12i.t(); tinv = -sRinv*mt12i
+        const double inv_s = 1.0 / (double)ms12i;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                T12[4 * i + j] = cvt_scale(R[3 * i + j], (double)ms12i);
+                T21[4 * i + j] = cvt_scale(R[3 * j + i], inv_s);
+            }
+            T12[4 * i + 3] = t12[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float t = T21[4 * i] * t12[0] + T21[4 * i + 1] * t12[1] + T21[4 * i + 2] * t12[2];
+            T21[4 * i + 3] = gemm_out(t, -1.0, 0.0f, 0.0);
+        }
+    }
+    if (y.T12) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) y.T12[g * 12 + k] = T12[k];
+    }
+    if (y.T21) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) y.T21[g * 12 + k] = T21[k];
+    }
+    if (y.sim3) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) y.sim3[g * 13 + k] = R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y.sim3[g * 13 + 9 + k] = t12[k];
+        y.sim3[g * 13 + 12] = ms12i;
+    }
+    if (y.quat) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y.quat[g * 4 + k] = q[k];
+    }
+    if (y.sets_out) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) y.sets_out[g * 3 + k] = idx[k];
+    }
+}
+
+// What iterate returns per solver: the Sim3 (13 floats) and the mask row of hypothesis first_accept,
+// or of best_at[n_hyp - 1] (mBestT12) when nothing was accepted; NaN and a zero row when the best is
+// still the earlier calls' (best_at < 0).
+__global__ void __launch_bounds__(64) k_sim3_accepted(ConsArgs a, const float* sim3, float* accepted,
+                                                      uint64_t* accepted_mask) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int f = a.first[s];
+    const int h = f >= 0 ? f : a.best_at[(size_t)s * a.n_hyp + a.n_hyp - 1];
+    if (accepted && tid < 13)
+        accepted[(size_t)s * 13 + tid] = h >= 0 ? sim3[((size_t)s * a.n_hyp + h) * 13 + tid] : __builtin_nanf("");
+    if (accepted_mask)
+        for (int w = tid; w < a.W; w += 64)
+            accepted_mask[(size_t)s * a.W + w] = h >= 0 ? a.masks[((size_t)s * a.n_hyp + h) * a.W + w] : 0ull;
+}
+
 template <int MODEL, class HT>
-int launch(const ConsArgs& a, const HT* HA, const HT* HB, hipStream_t st) {
+int launch(const ConsArgs& a, const HT* HA, const HT* HB, hipStream_t st, const HypArgs* hyp = nullptr) {
     hipLaunchKernelGGL((k_cons_prepare<MODEL>), dim3(a.S), dim3(CS_PREP_THREADS), 0, st, a);
     ORB_HIPCHK(hipGetLastError());
+    if (hyp) {
+        hipLaunchKernelGGL(k_sim3_hypotheses, dim3((a.n_hyp + 63) / 64, a.S), dim3(64), 0, st, a, *hyp);
+        ORB_HIPCHK(hipGetLastError());
+    }
     const int tiles = (a.n_hyp + CS_TILE - 1) / CS_TILE;
     const int zg = (std::max(a.W, 1) + CS_WAVES - 1) / CS_WAVES;
     hipLaunchKernelGGL((k_cons_score<MODEL, HT>), dim3(a.S, tiles, zg), dim3(CS_THREADS), 0, st, a, HA, HB);
@@ -489,9 +864,236 @@ int fill_batch(ConsArgs& a, const char* who, const orb_keypoint_t* d_kps, const 
     return ORB_OK;
 }
 
+// Exactly one of sets / rand31, every value in range (the host forms).
+int check_draws(const char* who, int n, int n_hyp, const int32_t* sets, const int32_t* rand31) {
+    if ((sets != nullptr) == (rand31 != nullptr))
+        return fail(ORB_EINVAL, std::string(who) + ": exactly one of sets and rand31 must be given");
+    const int32_t* v = sets ? sets : rand31;
+    for (size_t k = 0; k < (size_t)n_hyp * 3; ++k) {
+        if (sets && (v[k] < 0 || v[k] >= n))
+            return fail(ORB_EINVAL, std::string(who) + ": sets[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
+                                        " is outside [0, n)");
+        if (rand31 && v[k] < 0)
+            return fail(ORB_EINVAL, std::string(who) + ": rand31[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
+                                        " is outside [0, 2^31)");
+    }
+    return ORB_OK;
+}
+
+struct HypHost {  // the host outputs of the generation, each may be NULL
+    float* T12;
+    float* T21;
+    float* sim3;
+    float* quat;
+    int32_t* sets_out;
+    float* accepted;
+};
+
+// One Sim3Solver from compact host arrays: the hypotheses and, with `score`, the consensus on them in
+// one stream-ordered chain.  Without `score` the sigma2 arrays may be NULL (zeros are staged).
+int run_host_sim3(ConsArgs a, bool score, int n, const float* x1, const float* x2, const float* s1, const float* s2,
+                  const int32_t* sets, const int32_t* rand31, const HypHost& o, int32_t* counts, uint64_t* masks,
+                  int32_t* best_at, int32_t* first, int best_in, int device) {
+    int ndev = 0;
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
+    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
+    ORB_HIPCHK(hipSetDevice(device));
+    const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
+    const size_t nh = (size_t)n_hyp;
+    // staging: in  [x1 | x2 | s1 | s2 | draws | best_in]
+    //          out [counts | best_at | first, n | T12 | T21 | sim3 | quat | sets | accepted | masks]
+    //          then the SoA scratch (device only)
+    const size_t o1 = 0, o2 = al(o1 + (size_t)n * 12), o3 = al(o2 + (size_t)n * 12), o4 = al(o3 + (size_t)n * 4),
+                 oD = al(o4 + (size_t)n * 4), oI = al(oD + nh * 12), in_end = al(oI + 4);
+    const size_t oC = in_end, oB = al(oC + nh * 4), oF = al(oB + nh * 4), oT12 = al(oF + 8), oT21 = al(oT12 + nh * 48),
+                 oS = al(oT21 + nh * 48), oQ = al(oS + nh * 52), oSet = al(oQ + nh * 16), oA = al(oSet + nh * 12),
+                 oM = al(oA + 52), out_end = al(oM + nh * W * 8), total = al(out_end + (size_t)NV_SIM3 * cap * 4);
+    if (int r = C->reserve(total, out_end)) return r;
+    uint8_t* hp = C->pinned;
+    if (n) {
+        std::memcpy(hp + o1, x1, (size_t)n * 12);
+        std::memcpy(hp + o2, x2, (size_t)n * 12);
+        if (s1) std::memcpy(hp + o3, s1, (size_t)n * 4); else std::memset(hp + o3, 0, (size_t)n * 4);
+        if (s2) std::memcpy(hp + o4, s2, (size_t)n * 4); else std::memset(hp + o4, 0, (size_t)n * 4);
+    }
+    std::memcpy(hp + oD, sets ? sets : rand31, nh * 12);
+    std::memcpy(hp + oI, &best_in, 4);
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    uint8_t* d = C->buf;
+    a.c0 = (const float*)(d + o1);
+    a.c1 = (const float*)(d + o2);
+    a.c2 = (const float*)(d + o3);
+    a.c3 = (const float*)(d + o4);
+    a.n_direct = n;
+    a.best_in = (const int32_t*)(d + oI);
+    a.soa = (float*)(d + out_end);
+    a.counts = (int32_t*)(d + oC);
+    a.best_at = (int32_t*)(d + oB);
+    a.first = (int32_t*)(d + oF);
+    a.n = a.first + 1;
+    a.index = nullptr;
+    a.masks = W ? (uint64_t*)(d + oM) : nullptr;
+    a.cap = cap;
+    a.S = 1;
+    a.W = W;
+    HypArgs y{};
+    (sets ? y.sets : y.rand31) = (const int32_t*)(d + oD);
+    y.T12 = (float*)(d + oT12);
+    y.T21 = (float*)(d + oT21);
+    y.sim3 = (float*)(d + oS);
+    y.quat = (float*)(d + oQ);
+    y.sets_out = (int32_t*)(d + oSet);
+    int r = ORB_OK;
+    hipError_t e = hipSuccess;
+    if (score) {
+        r = launch<SIM3, float>(a, y.T12, y.T21, C->stream, &y);
+        if (r == ORB_OK) {
+            hipLaunchKernelGGL(k_sim3_accepted, dim3(1), dim3(64), 0, C->stream, a, y.sim3, (float*)(d + oA),
+                               (uint64_t*)nullptr);
+            e = hipGetLastError();
+        }
+    } else {
+        hipLaunchKernelGGL((k_cons_prepare<SIM3>), dim3(1), dim3(CS_PREP_THREADS), 0, C->stream, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_sim3_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, C->stream, a, y);
+            e = hipGetLastError();
+        }
+    }
+    if (r == ORB_OK && e == hipSuccess)
+        e = hipMemcpyAsync(hp + oC, d + oC, out_end - oC, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
+    if (r) return r;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+    if (score) {
+        if (counts) std::memcpy(counts, hp + oC, nh * 4);
+        if (best_at) std::memcpy(best_at, hp + oB, nh * 4);
+        if (first) std::memcpy(first, hp + oF, 4);
+        if (masks && W) std::memcpy(masks, hp + oM, nh * W * 8);
+        if (o.accepted) std::memcpy(o.accepted, hp + oA, 52);
+    }
+    if (o.T12) std::memcpy(o.T12, hp + oT12, nh * 48);
+    if (o.T21) std::memcpy(o.T21, hp + oT21, nh * 48);
+    if (o.sim3) std::memcpy(o.sim3, hp + oS, nh * 52);
+    if (o.quat) std::memcpy(o.quat, hp + oQ, nh * 16);
+    if (o.sets_out) std::memcpy(o.sets_out, hp + oSet, nh * 12);
+    return ORB_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int orb_sim3_compute_hypotheses(int n, const float* x3dc1, const float* x3dc2, int n_hyp, const int32_t* sets,
+                                const int32_t* rand31, float* T12, float* T21, float* sim3, float* quat,
+                                int32_t* sets_out, int device) {
+    const char* who = "sim3_compute_hypotheses";
+    if (n < 1 || !x3dc1 || !x3dc2) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (int r = check_limits(who, n, n_hyp)) return r;
+    if (int r = check_draws(who, n, n_hyp, sets, rand31)) return r;
+    if (rand31 && n < 3) return fail(ORB_EINVAL, std::string(who) + ": a minimal set is drawn from n >= 3 correspondences");
+    ConsArgs a{};
+    a.K1[0] = a.K1[1] = a.K2[0] = a.K2[1] = 1.0f;
+    a.n_hyp = n_hyp;
+    a.min_inliers = 0;
+    const HypHost o{T12, T21, sim3, quat, sets_out, nullptr};
+    return run_host_sim3(a, false, n, x3dc1, x3dc2, nullptr, nullptr, sets, rand31, o, nullptr, nullptr, nullptr, nullptr, 0,
+                         device);
+}
+
+int orb_sim3_ransac(int n, const float* x3dc1, const float* x3dc2, const float* sigma2_1, const float* sigma2_2,
+                    const float* K1, const float* K2, int n_hyp, const int32_t* sets, const int32_t* rand31,
+                    int min_inliers, int best_in, int32_t* counts, uint64_t* masks, int32_t* best_at,
+                    int32_t* first_accept, float* T12, float* T21, float* sim3, int32_t* sets_out, float* accepted,
+                    int device) {
+    const char* who = "sim3_ransac";
+    if (n < 0 || (n && (!x3dc1 || !x3dc2 || !sigma2_1 || !sigma2_2)) || !K1 || !K2)
+        return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (int r = check_limits(who, n, n_hyp)) return r;
+    if (min_inliers < 3)
+        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 3, the size of a minimal set (got " +
+                                    std::to_string(min_inliers) + ")");
+    if (int r = check_draws(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_sigma2(who, sigma2_1, n, true)) return r;
+    if (int r = check_sigma2(who, sigma2_2, n, true)) return r;
+    ConsArgs a{};
+    std::memcpy(a.K1, K1, 16);
+    std::memcpy(a.K2, K2, 16);
+    a.n_hyp = n_hyp;
+    a.min_inliers = min_inliers;
+    const HypHost o{T12, T21, sim3, nullptr, sets_out, accepted};
+    return run_host_sim3(a, true, n, x3dc1, x3dc2, sigma2_1, sigma2_2, sets, rand31, o, counts, masks, best_at,
+                         first_accept, best_in, device);
+}
+
+int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                 const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                 const float* d_mp_pos, const uint8_t* d_mp_bad, const float* d_pose,
+                                 const float* level_sigma2, int nlevels, const float* K, int n_hyp,
+                                 const int32_t* d_rand31, int min_inliers, const int32_t* d_best_in, int32_t* d_n,
+                                 int32_t* d_index, int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                 int32_t* d_first_accept, float* d_T12, float* d_T21, float* d_sim3,
+                                 int32_t* d_sets_out, float* d_accepted, uint64_t* d_accepted_mask, void* stream) {
+    const char* who = "sim3_ransac_batch";
+    ConsArgs a{};
+    if (int r = fill_batch(a, who, d_kps, d_counts, cap, S, d_pair_a, d_pair_b, d_match, d_mp_pos, d_mp_bad,
+                           level_sigma2, nlevels, n_hyp, true))
+        return r;
+    if (min_inliers < 3)
+        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 3, the size of a minimal set (got " +
+                                    std::to_string(min_inliers) + ")");
+    if (S == 0) return ORB_OK;
+    if (!d_pose || !K) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (!d_rand31) return fail(ORB_EINVAL, std::string(who) + ": no rand31 values given");
+    hipStream_t st = (hipStream_t)stream;
+    a.pose = d_pose;
+    std::memcpy(a.K1, K, 16);
+    std::memcpy(a.K2, K, 16);
+    a.min_inliers = min_inliers;
+    a.best_in = d_best_in;
+    a.index = d_index;
+    // stream-ordered scratch for the SoA values and for every array the chain needs and the caller
+    // did not ask for
+    const size_t SH = (size_t)S * n_hyp;
+    const bool want_acc = d_accepted || d_accepted_mask;
+    const size_t need[9] = {(size_t)S * NV_SIM3 * cap * 4,
+                            d_n ? 0 : (size_t)S * 4,
+                            d_counts_out ? 0 : SH * 4,
+                            d_T12 ? 0 : SH * 48,
+                            d_T21 ? 0 : SH * 48,
+                            d_sim3 || !d_accepted ? 0 : SH * 52,
+                            d_best_at || !want_acc ? 0 : SH * 4,
+                            d_first_accept || !want_acc ? 0 : (size_t)S * 4,
+                            d_masks || !d_accepted_mask ? 0 : SH * a.W * 8};
+    size_t off[10] = {0};
+    for (int k = 0; k < 9; ++k) off[k + 1] = off[k] + al(need[k]);
+    uint8_t* tmp = nullptr;
+    hipError_t e = hipMallocAsync((void**)&tmp, off[9], st);
+    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("solvers: scratch: ") + hipGetErrorString(e));
+    a.soa = (float*)tmp;
+    a.n = d_n ? d_n : (int32_t*)(tmp + off[1]);
+    a.counts = d_counts_out ? d_counts_out : (int32_t*)(tmp + off[2]);
+    HypArgs y{};
+    y.rand31 = d_rand31;
+    y.T12 = d_T12 ? d_T12 : (float*)(tmp + off[3]);
+    y.T21 = d_T21 ? d_T21 : (float*)(tmp + off[4]);
+    y.sim3 = d_sim3 ? d_sim3 : (need[5] ? (float*)(tmp + off[5]) : nullptr);
+    y.sets_out = d_sets_out;
+    a.best_at = d_best_at ? d_best_at : (need[6] ? (int32_t*)(tmp + off[6]) : nullptr);
+    a.first = d_first_accept ? d_first_accept : (need[7] ? (int32_t*)(tmp + off[7]) : nullptr);
+    a.masks = d_masks ? d_masks : (need[8] ? (uint64_t*)(tmp + off[8]) : nullptr);
+    int r = launch<SIM3, float>(a, y.T12, y.T21, st, &y);
+    if (r == ORB_OK && want_acc) {
+        hipLaunchKernelGGL(k_sim3_accepted, dim3(S), dim3(64), 0, st, a, y.sim3, d_accepted, d_accepted_mask);
+        e = hipGetLastError();
+        if (e != hipSuccess) r = fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+    }
+    (void)hipFreeAsync(tmp, st);
+    return r;
+}
 
 int orb_pnp_check_inliers(int n, const float* p3d, const float* p2d, const float* sigma2, float th2, double fu,
                           double fv, double uc, double vc, int n_hyp, const double* R, const double* t,

@@ -2,10 +2,12 @@
 src/Sim3Solver.cc), over the C ABI of ``include/orb_abi.h`` (csrc/orb_solvers.hip).
 
 ``CheckInliers`` for all hypotheses of a solver in one call, with the constructors'
-per-correspondence set-up and the keep-the-best rule of ``iterate``.  The hypotheses (EPnP
-``compute_pose``, ``Refine``'s pose, Horn's ``computeT``), the random minimal sets and the
-iteration counters are the caller's.  ``pnp_ransac_parameters`` / ``sim3_ransac_parameters`` are
-the scalar arithmetic of the two ``SetRansacParameters``.
+per-correspondence set-up and the keep-the-best rule of ``iterate``.  For PnP the hypotheses (EPnP
+``compute_pose``, ``Refine``'s pose), the random minimal sets and the iteration counters are the
+caller's.  For Sim3, ``Sim3Ransac`` also draws the minimal sets from the caller's ``rand()`` values
+and runs Horn's ``computeT`` on the device, so a whole ``iterate`` is one call; the package owns no
+random generator.  ``pnp_ransac_parameters`` / ``sim3_ransac_parameters`` are the scalar arithmetic
+of the two ``SetRansacParameters``.
 """
 from __future__ import annotations
 
@@ -233,3 +235,127 @@ def _rows012(T) -> np.ndarray:
     if T.ndim >= 2 and T.shape[-2:] == (4, 4):
         T = T.reshape(-1, 4, 4)[:, :3, :]
     return np.ascontiguousarray(T, np.float32).reshape(-1, 12)
+
+
+def sim3_minimal_sets(N: int, rand31, fixed: bool = False) -> np.ndarray:
+    """The minimal sets of Sim3Solver::iterate (Sim3Solver.cc:163-177) for (n_hyp, 3) values of
+    ``rand()``: draw i is ``RandomInt(0, size - 1) = (r * size) >> 31`` on the list of size N - i,
+    and ``vAvailableIndices[idx] = back(); pop_back()`` overwrites the entry at the value drawn, not
+    at the position, so a set may hold an index twice.  The list is N entries whose size shrinks;
+    the write may land one slot past the size, where nothing reads it.  ``fixed`` removes by
+    position instead (what the reference meant; for tests)."""
+    N = int(N)
+    r = np.asarray(rand31, np.int64).reshape(-1, 3)
+    if N < 3:
+        raise ValueError("a minimal set is drawn from at least 3 correspondences")
+    if r.size and (r.min() < 0 or r.max() >= 2 ** 31):
+        raise ValueError("rand31 values must be in [0, 2^31)")
+    sets = np.zeros((len(r), 3), np.int32)
+    for h in range(len(r)):
+        avail = list(range(N))
+        size = N
+        for i in range(3):
+            randi = (int(r[h, i]) * size) >> 31
+            idx = avail[randi]
+            sets[h, i] = idx
+            avail[randi if fixed else idx] = avail[size - 1]
+            size -= 1
+    return sets
+
+
+def _draws(sets, rand31):
+    if (sets is None) == (rand31 is None):
+        raise ValueError("exactly one of sets and rand31 must be given")
+    a = np.asarray(sets if rand31 is None else rand31)
+    if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
+        raise ValueError("rand31 values must be in [0, 2^31)")
+    a = np.ascontiguousarray(a, np.int32).reshape(-1, 3)
+    return (a, None, len(a)) if rand31 is None else (None, a, len(a))
+
+
+class Sim3Ransac(Sim3Consensus):
+    """A whole Sim3Solver::iterate on the GPU (Sim3Solver.cc:140-207): the minimal sets from the
+    caller's ``rand()`` values, Horn's closed form (``computeT``) per set, ``CheckInliers`` and the
+    keep-the-best rule, in one call.  K1 / K2 / min_inliers as for Sim3Consensus; min_inliers >= 3."""
+
+    def compute_hypotheses(self, x3dc1, x3dc2, sets=None, rand31=None) -> dict:
+        """``computeT`` alone (orb_sim3_compute_hypotheses; host buffers, synchronous) for (n_hyp, 3)
+        ``sets`` of indices or ``rand31`` values.  Returns T12 / T21 (n_hyp, 3, 4), sim3 (n_hyp, 13: R
+        row-major, t, s), quat (n_hyp, 4: the best eigenvector of Horn's N, w first) and sets."""
+        x1, x2 = _f32(x3dc1, 3), _f32(x3dc2, 3)
+        n = len(x1)
+        if len(x2) != n:
+            raise ValueError("x3dc1 and x3dc2 must hold one entry per correspondence")
+        sets, rand31, n_hyp = _draws(sets, rand31)
+        m = max(n_hyp, 1)
+        T12, T21 = np.zeros((m, 3, 4), np.float32), np.zeros((m, 3, 4), np.float32)
+        sim3, quat, sets_out = np.zeros((m, 13), np.float32), np.zeros((m, 4), np.float32), np.zeros((m, 3), np.int32)
+        check(self._lib.orb_sim3_compute_hypotheses(n, ptr(x1), ptr(x2), n_hyp, ptr(sets), ptr(rand31), ptr(T12),
+                                                    ptr(T21), ptr(sim3), ptr(quat), ptr(sets_out), self.device))
+        return {"T12": T12[:n_hyp], "T21": T21[:n_hyp], "sim3": sim3[:n_hyp], "quat": quat[:n_hyp],
+                "sets": sets_out[:n_hyp]}
+
+    def iterate(self, x3dc1, x3dc2, sigma2_1, sigma2_2, sets=None, rand31=None, best_in: int = 0,
+                want_masks: bool = True) -> dict:
+        """One ``iterate(n_hyp, ...)`` without its early return (orb_sim3_ransac; host buffers,
+        synchronous).  Returns what Sim3Consensus.check returns plus T12, T21, sim3, sets and
+        ``accepted`` (13,): the Sim3 of hypothesis first_accept, or of best_at[-1] when nothing was
+        accepted (NaN while the best is still an earlier call's)."""
+        x1, x2, s1, s2 = _f32(x3dc1, 3), _f32(x3dc2, 3), _f32(sigma2_1, 0), _f32(sigma2_2, 0)
+        n = len(x1)
+        if len(x2) != n or len(s1) != n or len(s2) != n:
+            raise ValueError("x3dc1, x3dc2 and the sigma2 arrays must hold one entry per correspondence")
+        sets, rand31, n_hyp = _draws(sets, rand31)
+        counts, masks, best_at, first, W = _host_outputs(n_hyp, n)
+        m = max(n_hyp, 1)
+        T12, T21 = np.zeros((m, 3, 4), np.float32), np.zeros((m, 3, 4), np.float32)
+        sim3, sets_out, accepted = np.zeros((m, 13), np.float32), np.zeros((m, 3), np.int32), np.zeros(13, np.float32)
+        check(self._lib.orb_sim3_ransac(
+            n, ptr(x1), ptr(x2), ptr(s1), ptr(s2), ptr(self.K1), ptr(self.K2), n_hyp, ptr(sets), ptr(rand31),
+            self.min_inliers, int(best_in), ptr(counts), ptr(masks) if want_masks else None, ptr(best_at),
+            ctypes.byref(first), ptr(T12), ptr(T21), ptr(sim3), ptr(sets_out), ptr(accepted), self.device))
+        out = {"n": n, "counts": counts[:n_hyp], "best_at": best_at[:n_hyp], "first_accept": int(first.value),
+               "T12": T12[:n_hyp], "T21": T21[:n_hyp], "sim3": sim3[:n_hyp], "sets": sets_out[:n_hyp],
+               "accepted": accepted}
+        if want_masks:
+            mm = masks.reshape(-1)[:n_hyp * W].reshape(n_hyp, W)
+            out.update(masks=mm, inliers=unpack_mask(mm, n) if W else np.zeros((n_hyp, 0), bool))
+        return out
+
+    def iterate_batch_device(self, d_kps, d_counts, pair_1, pair_2, d_match, d_mp_pos, d_mp_bad, d_pose, level_sigma2,
+                             d_rand31, d_best_in=None, stream=None) -> dict:
+        """S solvers on device-resident data (orb_sim3_ransac_batch_device): as
+        Sim3Consensus.check_batch_device with d_rand31 (S, n_hyp, 3) int32 in place of the
+        hypotheses (a negative value is clamped to 0).  Returns its device tensors plus T12 / T21 (S,
+        n_hyp, 12), sim3 (S, n_hyp, 13), sets (S, n_hyp, 3), accepted (S, 13: what
+        Optimizer.optimize_sim3_batch_device takes as d_sim3_in) and accepted_mask (S, W) int64.
+        Asynchronous on `stream`."""
+        import torch
+
+        S, cap = int(d_match.shape[0]), int(d_kps.shape[1])
+        if int(d_match.shape[1]) != cap:
+            raise ValueError("d_match must be (S, cap)")
+        dev = d_kps.device
+        if d_rand31.dtype != torch.int32 or d_rand31.dim() != 3 or int(d_rand31.shape[0]) != S or int(d_rand31.shape[2]) != 3:
+            raise ValueError("d_rand31 must be an int32 tensor (S, n_hyp, 3)")
+        d_rand31 = d_rand31.contiguous()
+        n_hyp = int(d_rand31.shape[1])
+        ls2 = np.ascontiguousarray(level_sigma2, np.float32)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            out = _batch_outputs(torch, S, cap, n_hyp, dev)
+            W = (cap + 63) // 64
+            out.update(T12=torch.empty((S, n_hyp, 12), dtype=torch.float32, device=dev),
+                       T21=torch.empty((S, n_hyp, 12), dtype=torch.float32, device=dev),
+                       sim3=torch.empty((S, n_hyp, 13), dtype=torch.float32, device=dev),
+                       sets=torch.empty((S, n_hyp, 3), dtype=torch.int32, device=dev),
+                       accepted=torch.empty((S, 13), dtype=torch.float32, device=dev),
+                       accepted_mask=torch.empty((S, W), dtype=torch.int64, device=dev))
+        check(self._lib.orb_sim3_ransac_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, S, ptr(pair_1), ptr(pair_2), ptr(d_match), ptr(d_mp_pos), ptr(d_mp_bad),
+            ptr(d_pose), ptr(ls2), len(ls2), ptr(self.K1), n_hyp, ptr(d_rand31), self.min_inliers, ptr(d_best_in),
+            ptr(out["n"]), ptr(out["index"]), ptr(out["counts"]), ptr(out["masks"]), ptr(out["best_at"]),
+            ptr(out["first"]), ptr(out["T12"]), ptr(out["T21"]), ptr(out["sim3"]), ptr(out["sets"]),
+            ptr(out["accepted"]), ptr(out["accepted_mask"]), ctypes.c_void_p(s.cuda_stream)))
+        out["first_accept"] = out.pop("first")
+        return out
