@@ -186,6 +186,27 @@ __device__ __forceinline__ int predict_level(const DView& T, float ratio) {  // 
 __device__ __forceinline__ bool kf_in_image(const DView& T, float x, float y) {  // KeyFrame.cc:654-657
     return x >= (float)T.minX && x < (float)T.maxX && y >= (float)T.minY && y < (float)T.maxY;
 }
+// (int) of a float the way the reference's x86 build converts it (cvttss2si): NaN and every value
+// outside int's range give INT_MIN.  C++ leaves these conversions undefined, and the GPU's own
+// conversion gives 0 for NaN and saturates, which would file a NaN keypoint in cell 0, send a NaN
+// box edge to cell 0 and an infinite one to the last cell (FP policy).
+__device__ __forceinline__ int cvt_x86(float v) {
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MIN;
+}
+struct CellRange {
+    int minCX, maxCX, minCY, maxCY;
+};
+// The cell range of a search box (Frame.cc:205-223 / KeyFrame.cc:617-635); false: no cell.
+__device__ __forceinline__ bool cell_range(const DView& T, float u, float v, float r, CellRange& c) {
+    c.minCX = max(0, cvt_x86(floorf((u - (float)T.minX - r) * T.invW)));
+    if (c.minCX >= GRID_COLS) return false;
+    c.maxCX = min(GRID_COLS - 1, cvt_x86(ceilf((u - (float)T.minX + r) * T.invW)));
+    if (c.maxCX < 0) return false;
+    c.minCY = max(0, cvt_x86(floorf((v - (float)T.minY - r) * T.invH)));
+    if (c.minCY >= GRID_ROWS) return false;
+    c.maxCY = min(GRID_ROWS - 1, cvt_x86(ceilf((v - (float)T.minY + r) * T.invH)));
+    return c.maxCY >= 0;
+}
 __device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:668-675
     float rot = a1 - a2;
     if (rot < 0.0f) rot += 360.0f;
@@ -228,8 +249,8 @@ __global__ void __launch_bounds__(1024) k_grid_build(const orb_keypoint_t* __res
     __shared__ int s_wt[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto cell_of = [&](int i) {
-        const int px = (int)roundf((kps[i].x - (float)minX) * invW);
-        const int py = (int)roundf((kps[i].y - (float)minY) * invH);
+        const int px = cvt_x86(roundf((kps[i].x - (float)minX) * invW));
+        const int py = cvt_x86(roundf((kps[i].y - (float)minY) * invH));
         return (px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS) ? -1 : px * GRID_ROWS + py;
     };
     for (int c = tid; c < NCELLS; c += 1024) s_cnt[c] = 0;
@@ -460,19 +481,9 @@ __device__ __forceinline__ void enum_candidates(const Job& J, const QP& p, int l
         for (int pos = p.lo + lane; pos < p.hi; pos += 64) visit(pos, T.items[pos]);
         return;
     }
-    // Frame.cc:205-223 / KeyFrame.cc:617-635
-    int minCX = (int)floorf((p.u - (float)T.minX - p.r) * T.invW);
-    minCX = max(0, minCX);
-    if (minCX >= GRID_COLS) return;
-    int maxCX = (int)ceilf((p.u - (float)T.minX + p.r) * T.invW);
-    maxCX = min(GRID_COLS - 1, maxCX);
-    if (maxCX < 0) return;
-    int minCY = (int)floorf((p.v - (float)T.minY - p.r) * T.invH);
-    minCY = max(0, minCY);
-    if (minCY >= GRID_ROWS) return;
-    int maxCY = (int)ceilf((p.v - (float)T.minY + p.r) * T.invH);
-    maxCY = min(GRID_ROWS - 1, maxCY);
-    if (maxCY < 0) return;
+    CellRange c;
+    if (!cell_range(T, p.u, p.v, p.r, c)) return;
+    const int minCX = c.minCX, maxCX = c.maxCX, minCY = c.minCY, maxCY = c.maxCY;
     const bool kfArea = p.flags & 2, post = p.flags & 4;
     const bool checkLevels = !(p.aMin == -1 && p.aMax == -1), sameLevel = checkLevels && p.aMin == p.aMax;
     for (int ix = minCX; ix <= maxCX; ++ix) {
@@ -588,18 +599,9 @@ __global__ void __launch_bounds__(256) k_area_fill(Job J) {
     // enum_candidates visits in strided lane order; wrap each 64-candidate batch of a cell
     // range with a ballot so the output keeps the traversal order
     const DView& T = J.T;
-    int minCX = (int)floorf((p.u - (float)T.minX - p.r) * T.invW);
-    minCX = max(0, minCX);
-    if (minCX >= GRID_COLS) return;
-    int maxCX = (int)ceilf((p.u - (float)T.minX + p.r) * T.invW);
-    maxCX = min(GRID_COLS - 1, maxCX);
-    if (maxCX < 0) return;
-    int minCY = (int)floorf((p.v - (float)T.minY - p.r) * T.invH);
-    minCY = max(0, minCY);
-    if (minCY >= GRID_ROWS) return;
-    int maxCY = (int)ceilf((p.v - (float)T.minY + p.r) * T.invH);
-    maxCY = min(GRID_ROWS - 1, maxCY);
-    if (maxCY < 0) return;
+    CellRange c;
+    if (!cell_range(T, p.u, p.v, p.r, c)) return;
+    const int minCX = c.minCX, maxCX = c.maxCX, minCY = c.minCY, maxCY = c.maxCY;
     const bool kfArea = p.flags & 2;
     const bool checkLevels = !(p.aMin == -1 && p.aMax == -1), sameLevel = checkLevels && p.aMin == p.aMax;
     for (int ix = minCX; ix <= maxCX; ++ix) {

@@ -1,6 +1,8 @@
 """GPU parity of the ORBmatcher family (csrc/orb_match.hip) against the CPU oracle
 (oracle/orb_oracle_match.cpp): identical match arrays and counts, bit for bit, on seeded
-synthetic scenes (tests/scenes.py) that hit every acceptance / rejection branch."""
+synthetic scenes (tests/scenes.py) that hit every acceptance / rejection branch.  A random
+float never lands on a threshold: the geometric gates' behaviour exactly on and next to their
+bounds, and on NaN / inf inputs, lives in tests/test_gpu_matcher_gates.py."""
 import numpy as np
 import pytest
 
