@@ -614,6 +614,55 @@ int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_
                                        int32_t* d_best_f, float* d_best_score_f, uint8_t* d_inliers_f,
                                        int32_t* d_n_matches, void* stream);
 
+/* The hypotheses on the device: everything of Initializer::Initialize (Initializer.cc:44-221) up to
+ * the point where H, F, SH, SF, the two inlier vectors and RH are known: mvMatches12, the minimal
+ * sets (80-95), Normalize (747-793) over all keypoints of each frame, ComputeH21 / ComputeF21
+ * (224-301) with cv::SVDecomp as OpenCV 2.4's JacobiSVDImpl_<float> is read, T2inv*Hn*T1,
+ * H21i.inv() and T2t*Fn*T1, then the two checks above unchanged.  ReconstructH /
+ * ReconstructF stay with the caller.
+ * The draws are the caller's: rand31 holds the n_hyp x 8 values rand() returned, in the order the
+ * reference consumes them; draw j of a set is RandomInt(0, N - j - 1) = (r * (N - j)) >> 31 on a
+ * list that loses the drawn position (a set never repeats an index); one set serves both models.
+ * N is the number of matches.  With N < 8 (the reference would pop from an empty vector) nothing
+ * is generated: the hypothesis and set rows are written as zeros, so the best indices are -1, SH =
+ * SF = 0, the masks 0, RH = 0/0 and no model is chosen.  Nothing is repaired: a frame with no
+ * keypoints or no deviation in a coordinate gives inf / NaN, which flow on.
+ * Limits as above: 8192 keypoints per frame, 1 <= n_hyp <= 1024.
+ *
+ * ComputeH21 / ComputeF21 alone, host buffers, synchronous.  Exactly one of `sets` (n_hyp x 8 match
+ * ordinals, each in [0, N)) and `rand31` (each >= 0) is given (ORB_EINVAL otherwise).  Outputs, any
+ * may be NULL: H21, H12, F21 (n_hyp x 9, the layout orb_initializer_check reads), Hn, Fn (the
+ * normalised solutions), T1, T2 (9 floats each), sets_out (n_hyp x 8), *n_matches = N. */
+int orb_initializer_compute_hypotheses(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                                       const int32_t* matches12, int n_hyp, const int32_t* sets, const int32_t* rand31,
+                                       float* H21, float* H12, float* F21, float* Hn, float* Fn, float* T1, float* T2,
+                                       int32_t* sets_out, int* n_matches, int device);
+/* The whole of it for one pair, host buffers, synchronous: the outputs of orb_initializer_check for
+ * the generated hypotheses, the hypotheses and sets themselves, and per pair best_H21 / best_F21 (9
+ * floats: H and F of Initialize, NaN when the best index is -1), *RH = SH / (SH + SF) and *use_h =
+ * (RH > 0.40), the model Initialize would reconstruct from (Initializer.cc:113).  A negative draw
+ * is ORB_EINVAL.  Any output may be NULL. */
+int orb_initializer_ransac(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                           const int32_t* matches12, float sigma, int n_hyp, const int32_t* rand31, float* H21,
+                           float* H12, float* F21, int32_t* sets_out, float* scores_h, float* scores_f, int32_t* best_h,
+                           float* best_score_h, uint8_t* inliers_h, int32_t* best_f, float* best_score_f,
+                           uint8_t* inliers_f, float* best_H21, float* best_F21, float* RH, int32_t* use_h,
+                           int* n_matches, int device);
+/* The same for P pairs on device-resident extractor and matcher output: the arguments, limits and
+ * precondition of orb_initializer_check_batch_device with d_rand31 (P x n_hyp x 8 int32; a
+ * negative value counts as 0) in place of the hypotheses, and the outputs d_H21 / d_H12 / d_F21 (P
+ * x n_hyp x 9), d_sets_out (P x n_hyp x 8), d_best_H21 / d_best_F21 (P x 9), d_RH (P floats),
+ * d_use_h (P int32).  Any output may be NULL; what later kernels need of an absent one lives in
+ * stream-ordered scratch for the length of the call.  Asynchronous on `stream`. */
+int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                        const int32_t* d_pair_f1, const int32_t* d_pair_f2,
+                                        const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
+                                        float* d_H21, float* d_H12, float* d_F21, int32_t* d_sets_out,
+                                        float* d_scores_h, float* d_scores_f, int32_t* d_best_h, float* d_best_score_h,
+                                        uint8_t* d_inliers_h, int32_t* d_best_f, float* d_best_score_f,
+                                        uint8_t* d_inliers_f, int32_t* d_n_matches, float* d_best_H21,
+                                        float* d_best_F21, float* d_RH, int32_t* d_use_h, void* stream);
+
 /* ---- Solvers: PnP / Sim3 RANSAC consensus (GPU: csrc/orb_solvers.hip) ---------------- */
 /* PnPsolver::CheckInliers (reference src/PnPsolver.cc:280-311) and Sim3Solver::CheckInliers
  * (src/Sim3Solver.cc:335-359) for all RANSAC hypotheses of a solver at once, with the

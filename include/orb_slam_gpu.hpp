@@ -13,7 +13,8 @@
 // gpu::KeyFrameDatabase re-exposes KeyFrameDatabase (include/KeyFrameDatabase.h:44-71) over
 // keyframe ids, and gpu::score is mpVoc->score(...) (L1 vocabularies).  gpu::Initializer is the
 // scoring half of Initializer (include/Initializer.h:31-97): FindHomography / FindFundamental over
-// hypotheses the caller has computed.  gpu::PnPsolver and gpu::Sim3Solver are the consensus halves
+// hypotheses the caller has computed, and Initialize up to the Reconstruct* call with the hypotheses
+// computed on the device from the caller's rand() values.  gpu::PnPsolver and gpu::Sim3Solver are the consensus halves
 // of PnPsolver (include/PnPsolver.h) and Sim3Solver (include/Sim3Solver.h): CheckInliers and the
 // keep-the-best rule of iterate over poses the caller has computed.  gpu::Optimizer::PoseOptimization
 // is Optimizer::PoseOptimization (include/Optimizer.h), the motion-only optimisation, whole, and
@@ -372,7 +373,8 @@ private:
 // the front of each RANSAC iteration as the reference does (minimal set, ComputeH21 / ComputeF21,
 // the T2inv*Hn*T1, H21i.inv() and T2t*Fn*T1 products) for ALL iterations first and hands the
 // matrices over, 9 row-major floats per iteration; one call then scores them all and keeps the
-// best as the reference's loop does.
+// best as the reference's loop does.  Initialize(keys2, vMatches12, rand31) does
+// all of it, the front of every iteration included, on the device in one call.
 class Initializer {
 public:
     // Initializer(ReferenceFrame, sigma, iterations) (Initializer.cc:33-42): keys1 = the
@@ -407,6 +409,48 @@ public:
                         std::vector<float>& F21) {
         need(vF21);
         return find(nullptr, nullptr, vF21.data(), vF21, vbMatchesInliers, score, F21);
+    }
+
+    // What Initialize (Initializer.cc:44-116) knows when it calls ReconstructH / ReconstructF.
+    struct TwoViewModels {
+        std::vector<float> H, F;                                 // 9 floats each; empty without a winner, as the reference's cv::Mat
+        float SH, SF, RH;                                        // RH = SH / (SH + SF)
+        std::vector<bool> vbMatchesInliersH, vbMatchesInliersF;  // N flags each
+        bool bUseH;                                              // RH > 0.40: ReconstructH would be tried, else ReconstructF
+        int N;                                                   // mvMatches12.size(); below 8 nothing was generated
+        std::vector<std::vector<size_t> > mvSets;                // mMaxIterations x 8
+    };
+    // Initialize (Initializer.cc:44-116) up to the Reconstruct* call, on the device in one call:
+    // the matches, the minimal sets, Normalize, ComputeH21 / ComputeF21 and both checks for all
+    // mMaxIterations iterations.  rand31: the mMaxIterations x 8 values rand() returned, in the
+    // order DUtils::Random::RandomInt would consume them (the package owns no generator).
+    // ReconstructH / ReconstructF (CheckRT, Triangulate, DecomposeE) stay with the caller.
+    TwoViewModels Initialize(const std::vector<orb_keypoint_t>& keys2, const std::vector<int>& vMatches12,
+                             const std::vector<int>& rand31) {
+        if (rand31.size() != (size_t)mMaxIterations * 8) throw std::runtime_error("orb: rand31 must hold mMaxIterations x 8 values");
+        TwoViewModels r;
+        r.N = SetMatches(keys2, vMatches12);
+        std::vector<uint8_t> inH(mvKeys1.size() + 1, 0), inF(mvKeys1.size() + 1, 0);
+        std::vector<int32_t> draws(rand31.begin(), rand31.end()), sets((size_t)mMaxIterations * 8);
+        int32_t bh = -1, bf = -1, use_h = 0;
+        int n = 0;
+        float H[9], F[9];
+        orb_check(orb_initializer_ransac(mvKeys1.data(), (int)mvKeys1.size(), mvKeys2.data(), (int)mvKeys2.size(),
+                                         matches12_.data(), mSigma, mMaxIterations, draws.data(), nullptr, nullptr,
+                                         nullptr, sets.data(), nullptr, nullptr, &bh, &r.SH, inH.data(), &bf, &r.SF,
+                                         inF.data(), H, F, &r.RH, &use_h, &n, device_));
+        if (bh >= 0) r.H.assign(H, H + 9);
+        if (bf >= 0) r.F.assign(F, F + 9);
+        r.bUseH = use_h != 0;
+        r.vbMatchesInliersH.assign((size_t)n, false);
+        r.vbMatchesInliersF.assign((size_t)n, false);
+        for (int i = 0; i < n; ++i) {
+            r.vbMatchesInliersH[(size_t)i] = inH[(size_t)i] != 0;
+            r.vbMatchesInliersF[(size_t)i] = inF[(size_t)i] != 0;
+        }
+        r.mvSets.assign((size_t)mMaxIterations, std::vector<size_t>(8, 0));
+        for (size_t k = 0; k < sets.size(); ++k) r.mvSets[k / 8][k % 8] = (size_t)sets[k];
+        return r;
     }
 
     std::vector<std::pair<int, int> > mvMatches12;  // (index in frame 1, index in frame 2), as the reference's

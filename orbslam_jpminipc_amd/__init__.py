@@ -16,7 +16,7 @@ from .extractor import ORBextractor, keypoints_from_bytes
 from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
-from .initializer import Initializer
+from .initializer import Initializer, InitializerRansac, initializer_minimal_sets
 from .optimizer import Optimizer
 from .solvers import (PnPConsensus, Sim3Consensus, Sim3Ransac, pnp_ransac_parameters, sim3_minimal_sets,
                       sim3_ransac_parameters)
@@ -28,6 +28,8 @@ __all__ = [
     "ORBVocabulary",
     "KeyFrameDatabase",
     "Initializer",
+    "InitializerRansac",
+    "initializer_minimal_sets",
     "Optimizer",
     "PnPConsensus",
     "Sim3Consensus",

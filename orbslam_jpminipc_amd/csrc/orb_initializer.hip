@@ -2,8 +2,9 @@
 //
 // Initializer::CheckHomography (reference src/Initializer.cc:303-386) and CheckFundamental
 // (388-466) for every RANSAC hypothesis of a frame pair at once, plus the "keep the best" rule of
-// FindHomography / FindFundamental (146-169, 197-220).  The hypotheses themselves (ComputeH21 /
-// ComputeF21, cv::SVDecomp) are the caller's.
+// FindHomography / FindFundamental (146-169, 197-220).  In orb_initializer_check[_batch_device] the
+// hypotheses (ComputeH21 / ComputeF21, cv::SVDecomp) are the caller's; the second half of this file
+// generates them on the device and runs the same two kernels behind them.
 //
 // Arithmetic: plain float, the TU is built -ffp-contract=off and the fused multiply-adds that
 // g++ -O3 -march=native makes of the reference's expressions are written out
@@ -475,6 +476,836 @@ int orb_initializer_check(const orb_keypoint_t* kps1, int n1, const orb_keypoint
         if (inliers_f && nm) std::memcpy(inliers_f, hp + oI + cap, (size_t)nm);
     }
     return ORB_OK;
+}
+
+}  // extern "C"
+
+// ---- the hypotheses: minimal sets, Normalize, ComputeH21 / ComputeF21 --------------------------
+//
+// Everything of Initializer::Initialize (Initializer.cc:44-221, 224-301, 747-793) before the two
+// checks above, with the OpenCV 2.4 routines it calls restated as read (the CPU
+// statement of the same reading is tests/native/initializer_ransac_model.cpp, which shares no text
+// with this file).  Plain IEEE f32 / f64 operations only, no contraction, no libm call.
+//
+//   k_init_normalize   one workgroup per (pair, frame side).  Side 0 first lists the pair's matches
+//                      in index order (the keypoint index of every match ordinal, and N).  Wave 0
+//                      then runs Normalize's four float sums as the reference's chains: 64
+//                      keypoints per step loaded one per lane, every lane adding all 64 in order
+//                      (so the sum is uniform), and writes T, the means and the scales.  The
+//                      normalised points themselves are recomputed by the lanes that gather them:
+//                      (x - mean) * s is the same two operations.
+//   k_init_hypotheses  one lane per (pair, model, hypothesis), workgroups of one wave.  The lane's
+//                      work matrices live in LDS laid out [element][lane] (conflict free, any
+//                      runtime index): the 9 x 16 At and 9 x 9 Vt of ComputeH21's decomposition,
+//                      or the 9 x 9 of ComputeF21's with its 3 x 3 behind it, the doubles W, and
+//                      the 8 moved entries of the index list.  Every dot product and sum of
+//                      squares is one double accumulator with k ascending.
+//   k_init_result      one thread per pair: the winning H21 / F21 (NaN without a winner), RH and
+//                      which model Initialize would reconstruct from.
+namespace {
+
+constexpr int HY_A = 144;                                   // floats of the At region (9 x 16)
+constexpr int HY_V = 81;                                    // floats of the Vt region (9 x 9)
+constexpr int HY_LDS = (HY_A + HY_V) * 64 * 4 + 9 * 64 * 8;  // + W: 62208 bytes
+constexpr int HY_NORM = 16;                                 // floats per (pair, side): T, meanX, meanY, sX, sY
+constexpr int HY_MAX_FILL_TRIES = 16;                       // OpenCV's fill-in `while` has no bound; §16
+constexpr int NORM_THREADS = 256;
+
+struct HypArgs {
+    const orb_keypoint_t* kps;
+    const int32_t* counts;
+    const int32_t* pair_f1;
+    const int32_t* pair_f2;
+    const int32_t* matches12;
+    const int32_t* rand31;   // P x n_hyp x 8, or NULL when sets_in is given
+    const int32_t* sets_in;  // P x n_hyp x 8 match ordinals, each in [0, N)
+    int32_t* ord_i;          // P x cap: keypoint index in frame 1 of every match ordinal
+    int32_t* nmatch;         // P
+    float* norm;             // P x 2 x HY_NORM
+    float* H21;              // P x n_hyp x 9 each; any may be NULL
+    float* H12;
+    float* F21;
+    float* Hn;
+    float* Fn;
+    int32_t* sets_out;       // P x n_hyp x 8
+    int cap, P, n_hyp;
+};
+
+__global__ void __launch_bounds__(NORM_THREADS) k_init_normalize(HypArgs a) {
+    __shared__ int s_wtot[NORM_THREADS / 64];
+    const int p = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
+    InitArgs ia{};
+    ia.kps = a.kps;
+    ia.counts = a.counts;
+    ia.pair_f1 = a.pair_f1;
+    ia.pair_f2 = a.pair_f2;
+    ia.matches12 = a.matches12;
+    ia.cap = a.cap;
+    const PairView v = pair_view(ia, p);
+    if (side == 0) {
+        int32_t* ord = a.ord_i + (size_t)p * a.cap;
+        const int N = compact_matches<NORM_THREADS>(v, s_wtot, [&](int o, int i, int) { ord[o] = i; });
+        if (tid == 0) a.nmatch[p] = N;
+    }
+    if (tid >= 64) return;
+    // Normalize (Initializer.cc:747-793) over all n keypoints of the frame, matched or not
+    const orb_keypoint_t* k = side ? v.k2 : v.k1;
+    const int n = side ? v.n2 : v.n1;
+    float meanX = 0, meanY = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + tid;
+        const float x = i < n ? k[i].x : 0.0f, y = i < n ? k[i].y : 0.0f;
+        const int cnt = min(64, n - i0);
+        if (cnt == 64) {
+#pragma unroll
+            for (int j = 0; j < 64; ++j) {
+                meanX += __shfl(x, j);
+                meanY += __shfl(y, j);
+            }
+        } else {
+            for (int j = 0; j < cnt; ++j) {
+                meanX += __shfl(x, j);
+                meanY += __shfl(y, j);
+            }
+        }
+    }
+    meanX = meanX / (float)n;
+    meanY = meanY / (float)n;
+    float meanDevX = 0, meanDevY = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + tid;
+        const float x = i < n ? fabsf(k[i].x - meanX) : 0.0f, y = i < n ? fabsf(k[i].y - meanY) : 0.0f;
+        const int cnt = min(64, n - i0);
+        if (cnt == 64) {
+#pragma unroll
+            for (int j = 0; j < 64; ++j) {
+                meanDevX += __shfl(x, j);
+                meanDevY += __shfl(y, j);
+            }
+        } else {
+            for (int j = 0; j < cnt; ++j) {
+                meanDevX += __shfl(x, j);
+                meanDevY += __shfl(y, j);
+            }
+        }
+    }
+    meanDevX = meanDevX / (float)n;
+    meanDevY = meanDevY / (float)n;
+    const float sX = 1.0f / meanDevX, sY = 1.0f / meanDevY;  // 1.0/(float) narrowed: the float quotient (§11)
+    if (tid == 0) {
+        float* T = a.norm + ((size_t)p * 2 + side) * HY_NORM;
+        T[0] = sX;
+        T[1] = 0.0f;
+        T[2] = -meanX * sX;
+        T[3] = 0.0f;
+        T[4] = sY;
+        T[5] = -meanY * sY;
+        T[6] = 0.0f;
+        T[7] = 0.0f;
+        T[8] = 1.0f;
+        T[9] = meanX;
+        T[10] = meanY;
+        T[11] = sX;
+        T[12] = sY;
+    }
+}
+
+// lapack.cpp's own hypot (found before libm's inside namespace cv)
+__device__ __forceinline__ double hy_hypot(double a, double b) {
+    a = fabs(a);
+    b = fabs(b);
+    if (a > b) {
+        b /= a;
+        return a * __builtin_sqrt(1 + b * b);
+    }
+    if (b > 0) {
+        a /= b;
+        return b * __builtin_sqrt(1 + a * a);
+    }
+    return 0;
+}
+
+// JacobiSVDImpl_<float> on the lane's column of LDS: A = At, N rows of M (N1 rows when the rows
+// past N are filled in), V = Vt (N x N) when HASV, W = N doubles.  Element e of a region is at
+// [e * 64].  N1 == 0 leaves the rows of At as the sort left them (ComputeH21 reads only Vt).
+template <int M, int N, int N1, bool HASV>
+__device__ void hy_jacobi(float* A, float* V, double* W) {
+    const float eps = 1.1920928955078125e-7f * 10;  // FLT_EPSILON * 10
+    const double minval = 1.17549435082228750797e-38;  // FLT_MIN
+#pragma unroll 1
+    for (int i = 0; i < N; ++i) {
+        double sd = 0;
+        for (int k = 0; k < M; ++k) {
+            const float t = A[(i * M + k) * 64];
+            sd += (double)t * t;
+        }
+        W[i * 64] = sd;
+        if (HASV)
+            for (int k = 0; k < N; ++k) V[(i * N + k) * 64] = k == i ? 1.0f : 0.0f;
+    }
+#pragma unroll 1
+    for (int iter = 0; iter < 30; ++iter) {  // max(m, 30) with m <= 16
+        bool changed = false;
+#pragma unroll 1
+        for (int i = 0; i < N - 1; ++i)
+#pragma unroll 1
+            for (int j = i + 1; j < N; ++j) {
+                float* Ai = A + i * M * 64;
+                float* Aj = A + j * M * 64;
+                double a = W[i * 64], p = 0, b = W[j * 64];
+                for (int k = 0; k < M; ++k) p += (double)Ai[k * 64] * (double)Aj[k * 64];
+                if (fabs(p) <= (double)eps * __builtin_sqrt(a * b)) continue;
+                p *= 2;
+                const double beta = a - b, gamma = hy_hypot(p, beta);
+                float c, s;
+                if (beta < 0) {
+                    const double delta = (gamma - beta) * 0.5;
+                    s = (float)__builtin_sqrt(delta / gamma);
+                    c = (float)(p / (gamma * (double)s * 2));
+                } else {
+                    c = (float)__builtin_sqrt((gamma + beta) / (gamma * 2));
+                    s = (float)(p / (gamma * (double)c * 2));
+                }
+                a = b = 0;
+                for (int k = 0; k < M; ++k) {
+                    const float x = Ai[k * 64], y = Aj[k * 64];
+                    const float t0 = c * x + s * y;
+                    const float t1 = -s * x + c * y;
+                    Ai[k * 64] = t0;
+                    Aj[k * 64] = t1;
+                    a += (double)t0 * t0;
+                    b += (double)t1 * t1;
+                }
+                W[i * 64] = a;
+                W[j * 64] = b;
+                changed = true;
+                if (HASV) {
+                    float* Vi = V + i * N * 64;
+                    float* Vj = V + j * N * 64;
+                    for (int k = 0; k < N; ++k) {
+                        const float x = Vi[k * 64], y = Vj[k * 64];
+                        Vi[k * 64] = c * x + s * y;
+                        Vj[k * 64] = -s * x + c * y;
+                    }
+                }
+            }
+        if (!changed) break;
+    }
+#pragma unroll 1
+    for (int i = 0; i < N; ++i) {
+        double sd = 0;
+        for (int k = 0; k < M; ++k) {
+            const float t = A[(i * M + k) * 64];
+            sd += (double)t * t;
+        }
+        W[i * 64] = __builtin_sqrt(sd);
+    }
+    // descending selection sort, the first of equal values wins; rows of At and Vt follow
+#pragma unroll 1
+    for (int i = 0; i < N - 1; ++i) {
+        int j = i;
+        for (int k = i + 1; k < N; ++k)
+            if (W[j * 64] < W[k * 64]) j = k;
+        if (i != j) {
+            const double t = W[i * 64];
+            W[i * 64] = W[j * 64];
+            W[j * 64] = t;
+            for (int k = 0; k < M; ++k) {
+                const float x = A[(i * M + k) * 64];
+                A[(i * M + k) * 64] = A[(j * M + k) * 64];
+                A[(j * M + k) * 64] = x;
+            }
+            if (HASV)
+                for (int k = 0; k < N; ++k) {
+                    const float x = V[(i * N + k) * 64];
+                    V[(i * N + k) * 64] = V[(j * N + k) * 64];
+                    V[(j * N + k) * 64] = x;
+                }
+        }
+    }
+    if (N1 == 0) return;
+    unsigned long long state = 0x12345678ull;  // RNG rng(0x12345678), seeded per call
+#pragma unroll 1
+    for (int i = 0; i < N1; ++i) {
+        float* Ai = A + i * M * 64;
+        double sd = i < N ? W[i * 64] : 0;
+        int tries = 0;
+        while (sd <= minval && tries++ < HY_MAX_FILL_TRIES) {
+            const float val0 = (float)(1. / M);
+            for (int k = 0; k < M; ++k) {
+                state = (unsigned long long)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
+                Ai[k * 64] = ((unsigned)state & 256u) != 0 ? val0 : -val0;
+            }
+#pragma unroll 1
+            for (int it = 0; it < 2; ++it)
+#pragma unroll 1
+                for (int j = 0; j < i; ++j) {
+                    const float* Aj = A + j * M * 64;
+                    sd = 0;
+                    for (int k = 0; k < M; ++k) sd += (double)(Ai[k * 64] * Aj[k * 64]);
+                    float asum = 0;
+                    for (int k = 0; k < M; ++k) {
+                        const float t = (float)((double)Ai[k * 64] - sd * (double)Aj[k * 64]);
+                        Ai[k * 64] = t;
+                        asum += fabsf(t);
+                    }
+                    asum = asum != 0.0f ? 1.0f / asum : 0.0f;  // (a NaN sum is "true": 1/NaN)
+                    for (int k = 0; k < M; ++k) Ai[k * 64] *= asum;
+                }
+            sd = 0;
+            for (int k = 0; k < M; ++k) {
+                const float t = Ai[k * 64];
+                sd += (double)t * t;
+            }
+            sd = __builtin_sqrt(sd);
+        }
+        const float s = (float)(1 / sd);
+        for (int k = 0; k < M; ++k) Ai[k * 64] *= s;
+    }
+}
+
+struct M3 {
+    float m[9];
+};
+
+// gemm's 2 <= len <= 4 path, alpha = 1, no C: (float)((double)t * 1.0) is t
+__device__ __forceinline__ M3 hy_mul3(const M3& a, const M3& b) {
+    M3 d;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        d.m[3 * i + 0] = a.m[3 * i] * b.m[0] + a.m[3 * i + 1] * b.m[3] + a.m[3 * i + 2] * b.m[6];
+        d.m[3 * i + 1] = a.m[3 * i] * b.m[1] + a.m[3 * i + 1] * b.m[4] + a.m[3 * i + 2] * b.m[7];
+        d.m[3 * i + 2] = a.m[3 * i] * b.m[2] + a.m[3 * i + 1] * b.m[5] + a.m[3 * i + 2] * b.m[8];
+    }
+    return d;
+}
+
+// Mat::inv() of a 3x3 CV_32F: the closed form in double, zeros when det == 0
+__device__ __forceinline__ M3 hy_inv3(const M3& S) {
+#define SF(y, x) S.m[(y)*3 + (x)]
+#define DD(a, b, c, d) ((double)(a) * (double)(b) - (double)(c) * (double)(d))
+    double d = (double)SF(0, 0) * DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) -
+               (double)SF(0, 1) * DD(SF(1, 0), SF(2, 2), SF(1, 2), SF(2, 0)) +
+               (double)SF(0, 2) * DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0));
+    M3 D;
+    if (d != 0.) {
+        d = 1. / d;
+        D.m[0] = (float)(DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) * d);
+        D.m[1] = (float)(DD(SF(0, 2), SF(2, 1), SF(0, 1), SF(2, 2)) * d);
+        D.m[2] = (float)(DD(SF(0, 1), SF(1, 2), SF(0, 2), SF(1, 1)) * d);
+        D.m[3] = (float)(DD(SF(1, 2), SF(2, 0), SF(1, 0), SF(2, 2)) * d);
+        D.m[4] = (float)(DD(SF(0, 0), SF(2, 2), SF(0, 2), SF(2, 0)) * d);
+        D.m[5] = (float)(DD(SF(0, 2), SF(1, 0), SF(0, 0), SF(1, 2)) * d);
+        D.m[6] = (float)(DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0)) * d);
+        D.m[7] = (float)(DD(SF(0, 1), SF(2, 0), SF(0, 0), SF(2, 1)) * d);
+        D.m[8] = (float)(DD(SF(0, 0), SF(1, 1), SF(0, 1), SF(1, 0)) * d);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) D.m[k] = 0.0f;
+    }
+#undef DD
+#undef SF
+    return D;
+}
+
+__device__ __forceinline__ void hy_store9(float* dst, long long g, const M3& v) {
+    if (!dst) return;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dst[g * 9 + k] = v.m[k];
+}
+
+__global__ void __launch_bounds__(64) k_init_hypotheses(HypArgs a, int tiles) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int model = blockIdx.y;
+    const int p = blockIdx.x / tiles, tile = blockIdx.x - p * tiles;
+    const int lane = threadIdx.x;
+    const int h = tile * 64 + lane;
+    if (h >= a.n_hyp) return;  // (no barrier below: every lane works on its own column)
+    if (model == 0 ? (!a.H21 && !a.H12 && !a.Hn && !a.sets_out) : (!a.F21 && !a.Fn)) return;
+    float* A = (float*)smem + lane;
+    float* V = (float*)smem + HY_A * 64 + lane;
+    double* W = (double*)(smem + (HY_A + HY_V) * 64 * 4) + lane;
+    const long long g = (long long)p * a.n_hyp + h;
+    const int N = a.nmatch[p];
+    if (N < 8) {  // the reference would pop from an empty vector: nothing is generated
+        M3 z;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) z.m[k] = 0.0f;
+        if (model == 0) {
+            hy_store9(a.H21, g, z);
+            hy_store9(a.H12, g, z);
+            hy_store9(a.Hn, g, z);
+            if (a.sets_out)
+                for (int j = 0; j < 8; ++j) a.sets_out[g * 8 + j] = 0;
+        } else {
+            hy_store9(a.F21, g, z);
+            hy_store9(a.Fn, g, z);
+        }
+        return;
+    }
+    // The minimal set (Initializer.cc:80-95).  vAvailableIndices is the identity except where a
+    // removal wrote back() into the drawn position: at most 7 entries matter, kept as (position,
+    // value) in the W region, a later write to a position hiding an earlier one.
+    int* pos = (int*)W;          // [j * 128], [j * 128 + 1]: the two ints of the lane's double j
+    int* val = (int*)W + 1;
+    int* set = (int*)V;          // [j * 64]
+#pragma unroll 1
+    for (int j = 0; j < 8; ++j) {
+        int idx;
+        if (a.sets_in)
+            idx = a.sets_in[g * 8 + j];
+        else {
+            const int size = N - j;
+            const int r = max(a.rand31[g * 8 + j], 0);
+            const int randi = (int)(((long long)r * size) >> 31);  // RandomInt(0, size - 1), §15
+            idx = randi;
+            int back = size - 1;
+            for (int t = 0; t < j; ++t) {
+                if (pos[t * 128] == randi) idx = val[t * 128];
+                if (pos[t * 128] == size - 1) back = val[t * 128];
+            }
+            pos[j * 128] = randi;
+            val[j * 128] = back;
+        }
+        set[j * 64] = idx;
+        if (model == 0 && a.sets_out) a.sets_out[g * 8 + j] = idx;
+    }
+    InitArgs ia{};
+    ia.kps = a.kps;
+    ia.counts = a.counts;
+    ia.pair_f1 = a.pair_f1;
+    ia.pair_f2 = a.pair_f2;
+    ia.matches12 = a.matches12;
+    ia.cap = a.cap;
+    const PairView v = pair_view(ia, p);
+    const int32_t* ord = a.ord_i + (size_t)p * a.cap;
+    const float* n1 = a.norm + (size_t)p * 2 * HY_NORM;
+    const float* n2 = n1 + HY_NORM;
+    M3 T1, T2;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        T1.m[k] = n1[k];
+        T2.m[k] = n2[k];
+    }
+    const float m1x = n1[9], m1y = n1[10], s1x = n1[11], s1y = n1[12];
+    const float m2x = n2[9], m2y = n2[10], s2x = n2[11], s2y = n2[12];
+    // gather: vPn1[mvMatches12[idx].first], vPn2[mvMatches12[idx].second], and the rows of A
+    int sidx[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sidx[j] = set[j * 64];  // (V is written below)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int i = ord[sidx[j]];
+        const int m = v.m12[i];
+        const float u1 = (v.k1[i].x - m1x) * s1x, v1 = (v.k1[i].y - m1y) * s1y;
+        const float u2 = (v.k2[m].x - m2x) * s2x, v2 = (v.k2[m].y - m2y) * s2y;
+        if (model == 0) {
+            // ComputeH21: A is 16 x 9, rows < cols is false, so At = A^T, 9 rows of 16
+            const float r0[9] = {0.0f, 0.0f, 0.0f, -u1, -v1, -1.0f, v2 * u1, v2 * v1, v2};
+            const float r1[9] = {u1, v1, 1.0f, 0.0f, 0.0f, 0.0f, -u2 * u1, -u2 * v1, -u2};
+#pragma unroll
+            for (int c = 0; c < 9; ++c) {
+                A[(c * 16 + 2 * j) * 64] = r0[c];
+                A[(c * 16 + 2 * j + 1) * 64] = r1[c];
+            }
+        } else {
+            // ComputeF21: A is 8 x 9 and is worked on as it is; row 8 of the 9 x 9 starts as zeros
+            const float r[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.0f};
+#pragma unroll
+            for (int c = 0; c < 9; ++c) A[(j * 9 + c) * 64] = r[c];
+        }
+    }
+    if (model == 0) {
+        hy_jacobi<16, 9, 0, true>(A, V, W);
+        M3 Hn;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Hn.m[k] = V[(8 * 9 + k) * 64];  // vt.row(8)
+        const M3 H21 = hy_mul3(hy_mul3(hy_inv3(T2), Hn), T1);       // T2inv*Hn*T1
+        hy_store9(a.Hn, g, Hn);
+        hy_store9(a.H21, g, H21);
+        hy_store9(a.H12, g, hy_inv3(H21));
+    } else {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) A[(8 * 9 + c) * 64] = 0.0f;
+        hy_jacobi<9, 8, 9, false>(A, nullptr, W);
+        // Fpre = vt.row(8), the filled-in row; its decomposition takes the transpose path
+        float* A3 = V;
+        float* V3 = V + 9 * 64;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) A3[(i * 3 + k) * 64] = A[(8 * 9 + k * 3 + i) * 64];
+        hy_jacobi<3, 3, 3, true>(A3, V3, W);
+        M3 u, vt, D;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                u.m[r * 3 + c] = A3[(c * 3 + r) * 64];
+                vt.m[r * 3 + c] = V3[(r * 3 + c) * 64];
+                D.m[r * 3 + c] = 0.0f;
+            }
+        D.m[0] = (float)W[0];
+        D.m[4] = (float)W[64];  // w[2] = 0
+        const M3 Fn = hy_mul3(hy_mul3(u, D), vt);
+        M3 T2t;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) T2t.m[r * 3 + c] = T2.m[c * 3 + r];
+        hy_store9(a.Fn, g, Fn);
+        hy_store9(a.F21, g, hy_mul3(hy_mul3(T2t, Fn), T1));  // T2t*Fn*T1
+    }
+}
+
+struct ResultArgs {
+    const float* H21;
+    const float* F21;
+    const int32_t* best[2];
+    const float* best_score[2];
+    float* best_H21;
+    float* best_F21;
+    float* RH;
+    int32_t* use_h;
+    int P, n_hyp;
+};
+
+__global__ void __launch_bounds__(64) k_init_result(ResultArgs a) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= a.P) return;
+    const float nan = __builtin_nanf("");
+    const int bh = a.best[0][p], bf = a.best[1][p];
+    if (a.best_H21)
+        for (int k = 0; k < 9; ++k) a.best_H21[(size_t)p * 9 + k] = bh >= 0 ? a.H21[((size_t)p * a.n_hyp + bh) * 9 + k] : nan;
+    if (a.best_F21)
+        for (int k = 0; k < 9; ++k) a.best_F21[(size_t)p * 9 + k] = bf >= 0 ? a.F21[((size_t)p * a.n_hyp + bf) * 9 + k] : nan;
+    const float SH = a.best_score[0][p], SF = a.best_score[1][p];
+    const float RH = SH / (SH + SF);  // Initializer.cc:110
+    if (a.RH) a.RH[p] = RH;
+    if (a.use_h) a.use_h[p] = (double)RH > 0.40 ? 1 : 0;  // Initializer.cc:113: a float against the double 0.40
+}
+
+// What one chain call holds in scratch at most (every optional output absent).
+size_t chain_scratch_bytes(int P, int cap, int n_hyp) {
+    const size_t hyp = orb_align256((size_t)P * n_hyp * 9 * 4);
+    return orb_align256((size_t)P * cap * 4) + orb_align256((size_t)P * 4) + orb_align256((size_t)P * 2 * HY_NORM * 4) +
+           3 * hyp + 2 * orb_align256((size_t)P * n_hyp * 4) + 4 * orb_align256((size_t)P * 4);
+}
+
+struct ChainOut {
+    float *H21, *H12, *F21, *Hn, *Fn, *norm;
+    int32_t* sets_out;
+    float *scores_h, *scores_f;
+    int32_t* best_h;
+    float* best_score_h;
+    uint8_t* inliers_h;
+    int32_t* best_f;
+    float* best_score_f;
+    uint8_t* inliers_f;
+    int32_t* n_matches;
+    float *best_H21, *best_F21, *RH;
+    int32_t* use_h;
+};
+
+// normalise -> hypotheses -> (when `score`) k_init_scores, k_init_best, k_init_result, enqueued on
+// `st`.  `scratch`: chain_scratch_bytes() of device memory, or NULL for a stream-ordered allocation
+// freed after the last kernel.
+int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
+              const int32_t* d_pair_f2, const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
+              const int32_t* d_sets, bool score, const ChainOut& o, uint8_t* scratch, hipStream_t st) {
+    void* owned = nullptr;
+    if (!scratch) {
+        hipError_t e = hipMallocAsync(&owned, chain_scratch_bytes(P, cap, n_hyp), st);
+        if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("initializer: scratch: ") + hipGetErrorString(e));
+        scratch = (uint8_t*)owned;
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* r = scratch + off;
+        off += orb_align256(bytes);
+        return r;
+    };
+    const size_t hyp = (size_t)P * n_hyp * 9 * 4;
+    HypArgs h{};
+    h.kps = d_kps;
+    h.counts = d_counts;
+    h.pair_f1 = d_pair_f1;
+    h.pair_f2 = d_pair_f2;
+    h.matches12 = d_matches12;
+    h.rand31 = d_rand31;
+    h.sets_in = d_sets;
+    h.ord_i = (int32_t*)take((size_t)P * cap * 4);
+    h.nmatch = o.n_matches ? o.n_matches : (int32_t*)take((size_t)P * 4);
+    h.norm = o.norm ? o.norm : (float*)take((size_t)P * 2 * HY_NORM * 4);
+    h.H21 = o.H21 ? o.H21 : score ? (float*)take(hyp) : nullptr;
+    h.H12 = o.H12 ? o.H12 : score ? (float*)take(hyp) : nullptr;
+    h.F21 = o.F21 ? o.F21 : score ? (float*)take(hyp) : nullptr;
+    h.Hn = o.Hn;
+    h.Fn = o.Fn;
+    h.sets_out = o.sets_out;
+    h.cap = cap;
+    h.P = P;
+    h.n_hyp = n_hyp;
+    int r = ORB_OK;
+    hipError_t e = hipSuccess;
+    const int tiles = (n_hyp + 63) / 64;
+    hipLaunchKernelGGL(k_init_normalize, dim3(P, 2), dim3(NORM_THREADS), 0, st, h);
+    if ((e = hipGetLastError()) == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_init_hypotheses, hipFuncAttributeMaxDynamicSharedMemorySize, HY_LDS);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_init_hypotheses, dim3((unsigned)((size_t)P * tiles), 2), dim3(64), HY_LDS, st, h, tiles);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && score) {
+        InitArgs a{};
+        a.kps = d_kps;
+        a.counts = d_counts;
+        a.pair_f1 = d_pair_f1;
+        a.pair_f2 = d_pair_f2;
+        a.matches12 = d_matches12;
+        a.M21[0] = h.H21;
+        a.M21[1] = h.F21;
+        a.H12 = h.H12;
+        a.scores[0] = o.scores_h ? o.scores_h : (float*)take((size_t)P * n_hyp * 4);
+        a.scores[1] = o.scores_f ? o.scores_f : (float*)take((size_t)P * n_hyp * 4);
+        a.best[0] = o.best_h ? o.best_h : (int32_t*)take((size_t)P * 4);
+        a.best[1] = o.best_f ? o.best_f : (int32_t*)take((size_t)P * 4);
+        a.best_score[0] = o.best_score_h ? o.best_score_h : (float*)take((size_t)P * 4);
+        a.best_score[1] = o.best_score_f ? o.best_score_f : (float*)take((size_t)P * 4);
+        a.inliers[0] = o.inliers_h;
+        a.inliers[1] = o.inliers_f;
+        a.n_matches = o.n_matches;
+        a.cap = cap;
+        a.P = P;
+        a.n_hyp = n_hyp;
+        a.inv_sigma2 = 1.0f / (sigma * sigma);  // Initializer.cc:333, 409
+        r = launch(a, st);
+        if (r == ORB_OK && (o.best_H21 || o.best_F21 || o.RH || o.use_h)) {
+            ResultArgs ra{h.H21, h.F21, {a.best[0], a.best[1]}, {a.best_score[0], a.best_score[1]},
+                          o.best_H21, o.best_F21, o.RH, o.use_h, P, n_hyp};
+            hipLaunchKernelGGL(k_init_result, dim3((P + 63) / 64), dim3(64), 0, st, ra);
+            e = hipGetLastError();
+        }
+    }
+    if (owned) (void)hipFreeAsync(owned, st);
+    if (r) return r;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("initializer: ") + hipGetErrorString(e));
+    return ORB_OK;
+}
+
+// The host forms: the pair as a 2-frame batch with one pair (0, 1), staged like orb_initializer_check.
+struct HostOut {
+    float *H21, *H12, *F21, *Hn, *Fn, *T1, *T2;
+    int32_t* sets_out;
+    float *scores_h, *scores_f;
+    int32_t* best_h;
+    float* best_score_h;
+    uint8_t* inliers_h;
+    int32_t* best_f;
+    float* best_score_f;
+    uint8_t* inliers_f;
+    float *best_H21, *best_F21, *RH;
+    int32_t* use_h;
+    int* n_matches;
+};
+
+int host_run(const char* who, const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+             const int32_t* matches12, float sigma, int n_hyp, const int32_t* sets, const int32_t* rand31, bool score,
+             const HostOut& o, int device) {
+    const std::string w = std::string(who) + ": ";
+    if (n1 < 0 || n2 < 0 || (n1 && (!kps1 || !matches12)) || (n2 && !kps2)) return fail(ORB_EINVAL, w + "bad arguments");
+    if ((sets == nullptr) == (rand31 == nullptr)) return fail(ORB_EINVAL, w + "exactly one of sets and rand31 is given");
+    const int cap = std::max(std::max(n1, n2), 1);
+    if (cap > IN_MAX_CAP) return fail(ORB_ENOTSUP, w + "more than 8192 keypoints per frame");
+    if (n_hyp < 1 || n_hyp > IN_MAX_HYP)
+        return fail(ORB_EINVAL, w + "n_hyp must be in [1, 1024] (got " + std::to_string(n_hyp) + ")");
+    int N = 0;
+    for (int i = 0; i < n1; ++i) {
+        if (matches12[i] < -1 || matches12[i] >= n2)
+            return fail(ORB_EINVAL, w + "matches12[" + std::to_string(i) + "] = " + std::to_string(matches12[i]) +
+                                        " is outside [-1, n2)");
+        N += matches12[i] >= 0;
+    }
+    for (int k = 0; k < n_hyp * 8; ++k) {
+        if (rand31 && rand31[k] < 0)
+            return fail(ORB_EINVAL, w + "rand31[" + std::to_string(k) + "] = " + std::to_string(rand31[k]) + " is negative");
+        if (sets && N >= 8 && (sets[k] < 0 || sets[k] >= N))
+            return fail(ORB_EINVAL, w + "sets[" + std::to_string(k) + "] = " + std::to_string(sets[k]) +
+                                        " is outside [0, N = " + std::to_string(N) + ")");
+    }
+    int ndev = 0;
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
+    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
+    ORB_HIPCHK(hipSetDevice(device));
+    // in:  [kps 2 x cap | counts 2, f1, f2 | matches12 cap | draws n_hyp x 8]
+    // out: [H21 H12 F21 Hn Fn | sets | norm | scores 2 | best 2, best_score 2, n, RH, use_h | best_H21 best_F21 |
+    //       inliers 2 x cap]      then the chain's scratch (device only)
+    auto al = orb_align256;
+    const size_t hyp = al((size_t)n_hyp * 9 * 4);
+    const size_t oK = 0, oC = al(oK + 2 * (size_t)cap * sizeof(orb_keypoint_t)), oM = al(oC + 16),
+                 oD = al(oM + (size_t)cap * 4), in_end = al(oD + (size_t)n_hyp * 32);
+    const size_t oH = in_end, oSet = oH + 5 * hyp, oN = al(oSet + (size_t)n_hyp * 32), oS = al(oN + 2 * HY_NORM * 4),
+                 oB = al(oS + 2 * (size_t)n_hyp * 4), oBH = al(oB + 28), oI = al(oBH + 72),
+                 out_end = al(oI + 2 * (size_t)cap);
+    if (int r = C->reserve(out_end + chain_scratch_bytes(1, cap, n_hyp), out_end)) return r;
+    uint8_t* hp = C->pinned;
+    std::memset(hp, 0, in_end);
+    if (n1) std::memcpy(hp + oK, kps1, (size_t)n1 * sizeof(orb_keypoint_t));
+    if (n2) std::memcpy(hp + oK + (size_t)cap * sizeof(orb_keypoint_t), kps2, (size_t)n2 * sizeof(orb_keypoint_t));
+    const int32_t hdr[4] = {n1, n2, 0, 1};
+    std::memcpy(hp + oC, hdr, 16);
+    int32_t* hm = (int32_t*)(hp + oM);
+    for (int i = 0; i < cap; ++i) hm[i] = i < n1 ? matches12[i] : -1;
+    std::memcpy(hp + oD, sets ? sets : rand31, (size_t)n_hyp * 32);
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    uint8_t* d = C->buf;
+    ChainOut co{};
+    co.H21 = (float*)(d + oH);
+    co.H12 = (float*)(d + oH + hyp);
+    co.F21 = (float*)(d + oH + 2 * hyp);
+    co.Hn = (float*)(d + oH + 3 * hyp);
+    co.Fn = (float*)(d + oH + 4 * hyp);
+    co.sets_out = (int32_t*)(d + oSet);
+    co.norm = (float*)(d + oN);
+    co.n_matches = (int32_t*)(d + oB + 16);
+    if (score) {
+        co.scores_h = (float*)(d + oS);
+        co.scores_f = co.scores_h + n_hyp;
+        co.best_h = (int32_t*)(d + oB);
+        co.best_f = co.best_h + 1;
+        co.best_score_h = (float*)(d + oB + 8);
+        co.best_score_f = co.best_score_h + 1;
+        co.RH = (float*)(d + oB + 20);
+        co.use_h = (int32_t*)(d + oB + 24);
+        co.best_H21 = (float*)(d + oBH);
+        co.best_F21 = co.best_H21 + 9;
+        co.inliers_h = d + oI;
+        co.inliers_f = d + oI + cap;
+    }
+    const int32_t* dc = (const int32_t*)(d + oC);
+    const int32_t* dd = (const int32_t*)(d + oD);
+    const int r = run_chain((const orb_keypoint_t*)(d + oK), dc, cap, 1, dc + 2, dc + 3, (const int32_t*)(d + oM), sigma,
+                            n_hyp, rand31 ? dd : nullptr, sets ? dd : nullptr, score, co, d + out_end, C->stream);
+    hipError_t e = hipSuccess;
+    if (r == ORB_OK) e = hipMemcpyAsync(hp + oH, d + oH, out_end - oH, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
+    if (r) return r;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, w + hipGetErrorString(e));
+    const size_t hb = (size_t)n_hyp * 9 * 4;
+    float* const ho[5] = {o.H21, o.H12, o.F21, o.Hn, o.Fn};
+    for (int k = 0; k < 5; ++k)
+        if (ho[k]) std::memcpy(ho[k], hp + oH + k * hyp, hb);
+    if (o.sets_out) std::memcpy(o.sets_out, hp + oSet, (size_t)n_hyp * 32);
+    if (o.T1) std::memcpy(o.T1, hp + oN, 36);
+    if (o.T2) std::memcpy(o.T2, hp + oN + HY_NORM * 4, 36);
+    int32_t nm;
+    std::memcpy(&nm, hp + oB + 16, 4);
+    if (o.n_matches) *o.n_matches = nm;
+    if (!score) return ORB_OK;
+    const float* hs = (const float*)(hp + oS);
+    const int32_t* bi = (const int32_t*)(hp + oB);
+    const float* bs = (const float*)(hp + oB + 8);
+    if (o.scores_h) std::memcpy(o.scores_h, hs, (size_t)n_hyp * 4);
+    if (o.scores_f) std::memcpy(o.scores_f, hs + n_hyp, (size_t)n_hyp * 4);
+    if (o.best_h) *o.best_h = bi[0];
+    if (o.best_f) *o.best_f = bi[1];
+    if (o.best_score_h) *o.best_score_h = bs[0];
+    if (o.best_score_f) *o.best_score_f = bs[1];
+    if (o.inliers_h && nm) std::memcpy(o.inliers_h, hp + oI, (size_t)nm);
+    if (o.inliers_f && nm) std::memcpy(o.inliers_f, hp + oI + cap, (size_t)nm);
+    if (o.RH) std::memcpy(o.RH, hp + oB + 20, 4);
+    if (o.use_h) std::memcpy(o.use_h, hp + oB + 24, 4);
+    if (o.best_H21) std::memcpy(o.best_H21, hp + oBH, 36);
+    if (o.best_F21) std::memcpy(o.best_F21, hp + oBH + 36, 36);
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orb_initializer_compute_hypotheses(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                                       const int32_t* matches12, int n_hyp, const int32_t* sets, const int32_t* rand31,
+                                       float* H21, float* H12, float* F21, float* Hn, float* Fn, float* T1, float* T2,
+                                       int32_t* sets_out, int* n_matches, int device) {
+    HostOut o{};
+    o.H21 = H21;
+    o.H12 = H12;
+    o.F21 = F21;
+    o.Hn = Hn;
+    o.Fn = Fn;
+    o.T1 = T1;
+    o.T2 = T2;
+    o.sets_out = sets_out;
+    o.n_matches = n_matches;
+    return host_run("initializer hypotheses", kps1, n1, kps2, n2, matches12, 1.0f, n_hyp, sets, rand31, false, o, device);
+}
+
+int orb_initializer_ransac(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                           const int32_t* matches12, float sigma, int n_hyp, const int32_t* rand31, float* H21,
+                           float* H12, float* F21, int32_t* sets_out, float* scores_h, float* scores_f, int32_t* best_h,
+                           float* best_score_h, uint8_t* inliers_h, int32_t* best_f, float* best_score_f,
+                           uint8_t* inliers_f, float* best_H21, float* best_F21, float* RH, int32_t* use_h,
+                           int* n_matches, int device) {
+    HostOut o{};
+    o.H21 = H21;
+    o.H12 = H12;
+    o.F21 = F21;
+    o.sets_out = sets_out;
+    o.scores_h = scores_h;
+    o.scores_f = scores_f;
+    o.best_h = best_h;
+    o.best_score_h = best_score_h;
+    o.inliers_h = inliers_h;
+    o.best_f = best_f;
+    o.best_score_f = best_score_f;
+    o.inliers_f = inliers_f;
+    o.best_H21 = best_H21;
+    o.best_F21 = best_F21;
+    o.RH = RH;
+    o.use_h = use_h;
+    o.n_matches = n_matches;
+    if (!rand31) return fail(ORB_EINVAL, "initializer ransac: rand31 is NULL");
+    return host_run("initializer ransac", kps1, n1, kps2, n2, matches12, sigma, n_hyp, nullptr, rand31, true, o, device);
+}
+
+int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                        const int32_t* d_pair_f1, const int32_t* d_pair_f2,
+                                        const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
+                                        float* d_H21, float* d_H12, float* d_F21, int32_t* d_sets_out,
+                                        float* d_scores_h, float* d_scores_f, int32_t* d_best_h, float* d_best_score_h,
+                                        uint8_t* d_inliers_h, int32_t* d_best_f, float* d_best_score_f,
+                                        uint8_t* d_inliers_f, int32_t* d_n_matches, float* d_best_H21,
+                                        float* d_best_F21, float* d_RH, int32_t* d_use_h, void* stream) {
+    if (P < 0 || cap <= 0) return fail(ORB_EINVAL, "initializer ransac: bad arguments");
+    if (int r = check_limits(cap, n_hyp, true, true)) return r;
+    if (P == 0) return ORB_OK;
+    if (P > 65535) return fail(ORB_ENOTSUP, "initializer ransac: more than 65535 pairs per call");
+    if (!d_kps || !d_counts || !d_pair_f1 || !d_pair_f2 || !d_matches12 || !d_rand31)
+        return fail(ORB_EINVAL, "initializer ransac: bad arguments");
+    ChainOut o{};
+    o.H21 = d_H21;
+    o.H12 = d_H12;
+    o.F21 = d_F21;
+    o.sets_out = d_sets_out;
+    o.scores_h = d_scores_h;
+    o.scores_f = d_scores_f;
+    o.best_h = d_best_h;
+    o.best_score_h = d_best_score_h;
+    o.inliers_h = d_inliers_h;
+    o.best_f = d_best_f;
+    o.best_score_f = d_best_score_f;
+    o.inliers_f = d_inliers_f;
+    o.n_matches = d_n_matches;
+    o.best_H21 = d_best_H21;
+    o.best_F21 = d_best_F21;
+    o.RH = d_RH;
+    o.use_h = d_use_h;
+    return run_chain(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, sigma, n_hyp, d_rand31, nullptr, true, o,
+                     nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,9 @@ of ``include/orb_abi.h`` (csrc/orb_initializer.hip).
 ``CheckHomography`` / ``CheckFundamental`` for all RANSAC hypotheses of a frame pair in one call,
 with the "keep the best" rule of ``FindHomography`` / ``FindFundamental``.  The hypotheses
 (``ComputeH21`` / ``ComputeF21``, ``Normalize``, the ``T2inv*Hn*T1`` / ``inv()`` products) are the
-caller's: arrays of shape (n_hyp, 3, 3) or (n_hyp, 9), float32, row-major.
+caller's in ``Initializer``: arrays of shape (n_hyp, 3, 3) or (n_hyp, 9), float32, row-major.
+``InitializerRansac`` generates them on the device from the caller's rand() values and scores them
+in the same call.
 """
 from __future__ import annotations
 
@@ -122,4 +124,132 @@ class Initializer:
             ptr(hyp[0]), ptr(hyp[1]), ptr(hyp[2]), o["scores_h"], o["scores_f"], o["best_h"], o["best_score_h"],
             o["inliers_h"], o["best_f"], o["best_score_f"], o["inliers_f"], ptr(out["n_matches"]),
             ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+
+def initializer_minimal_sets(N: int, rand31) -> np.ndarray:
+    """The minimal sets of Initializer::Initialize (Initializer.cc:80-95) for N matches: rand31
+    holds n_hyp x 8 values that rand() returned; draw j of a set is RandomInt(0, N - j - 1) =
+    (r * (N - j)) >> 31 on a list that loses the drawn *position* (the last entry moves into it), so
+    a set never repeats an index.  Returns (n_hyp, 8) int32 match ordinals."""
+    r = np.asarray(rand31, np.int64).reshape(-1, 8)
+    if N < 8:
+        raise ValueError("fewer than 8 matches: the reference would pop from an empty vector")
+    if (r < 0).any() or (r >= 1 << 31).any():
+        raise ValueError("rand31 values lie in [0, 2^31)")
+    sets = np.zeros(r.shape, np.int32)
+    for it in range(len(r)):
+        avail = list(range(N))
+        for j in range(8):
+            randi = (int(r[it, j]) * len(avail)) >> 31
+            sets[it, j] = avail[randi]
+            avail[randi] = avail[-1]
+            avail.pop()
+    return sets
+
+
+class InitializerRansac(Initializer):
+    """Initializer::Initialize up to the ReconstructH / ReconstructF call (Initializer.cc:44-113) on
+    the GPU: the minimal sets from the caller's rand() values, Normalize, ComputeH21 / ComputeF21
+    (cv::SVDecomp as OpenCV 2.4's Jacobi SVD is read, DESIGN.md §16) and both checks.  The package
+    owns no random generator: every call takes `rand31`, (n_hyp, 8) values that rand() returned."""
+
+    def _pair(self, F1, F2, matches12):
+        k1, k2 = _keys(F1), _keys(F2)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        if len(m12) != len(k1):
+            raise ValueError(f"matches12 holds {len(m12)} entries for {len(k1)} keypoints")
+        return k1, k2, m12
+
+    def compute_hypotheses(self, F1, F2, matches12, rand31=None, sets=None) -> dict:
+        """ComputeH21 / ComputeF21 of every iteration (host buffers, synchronous) from `rand31` or
+        from given `sets` ((n_hyp, 8) match ordinals).  Returns n_matches, sets (n_hyp, 8) int32,
+        H21, H12, F21 (what check() takes), Hn, Fn (n_hyp, 9) float32 and T1, T2 (3, 3).  With
+        fewer than 8 matches the hypothesis and set rows are zeros."""
+        k1, k2, m12 = self._pair(F1, F2, matches12)
+        if (rand31 is None) == (sets is None):
+            raise ValueError("exactly one of rand31 and sets is given")
+        draws = np.ascontiguousarray(rand31 if sets is None else sets, np.int32).reshape(-1, 8)
+        n_hyp = len(draws)
+        hyp = {k: np.zeros((max(n_hyp, 1), 9), np.float32) for k in ("H21", "H12", "F21", "Hn", "Fn")}
+        T = np.zeros((2, 9), np.float32)
+        so = np.zeros((max(n_hyp, 1), 8), np.int32)
+        nm = ctypes.c_int(0)
+        check(self._lib.orb_initializer_compute_hypotheses(
+            ptr(k1), len(k1), ptr(k2), len(k2), ptr(m12), n_hyp, ptr(draws if sets is not None else None),
+            ptr(draws if sets is None else None), ptr(hyp["H21"]), ptr(hyp["H12"]), ptr(hyp["F21"]), ptr(hyp["Hn"]),
+            ptr(hyp["Fn"]), ptr(T[0]), ptr(T[1]), ptr(so), ctypes.byref(nm), self.device))
+        out = {k: v[:n_hyp] for k, v in hyp.items()}
+        out.update(n_matches=nm.value, sets=so[:n_hyp], T1=T[0].reshape(3, 3), T2=T[1].reshape(3, 3))
+        return out
+
+    def find(self, F1, F2, matches12, rand31) -> dict:
+        """One Initialize up to RH (host buffers, synchronous).  Returns what check() returns for
+        the generated hypotheses, plus sets, H21, H12, F21, H / F (3, 3) float32 (the winners, NaN
+        when the best index is -1), RH (float32) and use_h (RH > 0.40: ReconstructH would be
+        tried)."""
+        k1, k2, m12 = self._pair(F1, F2, matches12)
+        draws = np.ascontiguousarray(rand31, np.int32).reshape(-1, 8)
+        n_hyp, n1 = len(draws), len(k1)
+        hyp = {k: np.zeros((max(n_hyp, 1), 9), np.float32) for k in ("H21", "H12", "F21")}
+        so = np.zeros((max(n_hyp, 1), 8), np.int32)
+        sc = np.zeros((2, max(n_hyp, 1)), np.float32)
+        best = np.full(2, -1, np.int32)
+        bs = np.zeros(2, np.float32)
+        inl = np.zeros((2, max(n1, 1)), np.uint8)
+        bm = np.zeros((2, 9), np.float32)
+        rh = np.zeros(1, np.float32)
+        use = np.zeros(1, np.int32)
+        nm = ctypes.c_int(0)
+        check(self._lib.orb_initializer_ransac(
+            ptr(k1), n1, ptr(k2), len(k2), ptr(m12), self.mSigma, n_hyp, ptr(draws), ptr(hyp["H21"]), ptr(hyp["H12"]),
+            ptr(hyp["F21"]), ptr(so), ptr(sc[0]), ptr(sc[1]), ptr(best[0:]), ptr(bs[0:]), ptr(inl[0]), ptr(best[1:]),
+            ptr(bs[1:]), ptr(inl[1]), ptr(bm[0]), ptr(bm[1]), ptr(rh), ptr(use), ctypes.byref(nm), self.device))
+        n = nm.value
+        out = {k: v[:n_hyp] for k, v in hyp.items()}
+        out.update(n_matches=n, sets=so[:n_hyp], scores_h=sc[0, :n_hyp].copy(), scores_f=sc[1, :n_hyp].copy(),
+                   best_h=int(best[0]), best_f=int(best[1]), best_score_h=np.float32(bs[0]),
+                   best_score_f=np.float32(bs[1]), inliers_h=inl[0, :n].astype(bool), inliers_f=inl[1, :n].astype(bool),
+                   H=bm[0].reshape(3, 3), F=bm[1].reshape(3, 3), RH=np.float32(rh[0]), use_h=bool(use[0]))
+        return out
+
+    def find_batch_device(self, d_kps, d_counts, pair_f1, pair_f2, d_matches12, d_rand31, stream=None,
+                          hypotheses=True) -> dict:
+        """P pairs on device-resident extractor and matcher output (orb_initializer_ransac_batch_device):
+        the arguments of check_batch_device with d_rand31 (P, n_hyp, 8) int32 (a negative value
+        counts as 0) in place of the hypotheses.  Returns the device tensors of check_batch_device
+        plus best_H21 / best_F21 (P, 9), RH (P,) float32, use_h (P,) int32 and, when `hypotheses`,
+        H21 / H12 / F21 (P, n_hyp, 9) and sets (P, n_hyp, 8).  Asynchronous on `stream`."""
+        import torch
+
+        P, cap = int(d_matches12.shape[0]), int(d_kps.shape[1])
+        if int(d_matches12.shape[1]) != cap:
+            raise ValueError("d_matches12 must be (P, cap)")
+        if d_rand31.dtype != torch.int32 or d_rand31.dim() != 3 or int(d_rand31.shape[0]) != P or int(d_rand31.shape[2]) != 8:
+            raise ValueError("d_rand31 must be an int32 tensor (P, n_hyp, 8)")
+        d_rand31 = d_rand31.contiguous()
+        n_hyp = int(d_rand31.shape[1])
+        dev = d_kps.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):  # the zero fills are ordered before the kernels
+            out = {"n_matches": torch.zeros((P,), dtype=torch.int32, device=dev)}
+            for t in "hf":
+                out["scores_" + t] = torch.empty((P, n_hyp), dtype=torch.float32, device=dev)
+                out["best_" + t] = torch.empty((P,), dtype=torch.int32, device=dev)
+                out["best_score_" + t] = torch.empty((P,), dtype=torch.float32, device=dev)
+                out["inliers_" + t] = torch.zeros((P, cap), dtype=torch.uint8, device=dev)
+            out["best_H21"] = torch.empty((P, 9), dtype=torch.float32, device=dev)
+            out["best_F21"] = torch.empty((P, 9), dtype=torch.float32, device=dev)
+            out["RH"] = torch.empty((P,), dtype=torch.float32, device=dev)
+            out["use_h"] = torch.empty((P,), dtype=torch.int32, device=dev)
+            if hypotheses:
+                for k in ("H21", "H12", "F21"):
+                    out[k] = torch.empty((P, n_hyp, 9), dtype=torch.float32, device=dev)
+                out["sets"] = torch.empty((P, n_hyp, 8), dtype=torch.int32, device=dev)
+        g = lambda k: ptr(out.get(k))  # noqa: E731
+        check(self._lib.orb_initializer_ransac_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, P, ptr(pair_f1), ptr(pair_f2), ptr(d_matches12), self.mSigma, n_hyp,
+            ptr(d_rand31), g("H21"), g("H12"), g("F21"), g("sets"), g("scores_h"), g("scores_f"), g("best_h"),
+            g("best_score_h"), g("inliers_h"), g("best_f"), g("best_score_f"), g("inliers_f"), g("n_matches"),
+            g("best_H21"), g("best_F21"), g("RH"), g("use_h"), ctypes.c_void_p(s.cuda_stream)))
         return out
