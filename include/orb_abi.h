@@ -667,10 +667,10 @@ int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32
 /* PnPsolver::CheckInliers (reference src/PnPsolver.cc:280-311) and Sim3Solver::CheckInliers
  * (src/Sim3Solver.cc:335-359) for all RANSAC hypotheses of a solver at once, with the
  * per-correspondence set-up of the two constructors and the keep-the-best rule of the two
- * iterate() loops.  In these four entry points the hypotheses are the caller's.  For PnP, EPnP
- * compute_pose (cvSVD) and Refine's pose stay on the host, as do the random minimal sets and the
- * iteration counters; for Sim3, computeT and the minimal sets run on the device in the
- * orb_sim3_ransac entry points below.  Counts and masks are the reference's bit for bit: a NaN
+ * iterate() loops.  In these four entry points the hypotheses are the caller's; the minimal sets
+ * and the hypotheses themselves (PnP: EPnP's compute_pose and Refine; Sim3: computeT) run on the
+ * device in the orb_pnp_ransac / orb_sim3_ransac entry points below.  The iteration counters and the
+ * random generator stay with the caller.  Counts and masks are the reference's bit for bit: a NaN
  * error is an outlier, a point behind the camera is not excluded.
  * Correspondence i of hypothesis h is bit i % 64 of word i / 64 of the h-th mask row (W words per
  * row); bits past n are zero.
@@ -793,6 +793,69 @@ int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_c
                                  int32_t* d_index, int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
                                  int32_t* d_first_accept, float* d_T12, float* d_T21, float* d_sim3,
                                  int32_t* d_sets_out, float* d_accepted, uint64_t* d_accepted_mask, void* stream);
+
+/* ---- PnPsolver: the hypotheses and the whole RANSAC (GPU: csrc/orb_solvers.hip) */
+/* The minimal sets of PnPsolver::iterate (PnPsolver.cc:160-173), EPnP's compute_pose (449-497 with its
+ * helpers, 347-922) and Refine (232-277), restated in double with the reference build's fused
+ * operations and OpenCV 2.4's cvMulTransposed / cvSVD / cvInvert / cvSolve as DESIGN.md §17 reads them.
+ * Nothing is repaired: coplanar or repeated points, a singular matrix, a zero beta and NaN flow on
+ * (every loop is bounded; a NaN pose scores 0 inliers).  The one exception: gauss_newton's x starts
+ * as zeros, where the reference reads it uninitialised when qr_solve returns early on its first call.
+ * Draws: either `sets`, n_hyp x 4 indices into the n correspondences, or `rand31`, n_hyp x 4 values
+ * as rand() returned them, mapped as for Sim3 above (the drawn value, not the position, is
+ * overwritten, so a set may hold a correspondence twice).  The package owns no random generator.
+ *
+ * compute_pose on minimal sets alone, host buffers, synchronous.  p3d n x 3, p2d n x 2; fu, fv, uc, vc
+ * the calibration.  Outputs, each may be NULL: R n_hyp x 9 and t n_hyp x 3 doubles (mRi, mti),
+ * rep_error n_hyp doubles (compute_pose's return value), sets_out n_hyp x 4.  ORB_EINVAL: both or
+ * neither of sets / rand31, a set index outside [0, n), a rand31 value outside [0, 2^31), n < 1, or
+ * n < 4 with rand31. */
+int orb_pnp_compute_hypotheses(int n, const float* p3d, const float* p2d, double fu, double fv, double uc, double vc,
+                               int n_hyp, const int32_t* sets, const int32_t* rand31, double* R, double* t,
+                               double* rep_error, int32_t* sets_out, int device);
+/* compute_pose on the n_sel correspondences sel[0 .. n_sel) in that order (what Refine computes on
+ * the set bits of a mask): R 9, t 3 doubles, *rep_error; each may be NULL.  1 <= n_sel <= 8192, every
+ * sel[k] in [0, n) (ORB_EINVAL). */
+int orb_pnp_compute_pose_n(int n, const float* p3d, const float* p2d, double fu, double fv, double uc, double vc,
+                           int n_sel, const int32_t* sel, double* R, double* t, double* rep_error, int device);
+/* One PnPsolver::iterate over n_hyp iterations, host buffers, synchronous: the arguments and outputs
+ * of orb_pnp_check_inliers with the draws in place of R / t, which are generated, scored and selected
+ * in one stream-ordered chain; then Refine at the iterations that replaced the best (best_at[h] == h:
+ * the only ones with a mask not yet refined), its pose scored over all n, and the result of the call.
+ * iterate's loop runs while mnIterations < mRansacMaxIts OR nCurrentIterations < nIterations
+ * (PnPsolver.cc:154): n_hyp is the caller's max(mRansacMaxIts - mnIterations, nIterations).
+ * Further outputs, each may be NULL: R, t, sets_out as above; refined_counts n_hyp (mnRefinedInliers at
+ * the replacing iterations, -1 elsewhere); *first_refined = the first replacing iteration whose
+ * refined count is > min_inliers (where iterate returns, having consumed first_refined + 1 sets of
+ * draws), or -1; pose 12 floats (Rcw row-major then tcw, double narrowed to float: the input pose of
+ * orb_pose_optimization_batch_device), pose_mask W words and *pose_inliers: mRefinedTcw,
+ * mvbRefinedInliers, mnRefinedInliers of iteration first_refined, else mBestTcw, mvbBestInliers,
+ * mnBestInliers of best_at[n_hyp - 1] when there is a best, else NaN, zeros and 0.  When the best is
+ * still the earlier calls' (best_at[n_hyp - 1] == -2) the pose is NaN, the mask zeros and
+ * *pose_inliers = best_in.  n < min_inliers is bNoMore (PnPsolver.cc:145-149): nothing is generated,
+ * the hypothesis and set rows are zeros, the counts 0, the indices -1.  ORB_EINVAL as above and for
+ * min_inliers < 4 (SetRansacParameters never yields it). */
+int orb_pnp_ransac(int n, const float* p3d, const float* p2d, const float* sigma2, float th2, double fu, double fv,
+                   double uc, double vc, int n_hyp, const int32_t* sets, const int32_t* rand31, int min_inliers,
+                   int best_in, int32_t* counts, uint64_t* masks, int32_t* best_at, int32_t* first_ok, double* R,
+                   double* t, int32_t* sets_out, int32_t* refined_counts, int32_t* first_refined, float* pose,
+                   uint64_t* pose_mask, int32_t* pose_inliers, int device);
+/* S PnPsolvers on device-resident data: the arguments of orb_pnp_check_inliers_batch_device with
+ * d_rand31 (S x n_hyp x 4 int32) in place of d_R / d_t; the draws are mapped to sets on the device,
+ * where each solver's n is.  A negative d_rand31 value is clamped to 0 (the host forms refuse it).
+ * Further outputs, each may be NULL: d_R S x n_hyp x 9, d_t S x n_hyp x 3 doubles, d_sets_out S x
+ * n_hyp x 4, d_refined_counts S x n_hyp, d_first_refined S, d_pose S x 12 floats, d_pose_mask S x W
+ * (before the scatter through d_index), d_pose_inliers S, as above.  Asynchronous on `stream`;
+ * scratch is stream-ordered. */
+int orb_pnp_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                const float* d_mp_pos, const uint8_t* d_mp_bad, const float* level_sigma2, int nlevels,
+                                float th2, double fu, double fv, double uc, double vc, int n_hyp,
+                                const int32_t* d_rand31, int min_inliers, const int32_t* d_best_in, int32_t* d_n,
+                                int32_t* d_index, int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                int32_t* d_first_ok, double* d_R, double* d_t, int32_t* d_sets_out,
+                                int32_t* d_refined_counts, int32_t* d_first_refined, float* d_pose,
+                                uint64_t* d_pose_mask, int32_t* d_pose_inliers, void* stream);
 
 /* ---- Optimizer: motion-only pose optimisation (GPU: csrc/orb_optimizer.hip) ----------- */
 /* Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285) with the parts of g2o

@@ -483,10 +483,11 @@ private:
     int device_;
 };
 
-// The consensus half of ORB_SLAM::PnPsolver (PnPsolver.cc:39-230, 280-311).  The caller draws the
-// minimal sets and runs EPnP's compute_pose for a block of iterations first (the callers ask for 5
-// at a time, Tracking.cc:961) and hands the poses over; one call scores them all and applies
-// lines 181-196.
+// ORB_SLAM::PnPsolver (PnPsolver.cc:39-311 and EPnP under it).  iterate(nIterations, bNoMore,
+// vbInliers, nInliers, rand31, Tcw) / find run whole iterations on the device, minimal sets, EPnP's
+// compute_pose and Refine included, from the values of rand() that the caller hands over (four per
+// iteration; the class owns no random generator).  The older iterate(vR, vt) scores poses the caller
+// made: one call scores them all and applies lines 181-196.
 class PnPsolver {
 public:
     // PnPsolver(F, vpMapPointMatches) (PnPsolver.cc:39-82) over PODs: keysUn = F.mvKeysUn,
@@ -551,6 +552,76 @@ public:
         return first;
     }
 
+    // iterate(nIterations, bNoMore, vbInliers, nInliers) (PnPsolver.cc:137-230).  rand31: the values
+    // rand() would return, 0 <= r < 2^31, four per iteration.  The reference's loop goes on while
+    // mnIterations < mRansacMaxIts || nCurrentIterations < nIterations, an OR: up to
+    // max(mRansacMaxIts - mnIterations, nIterations) iterations are run and rand31 must hold that many
+    // sets of four.  Returns true with the pose in Tcw (12 floats: Rcw row-major, then tcw) where the
+    // reference returns mRefinedTcw or mBestTcw, false where it returns an empty Mat.  vbInliers: per
+    // frame keypoint.  randUsed (may be NULL): the number of values consumed, 4 per iteration taken
+    // as run.  mRansacMinInliers >= 4 (SetRansacParameters sees to it).
+    bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers,
+                 const std::vector<int32_t>& rand31, float* Tcw, size_t* randUsed = nullptr) {
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        if (randUsed) *randUsed = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        const int k = std::max(mRansacMaxIts - mnIterations, nIterations);
+        if (k > 0) {
+            if (rand31.size() < (size_t)k * 4) throw std::runtime_error("orb: rand31 must hold 4 values per iteration");
+            const int W = (N + 63) / 64;
+            std::vector<int32_t> counts((size_t)k), best_at((size_t)k);
+            std::vector<uint64_t> masks((size_t)k * W + 1), pose_mask((size_t)W + 1);
+            std::vector<double> vR((size_t)k * 9), vt((size_t)k * 3);
+            int32_t first_refined = -1, pose_inliers = 0;
+            float pose[12];
+            orb_check(orb_pnp_ransac(N, mvP3Dw.data(), mvP2D.data(), mvSigma2.data(), mRansacTh, fu, fv, uc, vc, k,
+                                     nullptr, rand31.data(), mRansacMinInliers, mnBestInliers, counts.data(),
+                                     masks.data(), best_at.data(), nullptr, vR.data(), vt.data(), nullptr, nullptr,
+                                     &first_refined, pose, pose_mask.data(), &pose_inliers, device_));
+            const int last = first_refined >= 0 ? first_refined : k - 1;
+            mnIterations += last + 1;
+            if (randUsed) *randUsed = (size_t)(last + 1) * 4;
+            const int holder = best_at[(size_t)last];
+            if (holder >= 0) {
+                mnBest = holder;
+                mnBestInliers = counts[(size_t)holder];
+                unpack(&masks[(size_t)holder * W], mvbBestInliers);
+                for (int j = 0; j < 9; ++j) mBestTcw[j] = (float)vR[(size_t)holder * 9 + j];
+                for (int j = 0; j < 3; ++j) mBestTcw[9 + j] = (float)vt[(size_t)holder * 3 + j];
+            }
+            if (first_refined >= 0) {
+                nInliers = pose_inliers;
+                std::vector<bool> refined;
+                unpack(pose_mask.data(), refined);
+                vbInliers = InliersByKeyPoint(refined);
+                std::copy(pose, pose + 12, Tcw);
+                return true;
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) {
+            bNoMore = true;
+            if (mnBestInliers >= mRansacMinInliers) {
+                nInliers = mnBestInliers;
+                vbInliers = InliersByKeyPoint(mvbBestInliers);
+                std::copy(mBestTcw, mBestTcw + 12, Tcw);
+                return true;
+            }
+        }
+        return false;
+    }
+
+    // find (PnPsolver.cc:131-135): iterate(mRansacMaxIts, ...)
+    bool find(std::vector<bool>& vbInliers, int& nInliers, const std::vector<int32_t>& rand31, float* Tcw,
+              size_t* randUsed = nullptr) {
+        bool bFlag;
+        return iterate(mRansacMaxIts, bFlag, vbInliers, nInliers, rand31, Tcw, randUsed);
+    }
+
     // CheckInliers for one pose (Refine's scoring, PnPsolver.cc:255-262): the count and the flags.
     int CheckInliers(const double* R, const double* t, std::vector<bool>& vbInliers) const {
         std::vector<uint64_t> mask((size_t)(N + 63) / 64 + 1);
@@ -587,6 +658,7 @@ public:
     int mnIterations, mnBestInliers, mnBest;
     int mRansacMinInliers, mRansacMaxIts;
     float mRansacEpsilon, mRansacTh;
+    float mBestTcw[12] = {0};  // Rcw row-major, tcw
     int N;
 
 private:

@@ -18,8 +18,8 @@ from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, sy
 from .database import KeyFrameDatabase
 from .initializer import Initializer, InitializerRansac, initializer_minimal_sets
 from .optimizer import Optimizer
-from .solvers import (PnPConsensus, Sim3Consensus, Sim3Ransac, pnp_ransac_parameters, sim3_minimal_sets,
-                      sim3_ransac_parameters)
+from .solvers import (PnPConsensus, PnPRansac, Sim3Consensus, Sim3Ransac, pnp_minimal_sets, pnp_ransac_parameters,
+                      sim3_minimal_sets, sim3_ransac_parameters)
 from .vocabulary import ORBVocabulary
 
 __all__ = [
@@ -35,6 +35,8 @@ __all__ = [
     "Sim3Consensus",
     "Sim3Ransac",
     "sim3_minimal_sets",
+    "PnPRansac",
+    "pnp_minimal_sets",
     "pnp_ransac_parameters",
     "sim3_ransac_parameters",
     "Frame",

@@ -219,6 +219,11 @@ HIP_SIGNATURES = {
                              _vp, _vp, _i]),
     "orb_sim3_ransac_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_pnp_compute_hypotheses": (_i, [_i, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orb_pnp_compute_pose_n": (_i, [_i, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _i]),
+    "orb_pnp_ransac": (_i, [_i, _vp, _vp, _vp, _f, _d, _d, _d, _d, _i, _vp, _vp, _i, _i] + [_vp] * 12 + [_i]),
+    "orb_pnp_ransac_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _d, _d, _d, _d, _i, _vp,
+                                         _i] + [_vp] * 16),
     "orb_pose_optimization": (_i, [_i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_pose_optimization_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp]),

@@ -4,9 +4,11 @@
 // (src/Sim3Solver.cc:335-359, with Project 377-398) for every hypothesis of a solver at once, the
 // per-correspondence set-up of the two constructors (PnPsolver.cc:40-82, 126-128;
 // Sim3Solver.cc:37-112) and the keep-the-best rules of the two iterate() loops (PnPsolver.cc:181-196,
-// Sim3Solver.cc:183-200).  PnP's hypotheses (EPnP compute_pose) and minimal sets are the caller's;
-// Sim3's are made here from the caller's rand() values: the minimal sets of Sim3Solver::iterate
-// (Sim3Solver.cc:163-177) and Horn's closed form, Sim3Solver::computeT (215-332), DESIGN.md §15.
+// Sim3Solver.cc:183-200).  In the check_inliers entry points the hypotheses are the caller's; in the
+// ransac ones they are made here from the caller's rand() values: the minimal sets of
+// Sim3Solver::iterate (Sim3Solver.cc:163-177) and Horn's closed form, Sim3Solver::computeT (215-332),
+// DESIGN.md §15; the minimal sets of PnPsolver::iterate (PnPsolver.cc:160-173), EPnP's compute_pose
+// (449-497, csrc/orb_epnp_math.h) and Refine (232-277), DESIGN.md §17.
 //
 // Arithmetic: the TU is built -ffp-contract=off and the fused multiply-adds that g++ -O3
 // -march=native makes of the reference's own translation units are written out
@@ -41,6 +43,14 @@
 //                      scratch, computeT in registers (cv::eigen as JacobiImpl_<float> with every
 //                      array index a compile-time constant: no scratch memory), T12 / T21 written.
 //   k_sim3_accepted    one workgroup per solver: the Sim3 and mask row of the accepted hypothesis.
+//   k_pnp_hypotheses   one lane per (solver, hypothesis), between prepare and score: the four draws
+//                      mapped to indices, compute_pose with n = 4, the 12 x 12 work matrix of its
+//                      Jacobi SVD in LDS laid out [element][lane]; R / t written as doubles.
+//   k_pnp_refine       one workgroup per (solver, iteration that replaced the best): compute_pose on
+//                      the correspondences of the iteration's mask (one lane, every sum a single
+//                      chain); its poses are scored by k_cons_score<PNP> again.
+//   k_pnp_select       one workgroup per solver: the first replacing iteration whose refined count
+//                      is > min_inliers, and the pose, mask and count that iterate returns.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +60,7 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_epnp_math.h"
 #include "orb_internal.h"
 
 namespace {
@@ -547,9 +558,7 @@ __device__ __forceinline__ void centroid3(const float* P, float* Pr, float* C) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) Pr[k] = P[k] - C[k / 3];
 }
-// DUtils::Random::RandomInt(0, size - 1) on rand()'s value r: int(((double)r / 2^31) * size), which
-// for 0 <= r < 2^31 and size <= 8192 is (r * size) >> 31
-__device__ __forceinline__ int random_int(int r, int size) { return (int)(((long long)r * (long long)size) >> 31); }
+// (DUtils::Random::RandomInt and the minimal sets of both solvers: orb_epnp::minimal_set<K>)
 
 // One lane per (solver, hypothesis), after k_cons_prepare<SIM3>.
 __global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
@@ -570,15 +579,9 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) idx[i] = min(max(y.sets[3 * g + i], 0), n - 1);
         } else {
-            // vAvailableIndices starts as the identity; [idx] = back(), pop_back() with idx the value
-            // drawn (Sim3Solver.cc:175-176).  Two entries at most differ from the identity.
-            const int r0 = max(y.rand31[3 * g], 0), r1 = max(y.rand31[3 * g + 1], 0), r2 = max(y.rand31[3 * g + 2], 0);
-            idx[0] = random_int(r0, n);                 // [idx0] = n - 1
-            const int rb = random_int(r1, n - 1);
-            idx[1] = rb == idx[0] ? n - 1 : rb;
-            const int back2 = (n - 2 == idx[0]) ? n - 1 : n - 2;  // [idx1] = back(), the entry at n - 2
-            const int rc = random_int(r2, n - 2);
-            idx[2] = rc == idx[1] ? back2 : (rc == idx[0] ? n - 1 : rc);
+            // vAvailableIndices, [idx] = back(), pop_back() with idx the value drawn (Sim3Solver.cc:175-176):
+            // the mapping PnPsolver shares
+            orb_epnp::minimal_set<3>(y.rand31 + 3 * g, n, idx);
         }
         const float* x = a.soa + (size_t)s * NV_SIM3 * cap;
         float P1[9], P2[9], Pr1[9], Pr2[9], O1[3], O2[3];
@@ -718,6 +721,179 @@ __global__ void __launch_bounds__(64) k_sim3_accepted(ConsArgs a, const float* s
     if (accepted_mask)
         for (int w = tid; w < a.W; w += 64)
             accepted_mask[(size_t)s * a.W + w] = h >= 0 ? a.masks[((size_t)s * a.n_hyp + h) * a.W + w] : 0ull;
+}
+
+// ---- PnPsolver: the hypotheses and Refine (PnPsolver.cc:137-277, 314-922) ----------------
+constexpr int PNP_LDS = orb_epnp::WK_DOUBLES * 64 * 8;  // 79 872 bytes: [element][lane], two workgroups per CU
+
+struct PnpArgs {
+    const int32_t* rand31;  // S x n_hyp x 4 values of rand(), or
+    const int32_t* sets;    // S x n_hyp x 4 indices: exactly one of the two
+    double* R;              // S x n_hyp x 9, S x n_hyp x 3: the score kernel's input
+    double* t;
+    double* rep;            // may be NULL
+    int32_t* sets_out;      // may be NULL
+    // Refine and the result of the call
+    double* rR;
+    double* rt;
+    int32_t* rcounts;
+    uint64_t* rmasks;
+    const int32_t* sel;     // the stand-alone n-point pose: n_sel indices in place of a mask row
+    int n_sel;
+    int32_t* first_refined;
+    float* pose;
+    uint64_t* pose_mask;
+    int32_t* pose_inliers;
+};
+
+// The four correspondences of a minimal set, and alphas / pcs, in the lane's registers.
+struct Pts4 {
+    static constexpr bool STORED = true;
+    double pws[12], us[8], al[16], pcs[12];
+    __device__ __forceinline__ int size() const { return 4; }
+    __device__ __forceinline__ double pw(int i, int j) const { return pws[3 * i + j]; }
+    __device__ __forceinline__ double u(int i, int j) const { return us[2 * i + j]; }
+    __device__ __forceinline__ double& alpha(int i, int c) { return al[4 * i + c]; }
+    __device__ __forceinline__ double& pc(int i, int j) { return pcs[3 * i + j]; }
+};
+
+// The n correspondences of an index list, read from the SoA scratch where they are used; alphas and
+// pcs are recomputed where they are read (no per-correspondence storage).
+struct PtsList {
+    static constexpr bool STORED = false;
+    const float* q;
+    int cap, n;
+    const uint16_t* list;
+    __device__ __forceinline__ int size() const { return n; }
+    __device__ __forceinline__ double pw(int i, int j) const { return (double)q[(size_t)j * cap + list[i]]; }
+    __device__ __forceinline__ double u(int i, int j) const { return (double)q[(size_t)(3 + j) * cap + list[i]]; }
+};
+
+// One lane per (solver, hypothesis), after k_cons_prepare<PNP>: the set from the draws, compute_pose
+// with n = 4, the 12 x 12 and the small decompositions' work arrays in the lane's column of LDS.
+__global__ void __launch_bounds__(64) k_pnp_hypotheses(ConsArgs a, PnpArgs y) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int s = blockIdx.y, h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= a.n_hyp) return;
+    const size_t g = (size_t)s * a.n_hyp + h;
+    const int n = a.n[s], cap = a.cap;
+    double R[9], t[3], rep = 0;
+    int idx[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = 0;
+    t[0] = t[1] = t[2] = 0;
+    // N < mRansacMinInliers: bNoMore, nothing is generated (PnPsolver.cc:145-149); n >= 4 otherwise
+    if (n >= a.min_inliers && n >= (y.sets ? 1 : 4)) {
+        if (y.sets) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) idx[i] = min(max(y.sets[4 * g + i], 0), n - 1);
+        } else
+            orb_epnp::minimal_set<4>(y.rand31 + 4 * g, n, idx);
+        orb_epnp::Epnp<orb_epnp::Mat<64>, Pts4> e;
+        e.wk = orb_epnp::Mat<64>{(double*)smem + threadIdx.x};
+        const float* q = a.soa + (size_t)s * NV_PNP * cap;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {  // add_correspondence: float to double
+#pragma unroll
+            for (int j = 0; j < 3; ++j) e.pt.pws[3 * i + j] = (double)q[(size_t)j * cap + idx[i]];
+            e.pt.us[2 * i] = (double)q[(size_t)3 * cap + idx[i]];
+            e.pt.us[2 * i + 1] = (double)q[(size_t)4 * cap + idx[i]];
+        }
+        e.fu = a.fu, e.fv = a.fv, e.uc = a.uc, e.vc = a.vc;
+        e.br = 0;
+        rep = orb_epnp::compute_pose(e, R, t);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) y.R[g * 9 + k] = R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) y.t[g * 3 + k] = t[k];
+    if (y.rep) y.rep[g] = rep;
+    if (y.sets_out) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y.sets_out[g * 4 + k] = idx[k];
+    }
+}
+
+// Refine's compute_pose (PnPsolver.cc:234-256), one workgroup per (solver, iteration): only the
+// iterations that replaced the best have a new mask to refine (best_at[h] == h), the
+// others leave a NaN pose and a count of -1.  Lane 0 runs compute_pose on the correspondences of the
+// iteration's mask in index order; every sum over them is the single chain of the reference.  With
+// y.sel the list is given instead (the stand-alone n-point pose).
+__global__ void __launch_bounds__(64) k_pnp_refine(ConsArgs a, PnpArgs y) {
+    __shared__ uint16_t s_list[CS_MAX_CAP];
+    __shared__ double s_wk[orb_epnp::WK_DOUBLES];
+    __shared__ int s_n;
+    const int s = blockIdx.y, h = blockIdx.x, tid = threadIdx.x;
+    const size_t g = (size_t)s * a.n_hyp + h;
+    const bool live = y.sel || a.best_at[g] == h;
+    if (tid == 0 && y.rcounts) y.rcounts[g] = live ? 0 : -1;
+    if (!live) {
+        if (tid < 9) y.rR[g * 9 + tid] = __builtin_nan("");
+        if (tid < 3) y.rt[g * 3 + tid] = __builtin_nan("");
+        return;
+    }
+    if (y.sel) {
+        for (int i = tid; i < y.n_sel; i += 64) s_list[i] = (uint16_t)y.sel[i];
+        if (tid == 0) s_n = y.n_sel;
+    } else if (tid == 0) {
+        int k = 0;
+        for (int w = 0; w < a.W; ++w) {
+            unsigned long long bits = a.masks[g * a.W + w];  // only bits below n are ever set
+            while (bits) {
+                s_list[k++] = (uint16_t)(w * 64 + __builtin_ctzll(bits));
+                bits &= bits - 1;
+            }
+        }
+        s_n = k;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    orb_epnp::Epnp<orb_epnp::Mat<1>, PtsList> e;
+    e.wk = orb_epnp::Mat<1>{s_wk};
+    e.pt.q = a.soa + (size_t)s * NV_PNP * a.cap;
+    e.pt.cap = a.cap;
+    e.pt.n = s_n;
+    e.pt.list = s_list;
+    e.fu = a.fu, e.fv = a.fv, e.uc = a.uc, e.vc = a.vc;
+    e.br = 0;
+    double R[9], t[3];
+    const double rep = orb_epnp::compute_pose(e, R, t);
+    for (int k = 0; k < 9; ++k) y.rR[g * 9 + k] = R[k];
+    for (int k = 0; k < 3; ++k) y.rt[g * 3 + k] = t[k];
+    if (y.rep && y.sel) y.rep[g] = rep;
+}
+
+// What iterate returns per solver: the refined pose, mask and count of the first replacing iteration
+// whose Refine counted more than min_inliers (PnPsolver.cc:198-208, 264), else the best ones
+// (213-226); NaN and a zero row when there is nothing, or when the best is still the earlier calls'.
+// The pose is Rcw row-major then tcw, double narrowed to float (mBestTcw / mRefinedTcw).
+__global__ void __launch_bounds__(64) k_pnp_select(ConsArgs a, PnpArgs y) {
+    __shared__ int s_f;
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const size_t g0 = (size_t)s * a.n_hyp;
+    if (tid == 0) s_f = INT_MAX;
+    __syncthreads();
+    for (int h = tid; h < a.n_hyp; h += 64)
+        if (a.best_at[g0 + h] == h && y.rcounts[g0 + h] > a.min_inliers) atomicMin(&s_f, h);
+    __syncthreads();
+    const int f = s_f == INT_MAX ? -1 : s_f;
+    const int hb = a.best_at[g0 + a.n_hyp - 1];
+    const int best_in = a.best_in ? a.best_in[s] : 0;
+    if (tid == 0) {
+        if (y.first_refined) y.first_refined[s] = f;
+        if (y.pose_inliers)
+            y.pose_inliers[s] = f >= 0 ? y.rcounts[g0 + f]
+                                       : (hb >= 0 ? a.counts[g0 + hb] : (hb == -2 && best_in >= a.min_inliers ? best_in : 0));
+    }
+    if (y.pose && tid < 12) {
+        const double* Rs = f >= 0 ? y.rR + (g0 + f) * 9 : (hb >= 0 ? y.R + (g0 + hb) * 9 : nullptr);
+        const double* ts = f >= 0 ? y.rt + (g0 + f) * 3 : (hb >= 0 ? y.t + (g0 + hb) * 3 : nullptr);
+        y.pose[(size_t)s * 12 + tid] = Rs ? (float)(tid < 9 ? Rs[tid] : ts[tid - 9]) : __builtin_nanf("");
+    }
+    if (y.pose_mask)
+        for (int w = tid; w < a.W; w += 64)
+            y.pose_mask[(size_t)s * a.W + w] =
+                f >= 0 ? y.rmasks[(g0 + f) * a.W + w] : (hb >= 0 ? a.masks[(g0 + hb) * a.W + w] : 0ull);
 }
 
 template <int MODEL, class HT>
@@ -983,6 +1159,168 @@ int run_host_sim3(ConsArgs a, bool score, int n, const float* x1, const float* x
     return ORB_OK;
 }
 
+// The PnP chain on a filled ConsArgs / PnpArgs: prepare, hypotheses and, with `score`, the consensus on
+// them, Refine at the replacing iterations, the consensus on the refined poses and the result.
+int launch_pnp(const ConsArgs& a, const PnpArgs& y, bool score, hipStream_t st) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_pnp_hypotheses, hipFuncAttributeMaxDynamicSharedMemorySize, PNP_LDS);
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL((k_cons_prepare<PNP>), dim3(a.S), dim3(CS_PREP_THREADS), 0, st, a);
+    ORB_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((a.n_hyp + 63) / 64, a.S), dim3(64), PNP_LDS, st, a, y);
+    ORB_HIPCHK(hipGetLastError());
+    if (!score) return ORB_OK;
+    const dim3 sg(a.S, (a.n_hyp + CS_TILE - 1) / CS_TILE, (std::max(a.W, 1) + CS_WAVES - 1) / CS_WAVES);
+    hipLaunchKernelGGL((k_cons_score<PNP, double>), sg, dim3(CS_THREADS), 0, st, a, (const double*)y.R, (const double*)y.t);
+    ORB_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL((k_cons_select<PNP>), dim3(a.S), dim3(CS_SEL_THREADS), 0, st, a);
+    ORB_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pnp_refine, dim3(a.n_hyp, a.S), dim3(64), 0, st, a, y);
+    ORB_HIPCHK(hipGetLastError());
+    ConsArgs b = a;
+    b.counts = y.rcounts;
+    b.masks = y.rmasks;
+    hipLaunchKernelGGL((k_cons_score<PNP, double>), sg, dim3(CS_THREADS), 0, st, b, (const double*)y.rR, (const double*)y.rt);
+    ORB_HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pnp_select, dim3(a.S), dim3(64), 0, st, a, y);
+    ORB_HIPCHK(hipGetLastError());
+    return ORB_OK;
+}
+
+// Exactly one of sets / rand31 (n_hyp x 4), every value in range (the host forms).
+int check_draws4(const char* who, int n, int n_hyp, const int32_t* sets, const int32_t* rand31) {
+    if ((sets != nullptr) == (rand31 != nullptr))
+        return fail(ORB_EINVAL, std::string(who) + ": exactly one of sets and rand31 must be given");
+    const int32_t* v = sets ? sets : rand31;
+    for (size_t k = 0; k < (size_t)n_hyp * 4; ++k) {
+        if (sets && n > 0 && (v[k] < 0 || v[k] >= n))
+            return fail(ORB_EINVAL, std::string(who) + ": sets[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
+                                        " is outside [0, n)");
+        if (rand31 && v[k] < 0)
+            return fail(ORB_EINVAL, std::string(who) + ": rand31[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
+                                        " is outside [0, 2^31)");
+    }
+    return ORB_OK;
+}
+
+struct PnpHost {  // the host outputs, each may be NULL
+    double* R;
+    double* t;
+    double* rep;
+    int32_t* sets_out;
+    int32_t* refined_counts;
+    int32_t* first_refined;
+    float* pose;
+    uint64_t* pose_mask;
+    int32_t* pose_inliers;
+};
+
+enum { PNP_HYP = 0, PNP_RANSAC = 1, PNP_POSE_N = 2 };
+
+// One PnPsolver from compact host arrays in one stream-ordered chain: the hypotheses (PNP_HYP), the
+// whole iterate (PNP_RANSAC) or compute_pose on the n_sel correspondences `sel` (PNP_POSE_N, n_hyp = 1).
+// Without the consensus sigma2 may be NULL (zeros are staged).
+int run_host_pnp(ConsArgs a, int mode, int n, const float* p3d, const float* p2d, const float* sigma2,
+                 const int32_t* sets, const int32_t* rand31, const int32_t* sel, int n_sel, const PnpHost& o,
+                 int32_t* counts, uint64_t* masks, int32_t* best_at, int32_t* first, int best_in, int device) {
+    int ndev = 0;
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
+    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
+    ORB_HIPCHK(hipSetDevice(device));
+    const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
+    const size_t nh = (size_t)n_hyp;
+    // staging: in  [p3d | p2d | sigma2 | draws | sel | best_in]
+    //          out [counts | best_at | first, n | R | t | rep | sets | refined counts | first_refined, inliers |
+    //               pose | pose mask | masks]
+    //          then, device only, [refined R | refined t | refined masks | the SoA scratch]
+    const size_t o1 = 0, o2 = al(o1 + (size_t)n * 12), o3 = al(o2 + (size_t)n * 8), oD = al(o3 + (size_t)n * 4),
+                 oL = al(oD + nh * 16), oI = al(oL + (size_t)n_sel * 4), in_end = al(oI + 4);
+    const size_t oC = in_end, oB = al(oC + nh * 4), oF = al(oB + nh * 4), oR = al(oF + 8), oT = al(oR + nh * 72),
+                 oE = al(oT + nh * 24), oSet = al(oE + nh * 8), oRC = al(oSet + nh * 16), oFR = al(oRC + nh * 4),
+                 oP = al(oFR + 8), oPM = al(oP + 48), oM = al(oPM + (size_t)W * 8), out_end = al(oM + nh * W * 8);
+    const size_t oRR = out_end, oRT = al(oRR + nh * 72), oRM = al(oRT + nh * 24), oSoa = al(oRM + nh * W * 8),
+                 total = al(oSoa + (size_t)NV_PNP * cap * 4);
+    if (int r = C->reserve(total, out_end)) return r;
+    uint8_t* hp = C->pinned;
+    if (n) {
+        std::memcpy(hp + o1, p3d, (size_t)n * 12);
+        std::memcpy(hp + o2, p2d, (size_t)n * 8);
+        if (sigma2) std::memcpy(hp + o3, sigma2, (size_t)n * 4); else std::memset(hp + o3, 0, (size_t)n * 4);
+    }
+    if (sets || rand31) std::memcpy(hp + oD, sets ? sets : rand31, nh * 16);
+    if (n_sel) std::memcpy(hp + oL, sel, (size_t)n_sel * 4);
+    std::memcpy(hp + oI, &best_in, 4);
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    uint8_t* d = C->buf;
+    a.c0 = (const float*)(d + o1);
+    a.c1 = (const float*)(d + o2);
+    a.c2 = (const float*)(d + o3);
+    a.n_direct = n;
+    a.best_in = (const int32_t*)(d + oI);
+    a.soa = (float*)(d + oSoa);
+    a.counts = (int32_t*)(d + oC);
+    a.best_at = (int32_t*)(d + oB);
+    a.first = (int32_t*)(d + oF);
+    a.n = a.first + 1;
+    a.index = nullptr;
+    a.masks = W ? (uint64_t*)(d + oM) : nullptr;
+    a.cap = cap;
+    a.S = 1;
+    a.W = W;
+    PnpArgs y{};
+    if (mode != PNP_POSE_N) (sets ? y.sets : y.rand31) = (const int32_t*)(d + oD);
+    y.R = (double*)(d + oR);
+    y.t = (double*)(d + oT);
+    y.rep = (double*)(d + oE);
+    y.sets_out = (int32_t*)(d + oSet);
+    y.rR = (double*)(d + oRR);
+    y.rt = (double*)(d + oRT);
+    y.rcounts = (int32_t*)(d + oRC);
+    y.rmasks = W ? (uint64_t*)(d + oRM) : nullptr;
+    y.first_refined = (int32_t*)(d + oFR);
+    y.pose_inliers = y.first_refined + 1;
+    y.pose = (float*)(d + oP);
+    y.pose_mask = (uint64_t*)(d + oPM);
+    int r = ORB_OK;
+    hipError_t e = hipSuccess;
+    if (mode == PNP_POSE_N) {
+        y.sel = (const int32_t*)(d + oL);
+        y.n_sel = n_sel;
+        y.rR = y.R, y.rt = y.t;  // the pose goes where the caller reads R and t
+        y.rcounts = nullptr;
+        hipLaunchKernelGGL((k_cons_prepare<PNP>), dim3(1), dim3(CS_PREP_THREADS), 0, C->stream, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_pnp_refine, dim3(1, 1), dim3(64), 0, C->stream, a, y);
+            e = hipGetLastError();
+        }
+    } else
+        r = launch_pnp(a, y, mode == PNP_RANSAC, C->stream);
+    if (r == ORB_OK && e == hipSuccess)
+        e = hipMemcpyAsync(hp + oC, d + oC, out_end - oC, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
+    if (r) return r;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+    if (mode == PNP_RANSAC) {
+        if (counts) std::memcpy(counts, hp + oC, nh * 4);
+        if (best_at) std::memcpy(best_at, hp + oB, nh * 4);
+        if (first) std::memcpy(first, hp + oF, 4);
+        if (masks && W) std::memcpy(masks, hp + oM, nh * W * 8);
+        if (o.refined_counts) std::memcpy(o.refined_counts, hp + oRC, nh * 4);
+        if (o.first_refined) std::memcpy(o.first_refined, hp + oFR, 4);
+        if (o.pose_inliers) std::memcpy(o.pose_inliers, hp + oFR + 4, 4);
+        if (o.pose) std::memcpy(o.pose, hp + oP, 48);
+        if (o.pose_mask && W) std::memcpy(o.pose_mask, hp + oPM, (size_t)W * 8);
+    }
+    if (o.R) std::memcpy(o.R, hp + oR, nh * 72);
+    if (o.t) std::memcpy(o.t, hp + oT, nh * 24);
+    if (o.rep) std::memcpy(o.rep, hp + oE, nh * 8);
+    if (o.sets_out && mode != PNP_POSE_N) std::memcpy(o.sets_out, hp + oSet, nh * 16);
+    return ORB_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1091,6 +1429,133 @@ int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_c
         e = hipGetLastError();
         if (e != hipSuccess) r = fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
     }
+    (void)hipFreeAsync(tmp, st);
+    return r;
+}
+
+int orb_pnp_compute_hypotheses(int n, const float* p3d, const float* p2d, double fu, double fv, double uc, double vc,
+                               int n_hyp, const int32_t* sets, const int32_t* rand31, double* R, double* t,
+                               double* rep_error, int32_t* sets_out, int device) {
+    const char* who = "pnp_compute_hypotheses";
+    if (n < 1 || !p3d || !p2d) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (int r = check_limits(who, n, n_hyp)) return r;
+    if (int r = check_draws4(who, n, n_hyp, sets, rand31)) return r;
+    if (rand31 && n < 4) return fail(ORB_EINVAL, std::string(who) + ": a minimal set is drawn from n >= 4 correspondences");
+    ConsArgs a{};
+    a.fu = fu, a.fv = fv, a.uc = uc, a.vc = vc;
+    a.n_hyp = n_hyp;
+    a.min_inliers = 0;
+    const PnpHost o{R, t, rep_error, sets_out, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return run_host_pnp(a, PNP_HYP, n, p3d, p2d, nullptr, sets, rand31, nullptr, 0, o, nullptr, nullptr, nullptr, nullptr,
+                        0, device);
+}
+
+int orb_pnp_compute_pose_n(int n, const float* p3d, const float* p2d, double fu, double fv, double uc, double vc,
+                           int n_sel, const int32_t* sel, double* R, double* t, double* rep_error, int device) {
+    const char* who = "pnp_compute_pose_n";
+    if (n < 1 || !p3d || !p2d || !sel) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (int r = check_limits(who, n, 1)) return r;
+    if (n_sel < 1 || n_sel > CS_MAX_CAP)
+        return fail(ORB_EINVAL, std::string(who) + ": n_sel must be in [1, 8192] (got " + std::to_string(n_sel) + ")");
+    for (int k = 0; k < n_sel; ++k)
+        if (sel[k] < 0 || sel[k] >= n)
+            return fail(ORB_EINVAL, std::string(who) + ": sel[" + std::to_string(k) + "] = " + std::to_string(sel[k]) +
+                                        " is outside [0, n)");
+    ConsArgs a{};
+    a.fu = fu, a.fv = fv, a.uc = uc, a.vc = vc;
+    a.n_hyp = 1;
+    const PnpHost o{R, t, rep_error, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return run_host_pnp(a, PNP_POSE_N, n, p3d, p2d, nullptr, nullptr, nullptr, sel, n_sel, o, nullptr, nullptr, nullptr,
+                        nullptr, 0, device);
+}
+
+int orb_pnp_ransac(int n, const float* p3d, const float* p2d, const float* sigma2, float th2, double fu, double fv,
+                   double uc, double vc, int n_hyp, const int32_t* sets, const int32_t* rand31, int min_inliers,
+                   int best_in, int32_t* counts, uint64_t* masks, int32_t* best_at, int32_t* first_ok, double* R,
+                   double* t, int32_t* sets_out, int32_t* refined_counts, int32_t* first_refined, float* pose,
+                   uint64_t* pose_mask, int32_t* pose_inliers, int device) {
+    const char* who = "pnp_ransac";
+    if (n < 0 || (n && (!p3d || !p2d || !sigma2))) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
+    if (int r = check_limits(who, n, n_hyp)) return r;
+    if (min_inliers < 4)
+        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 4, the size of a minimal set (got " +
+                                    std::to_string(min_inliers) + ")");
+    if (int r = check_draws4(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_sigma2(who, sigma2, n, false)) return r;
+    ConsArgs a{};
+    a.th2 = th2;
+    a.fu = fu, a.fv = fv, a.uc = uc, a.vc = vc;
+    a.n_hyp = n_hyp;
+    a.min_inliers = min_inliers;
+    const PnpHost o{R, t, nullptr, sets_out, refined_counts, first_refined, pose, pose_mask, pose_inliers};
+    return run_host_pnp(a, PNP_RANSAC, n, p3d, p2d, sigma2, sets, rand31, nullptr, 0, o, counts, masks, best_at, first_ok,
+                        best_in, device);
+}
+
+int orb_pnp_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int S,
+                                const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                const float* d_mp_pos, const uint8_t* d_mp_bad, const float* level_sigma2, int nlevels,
+                                float th2, double fu, double fv, double uc, double vc, int n_hyp,
+                                const int32_t* d_rand31, int min_inliers, const int32_t* d_best_in, int32_t* d_n,
+                                int32_t* d_index, int32_t* d_counts_out, uint64_t* d_masks, int32_t* d_best_at,
+                                int32_t* d_first_ok, double* d_R, double* d_t, int32_t* d_sets_out,
+                                int32_t* d_refined_counts, int32_t* d_first_refined, float* d_pose,
+                                uint64_t* d_pose_mask, int32_t* d_pose_inliers, void* stream) {
+    const char* who = "pnp_ransac_batch";
+    ConsArgs a{};
+    if (int r = fill_batch(a, who, d_kps, d_counts, cap, S, d_pair_a, d_pair_b, d_match, d_mp_pos, d_mp_bad,
+                           level_sigma2, nlevels, n_hyp, false))
+        return r;
+    if (min_inliers < 4)
+        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 4, the size of a minimal set (got " +
+                                    std::to_string(min_inliers) + ")");
+    if (S == 0) return ORB_OK;
+    if (!d_rand31) return fail(ORB_EINVAL, std::string(who) + ": no rand31 values given");
+    hipStream_t st = (hipStream_t)stream;
+    a.th2 = th2;
+    a.fu = fu, a.fv = fv, a.uc = uc, a.vc = vc;
+    a.min_inliers = min_inliers;
+    a.best_in = d_best_in;
+    a.index = d_index;
+    // stream-ordered scratch for the SoA values, the refined poses and masks, and for every array the
+    // chain needs and the caller did not ask for
+    const size_t SH = (size_t)S * n_hyp;
+    const size_t need[11] = {(size_t)S * NV_PNP * cap * 4,
+                             d_n ? 0 : (size_t)S * 4,
+                             d_counts_out ? 0 : SH * 4,
+                             d_R ? 0 : SH * 72,
+                             d_t ? 0 : SH * 24,
+                             d_best_at ? 0 : SH * 4,
+                             d_masks ? 0 : SH * a.W * 8,
+                             d_refined_counts ? 0 : SH * 4,
+                             SH * 72,
+                             SH * 24,
+                             SH * a.W * 8};
+    size_t off[12] = {0};
+    for (int k = 0; k < 11; ++k) off[k + 1] = off[k] + al(need[k]);
+    uint8_t* tmp = nullptr;
+    hipError_t e = hipMallocAsync((void**)&tmp, off[11], st);
+    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("solvers: scratch: ") + hipGetErrorString(e));
+    a.soa = (float*)tmp;
+    a.n = d_n ? d_n : (int32_t*)(tmp + off[1]);
+    a.counts = d_counts_out ? d_counts_out : (int32_t*)(tmp + off[2]);
+    PnpArgs y{};
+    y.rand31 = d_rand31;
+    y.R = d_R ? d_R : (double*)(tmp + off[3]);
+    y.t = d_t ? d_t : (double*)(tmp + off[4]);
+    y.sets_out = d_sets_out;
+    a.best_at = d_best_at ? d_best_at : (int32_t*)(tmp + off[5]);
+    a.first = d_first_ok;
+    a.masks = d_masks ? d_masks : (uint64_t*)(tmp + off[6]);
+    y.rcounts = d_refined_counts ? d_refined_counts : (int32_t*)(tmp + off[7]);
+    y.rR = (double*)(tmp + off[8]);
+    y.rt = (double*)(tmp + off[9]);
+    y.rmasks = (uint64_t*)(tmp + off[10]);
+    y.first_refined = d_first_refined;
+    y.pose = d_pose;
+    y.pose_mask = d_pose_mask;
+    y.pose_inliers = d_pose_inliers;
+    const int r = launch_pnp(a, y, true, st);
     (void)hipFreeAsync(tmp, st);
     return r;
 }

@@ -2,11 +2,11 @@
 src/Sim3Solver.cc), over the C ABI of ``include/orb_abi.h`` (csrc/orb_solvers.hip).
 
 ``CheckInliers`` for all hypotheses of a solver in one call, with the constructors'
-per-correspondence set-up and the keep-the-best rule of ``iterate``.  For PnP the hypotheses (EPnP
-``compute_pose``, ``Refine``'s pose), the random minimal sets and the iteration counters are the
-caller's.  For Sim3, ``Sim3Ransac`` also draws the minimal sets from the caller's ``rand()`` values
-and runs Horn's ``computeT`` on the device, so a whole ``iterate`` is one call; the package owns no
-random generator.  ``pnp_ransac_parameters`` / ``sim3_ransac_parameters`` are the scalar arithmetic
+per-correspondence set-up and the keep-the-best rule of ``iterate``: ``PnPConsensus`` and
+``Sim3Consensus`` score hypotheses the caller made.  ``PnPRansac`` and ``Sim3Ransac`` also draw the
+minimal sets from the caller's ``rand()`` values and make the hypotheses on the device (EPnP's
+``compute_pose`` and ``Refine``; Horn's ``computeT``), so a whole ``iterate`` is one call; the
+iteration counters stay with the caller and the package owns no random generator.  ``pnp_ransac_parameters`` / ``sim3_ransac_parameters`` are the scalar arithmetic
 of the two ``SetRansacParameters``.
 """
 from __future__ import annotations
@@ -244,17 +244,22 @@ def sim3_minimal_sets(N: int, rand31, fixed: bool = False) -> np.ndarray:
     at the position, so a set may hold an index twice.  The list is N entries whose size shrinks;
     the write may land one slot past the size, where nothing reads it.  ``fixed`` removes by
     position instead (what the reference meant; for tests)."""
+    return _minimal_sets(N, rand31, 3, fixed)
+
+
+def _minimal_sets(N: int, rand31, K: int, fixed: bool) -> np.ndarray:
+    # the one sampler of Sim3Solver (K = 3) and PnPsolver (K = 4)
     N = int(N)
-    r = np.asarray(rand31, np.int64).reshape(-1, 3)
-    if N < 3:
-        raise ValueError("a minimal set is drawn from at least 3 correspondences")
+    r = np.asarray(rand31, np.int64).reshape(-1, K)
+    if N < K:
+        raise ValueError(f"a minimal set is drawn from at least {K} correspondences")
     if r.size and (r.min() < 0 or r.max() >= 2 ** 31):
         raise ValueError("rand31 values must be in [0, 2^31)")
-    sets = np.zeros((len(r), 3), np.int32)
+    sets = np.zeros((len(r), K), np.int32)
     for h in range(len(r)):
         avail = list(range(N))
         size = N
-        for i in range(3):
+        for i in range(K):
             randi = (int(r[h, i]) * size) >> 31
             idx = avail[randi]
             sets[h, i] = idx
@@ -358,4 +363,131 @@ class Sim3Ransac(Sim3Consensus):
             ptr(out["first"]), ptr(out["T12"]), ptr(out["T21"]), ptr(out["sim3"]), ptr(out["sets"]),
             ptr(out["accepted"]), ptr(out["accepted_mask"]), ctypes.c_void_p(s.cuda_stream)))
         out["first_accept"] = out.pop("first")
+        return out
+
+
+def pnp_minimal_sets(N: int, rand31, fixed: bool = False) -> np.ndarray:
+    """The minimal sets of PnPsolver::iterate (PnPsolver.cc:160-173) for (n_hyp, 4) values of ``rand()``:
+    ``sim3_minimal_sets`` with four draws (the same removal by value)."""
+    return _minimal_sets(N, rand31, 4, fixed)
+
+
+def _draws4(sets, rand31):
+    if (sets is None) == (rand31 is None):
+        raise ValueError("exactly one of sets and rand31 must be given")
+    a = np.asarray(sets if rand31 is None else rand31)
+    if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
+        raise ValueError("rand31 values must be in [0, 2^31)")
+    a = np.ascontiguousarray(a, np.int32).reshape(-1, 4)
+    return (a, None, len(a)) if rand31 is None else (None, a, len(a))
+
+
+class PnPRansac(PnPConsensus):
+    """A whole PnPsolver::iterate on the GPU (PnPsolver.cc:137-277): the minimal sets from the caller's
+    ``rand()`` values, EPnP's ``compute_pose`` per set, ``CheckInliers``, the keep-the-best rule and
+    ``Refine`` at the iterations that replaced the best, in one call.  Arguments as for PnPConsensus;
+    min_inliers >= 4."""
+
+    @staticmethod
+    def iterations(max_its: int, done: int, n_iterations: int) -> int:
+        """How many iterations ``iterate(n_iterations, ...)`` runs at most: its loop goes on while
+        ``mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`` (PnPsolver.cc:154), an OR, so
+        it is max(mRansacMaxIts - mnIterations, nIterations), the n_hyp to draw values for."""
+        return max(int(max_its) - int(done), int(n_iterations))
+
+    def compute_hypotheses(self, p3d, p2d, sets=None, rand31=None) -> dict:
+        """``compute_pose`` on minimal sets alone (orb_pnp_compute_hypotheses; host buffers, synchronous)
+        for (n_hyp, 4) ``sets`` of indices or ``rand31`` values.  Returns R (n_hyp, 3, 3), t (n_hyp, 3)
+        float64, rep_error (n_hyp,) and sets."""
+        p3d, p2d = _f32(p3d, 3), _f32(p2d, 2)
+        n = len(p3d)
+        if len(p2d) != n:
+            raise ValueError("p3d and p2d must hold one entry per correspondence")
+        sets, rand31, n_hyp = _draws4(sets, rand31)
+        m = max(n_hyp, 1)
+        R, t, rep, sets_out = np.zeros((m, 3, 3)), np.zeros((m, 3)), np.zeros(m), np.zeros((m, 4), np.int32)
+        check(self._lib.orb_pnp_compute_hypotheses(n, ptr(p3d), ptr(p2d), self.fu, self.fv, self.uc, self.vc, n_hyp,
+                                                   ptr(sets), ptr(rand31), ptr(R), ptr(t), ptr(rep), ptr(sets_out),
+                                                   self.device))
+        return {"R": R[:n_hyp], "t": t[:n_hyp], "rep_error": rep[:n_hyp], "sets": sets_out[:n_hyp]}
+
+    def compute_pose(self, p3d, p2d, sel) -> dict:
+        """``compute_pose`` on the correspondences ``sel`` in that order (orb_pnp_compute_pose_n): what
+        ``Refine`` computes on the set bits of a mask.  Returns R (3, 3), t (3,), rep_error."""
+        p3d, p2d = _f32(p3d, 3), _f32(p2d, 2)
+        sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        R, t, rep = np.zeros((3, 3)), np.zeros(3), np.zeros(1)
+        check(self._lib.orb_pnp_compute_pose_n(len(p3d), ptr(p3d), ptr(p2d), self.fu, self.fv, self.uc, self.vc,
+                                               len(sel), ptr(sel), ptr(R), ptr(t), ptr(rep), self.device))
+        return {"R": R, "t": t, "rep_error": float(rep[0])}
+
+    def iterate(self, p3d, p2d, sigma2, sets=None, rand31=None, best_in: int = 0, want_masks: bool = True) -> dict:
+        """One ``iterate`` over n_hyp iterations without its early return (orb_pnp_ransac; host buffers,
+        synchronous).  Returns what PnPConsensus.check returns plus R, t, sets, refined_counts (n_hyp,:
+        Refine's count at the replacing iterations, -1 elsewhere), first_refined (where iterate returns;
+        first_refined + 1 sets of draws were consumed), pose (12,) float32 (Rcw row-major, tcw),
+        pose_mask (W,), pose_in (n,) bool and pose_inliers."""
+        p3d, p2d, s2 = _f32(p3d, 3), _f32(p2d, 2), _f32(sigma2, 0)
+        n = len(p3d)
+        if len(p2d) != n or len(s2) != n:
+            raise ValueError("p3d, p2d and sigma2 must hold one entry per correspondence")
+        sets, rand31, n_hyp = _draws4(sets, rand31)
+        counts, masks, best_at, first, W = _host_outputs(n_hyp, n)
+        m = max(n_hyp, 1)
+        R, t, sets_out = np.zeros((m, 3, 3)), np.zeros((m, 3)), np.zeros((m, 4), np.int32)
+        rc, fr, pin = np.zeros(m, np.int32), ctypes.c_int32(-1), ctypes.c_int32(0)
+        pose, pmask = np.zeros(12, np.float32), np.zeros(max(W, 1), np.uint64)
+        check(self._lib.orb_pnp_ransac(
+            n, ptr(p3d), ptr(p2d), ptr(s2), self.th2, self.fu, self.fv, self.uc, self.vc, n_hyp, ptr(sets), ptr(rand31),
+            self.min_inliers, int(best_in), ptr(counts), ptr(masks) if want_masks else None, ptr(best_at),
+            ctypes.byref(first), ptr(R), ptr(t), ptr(sets_out), ptr(rc), ctypes.byref(fr), ptr(pose), ptr(pmask),
+            ctypes.byref(pin), self.device))
+        out = {"n": n, "counts": counts[:n_hyp], "best_at": best_at[:n_hyp], "first_ok": int(first.value),
+               "R": R[:n_hyp], "t": t[:n_hyp], "sets": sets_out[:n_hyp], "refined_counts": rc[:n_hyp],
+               "first_refined": int(fr.value), "pose": pose, "pose_mask": pmask[:W],
+               "pose_in": unpack_mask(pmask[:W], n) if W else np.zeros(0, bool), "pose_inliers": int(pin.value)}
+        if want_masks:
+            mm = masks.reshape(-1)[:n_hyp * W].reshape(n_hyp, W)
+            out.update(masks=mm, inliers=unpack_mask(mm, n) if W else np.zeros((n_hyp, 0), bool))
+        return out
+
+    def iterate_batch_device(self, d_kps, d_counts, pair_kf, pair_f, d_match, d_mp_pos, d_mp_bad, level_sigma2, d_rand31,
+                             d_best_in=None, stream=None) -> dict:
+        """S solvers on device-resident data (orb_pnp_ransac_batch_device): as
+        PnPConsensus.check_batch_device with d_rand31 (S, n_hyp, 4) int32 in place of the hypotheses (a
+        negative value is clamped to 0).  Returns its device tensors plus R (S, n_hyp, 9), t (S, n_hyp,
+        3) float64, sets (S, n_hyp, 4), refined_counts (S, n_hyp), first_refined (S,), pose (S, 12)
+        float32 (what Optimizer.pose_optimization_batch_device takes as its input pose), pose_mask (S,
+        W) int64 and pose_inliers (S,).  Asynchronous on `stream`."""
+        import torch
+
+        S, cap = int(d_match.shape[0]), int(d_kps.shape[1])
+        if int(d_match.shape[1]) != cap:
+            raise ValueError("d_match must be (S, cap)")
+        dev = d_kps.device
+        if d_rand31.dtype != torch.int32 or d_rand31.dim() != 3 or int(d_rand31.shape[0]) != S or int(d_rand31.shape[2]) != 4:
+            raise ValueError("d_rand31 must be an int32 tensor (S, n_hyp, 4)")
+        d_rand31 = d_rand31.contiguous()
+        n_hyp = int(d_rand31.shape[1])
+        ls2 = np.ascontiguousarray(level_sigma2, np.float32)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            out = _batch_outputs(torch, S, cap, n_hyp, dev)
+            W = (cap + 63) // 64
+            out.update(R=torch.empty((S, n_hyp, 9), dtype=torch.float64, device=dev),
+                       t=torch.empty((S, n_hyp, 3), dtype=torch.float64, device=dev),
+                       sets=torch.empty((S, n_hyp, 4), dtype=torch.int32, device=dev),
+                       refined_counts=torch.empty((S, n_hyp), dtype=torch.int32, device=dev),
+                       first_refined=torch.empty((S,), dtype=torch.int32, device=dev),
+                       pose=torch.empty((S, 12), dtype=torch.float32, device=dev),
+                       pose_mask=torch.empty((S, W), dtype=torch.int64, device=dev),
+                       pose_inliers=torch.empty((S,), dtype=torch.int32, device=dev))
+        check(self._lib.orb_pnp_ransac_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, S, ptr(pair_kf), ptr(pair_f), ptr(d_match), ptr(d_mp_pos), ptr(d_mp_bad),
+            ptr(ls2), len(ls2), self.th2, self.fu, self.fv, self.uc, self.vc, n_hyp, ptr(d_rand31), self.min_inliers,
+            ptr(d_best_in), ptr(out["n"]), ptr(out["index"]), ptr(out["counts"]), ptr(out["masks"]), ptr(out["best_at"]),
+            ptr(out["first"]), ptr(out["R"]), ptr(out["t"]), ptr(out["sets"]), ptr(out["refined_counts"]),
+            ptr(out["first_refined"]), ptr(out["pose"]), ptr(out["pose_mask"]), ptr(out["pose_inliers"]),
+            ctypes.c_void_p(s.cuda_stream)))
+        out["first_ok"] = out.pop("first")
         return out
