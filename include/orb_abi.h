@@ -619,7 +619,8 @@ int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_
  * sets (80-95), Normalize (747-793) over all keypoints of each frame, ComputeH21 / ComputeF21
  * (224-301) with cv::SVDecomp as OpenCV 2.4's JacobiSVDImpl_<float> is read, T2inv*Hn*T1,
  * H21i.inv() and T2t*Fn*T1, then the two checks above unchanged.  ReconstructH /
- * ReconstructF stay with the caller.
+ * ReconstructF follow in orb_initializer_reconstruct* and, in the same call, orb_initializer_initialize*
+ * below.
  * The draws are the caller's: rand31 holds the n_hyp x 8 values rand() returned, in the order the
  * reference consumes them; draw j of a set is RandomInt(0, N - j - 1) = (r * (N - j)) >> 31 on a
  * list that loses the drawn position (a set never repeats an index); one set serves both models.
@@ -662,6 +663,79 @@ int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32
                                         uint8_t* d_inliers_h, int32_t* d_best_f, float* d_best_score_f,
                                         uint8_t* d_inliers_f, int32_t* d_n_matches, float* d_best_H21,
                                         float* d_best_F21, float* d_RH, int32_t* d_use_h, void* stream);
+
+/* The reconstruction: what Initialize does with the winning model (Initializer.cc:113-116):
+ * ReconstructF (468-568: E21 = K.t()*F21*K, DecomposeE, 4 motion hypotheses) or ReconstructH
+ * (570-730: Faugeras, 8 hypotheses, none when d1/d2 or d2/d3 < 1.00001), CheckRT (796-905) with
+ * Triangulate (732-745) for every hypothesis over every inlier match, and the acceptance rule of
+ * the model in use.  Everything is the statement-for-statement model's bit for bit
+ * except parallax_deg, which goes through acosf (§18 records the bound).
+ *
+ * One pair, host buffers, synchronous.  kps1 / kps2 / matches12 as orb_initializer_check.  M21: the 9
+ * floats of H21 (use_h = 1) or F21 (use_h = 0; anything else is ORB_EINVAL).  inliers: the model's
+ * vbMatchesInliers over match ordinals as orb_initializer_check writes inliers_*, N entries, each 0
+ * or 1 (ORB_EINVAL otherwise).  K4 = fx, fy, cx, cy of the reference camera's K (Tracking.cc:52-63),
+ * finite, fx and fy not 0; sigma = mSigma, finite and not 0; min_parallax (1.0) finite;
+ * min_triangulated (50) >= 0 (ORB_EINVAL with a message naming the argument).  At most 8192
+ * keypoints per frame (ORB_ENOTSUP).
+ * Outputs, any may be NULL: *ok (the return value of Reconstruct*); R21 (9) and t21 (3); P3D (n1 x 3)
+ * and triangulated (n1 u8), vP3D / vbTriangulated indexed by frame-1 keypoint; all four are zeros
+ * when *ok == 0.  Diagnostics, written either way: *n_motion (0, 4 or 8), motion_R (8 x 9) and
+ * motion_t (8 x 3) in the order CheckRT sees them (rows >= n_motion zeros), n_good (8),
+ * cos_parallax (8: vCosParallax[min(50, size - 1)] after the sort, a NaN sorted after every
+ * number; NaN when nGood == 0), parallax_deg (8; 0 when nGood == 0), *best (the chosen hypothesis
+ * or -1), *n_inliers (the N of Reconstruct*: the set entries of the mask). */
+int orb_initializer_reconstruct(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                                const int32_t* matches12, const float* M21, int use_h, const uint8_t* inliers,
+                                const float* K4, float sigma, float min_parallax, int min_triangulated, int32_t* ok,
+                                float* R21, float* t21, float* P3D, uint8_t* triangulated, int32_t* n_motion,
+                                float* motion_R, float* motion_t, int32_t* n_good, float* cos_parallax,
+                                float* parallax_deg, int32_t* best, int32_t* n_inliers, int device);
+/* The same for P pairs on what orb_initializer_ransac_batch_device wrote (d_best_H21, d_best_F21,
+ * d_use_h, d_inliers_h, d_inliers_f: none NULL; d_n_matches may be NULL, when given no ordinal at or
+ * above it is walked), next to the batch arrays of that call; K4 is host memory, one camera for
+ * the batch.  Pair p uses the model and mask that d_use_h[p] names (non-zero: H); a mask entry
+ * other than 0 counts as set; a NaN model (best index -1) ends with ok = 0.  Outputs per pair:
+ * d_P3D P x cap x 3, d_triangulated P x cap (all cap rows written), d_R21 P x 9, d_t21 P x 3,
+ * d_motion_R P x 72, d_motion_t P x 24, d_n_good / d_cos_parallax / d_parallax_deg P x 8, the rest
+ * P; any may be NULL.  Scratch is stream-ordered, about 44 bytes x P x cap, freed with the call.
+ * P <= 65535.  Asynchronous on `stream`. */
+int orb_initializer_reconstruct_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                             const int32_t* d_pair_f1, const int32_t* d_pair_f2,
+                                             const int32_t* d_matches12, const float* d_best_H21,
+                                             const float* d_best_F21, const int32_t* d_use_h,
+                                             const uint8_t* d_inliers_h, const uint8_t* d_inliers_f,
+                                             const int32_t* d_n_matches, const float* K4, float sigma,
+                                             float min_parallax, int min_triangulated, int32_t* d_ok, float* d_R21,
+                                             float* d_t21, float* d_P3D, uint8_t* d_triangulated, int32_t* d_n_motion,
+                                             float* d_motion_R, float* d_motion_t, int32_t* d_n_good,
+                                             float* d_cos_parallax, float* d_parallax_deg, int32_t* d_best,
+                                             int32_t* d_n_inliers, void* stream);
+/* Initializer::Initialize in one call: orb_initializer_ransac followed by orb_initializer_reconstruct
+ * on the model it chose; arguments and outputs are those of the two (any output may be NULL).  The
+ * host form passes the winner, its mask and use_h through the host between the two chains. */
+int orb_initializer_initialize(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                               const int32_t* matches12, float sigma, int n_hyp, const int32_t* rand31, const float* K4,
+                               float min_parallax, int min_triangulated, float* H21, float* H12, float* F21,
+                               int32_t* sets_out, float* scores_h, float* scores_f, int32_t* best_h,
+                               float* best_score_h, uint8_t* inliers_h, int32_t* best_f, float* best_score_f,
+                               uint8_t* inliers_f, float* best_H21, float* best_F21, float* RH, int32_t* use_h,
+                               int* n_matches, int32_t* ok, float* R21, float* t21, float* P3D, uint8_t* triangulated,
+                               int32_t* n_motion, float* motion_R, float* motion_t, int32_t* n_good,
+                               float* cos_parallax, float* parallax_deg, int32_t* best, int32_t* n_inliers,
+                               int device);
+/* The batch form: both chains enqueued on `stream` with no host round trip between them; what the
+ * second needs of an absent output of the first lives in stream-ordered scratch. */
+int orb_initializer_initialize_batch_device(
+    const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
+    const int32_t* d_pair_f2, const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
+    const float* K4, float min_parallax, int min_triangulated, float* d_H21, float* d_H12, float* d_F21,
+    int32_t* d_sets_out, float* d_scores_h, float* d_scores_f, int32_t* d_best_h, float* d_best_score_h,
+    uint8_t* d_inliers_h, int32_t* d_best_f, float* d_best_score_f, uint8_t* d_inliers_f, int32_t* d_n_matches,
+    float* d_best_H21, float* d_best_F21, float* d_RH, int32_t* d_use_h, int32_t* d_ok, float* d_R21, float* d_t21,
+    float* d_P3D, uint8_t* d_triangulated, int32_t* d_n_motion, float* d_motion_R, float* d_motion_t,
+    int32_t* d_n_good, float* d_cos_parallax, float* d_parallax_deg, int32_t* d_best, int32_t* d_n_inliers,
+    void* stream);
 
 /* ---- Solvers: PnP / Sim3 RANSAC consensus (GPU: csrc/orb_solvers.hip) ---------------- */
 /* PnPsolver::CheckInliers (reference src/PnPsolver.cc:280-311) and Sim3Solver::CheckInliers

@@ -424,7 +424,7 @@ public:
     // the matches, the minimal sets, Normalize, ComputeH21 / ComputeF21 and both checks for all
     // mMaxIterations iterations.  rand31: the mMaxIterations x 8 values rand() returned, in the
     // order DUtils::Random::RandomInt would consume them (the package owns no generator).
-    // ReconstructH / ReconstructF (CheckRT, Triangulate, DecomposeE) stay with the caller.
+    // ReconstructH / ReconstructF below take it from there; the eight-argument Initialize does both.
     TwoViewModels Initialize(const std::vector<orb_keypoint_t>& keys2, const std::vector<int>& vMatches12,
                              const std::vector<int>& rand31) {
         if (rand31.size() != (size_t)mMaxIterations * 8) throw std::runtime_error("orb: rand31 must hold mMaxIterations x 8 values");
@@ -453,6 +453,33 @@ public:
         return r;
     }
 
+    // ReconstructH / ReconstructF (Initializer.cc:468-730) on a given model, after SetMatches or
+    // Initialize: vbMatchesInliers (N flags) and H21 / F21 (9 floats) as FindHomography /
+    // FindFundamental gave them, K4 = fx, fy, cx, cy of mK.  On true R21 (9 floats), t21 (3), vP3D
+    // (3 floats per key of frame 1) and vbTriangulated are the reference's; on false R21 and t21
+    // are empty, as the reference's cv::Mat, and the two vectors are left as they were.
+    bool ReconstructH(const std::vector<bool>& vbMatchesInliers, const std::vector<float>& H21, const float* K4,
+                      std::vector<float>& R21, std::vector<float>& t21, std::vector<float>& vP3D,
+                      std::vector<bool>& vbTriangulated, float minParallax = 1.0f, int minTriangulated = 50) {
+        return reconstruct(1, vbMatchesInliers, H21, K4, R21, t21, vP3D, vbTriangulated, minParallax, minTriangulated);
+    }
+    bool ReconstructF(const std::vector<bool>& vbMatchesInliers, const std::vector<float>& F21, const float* K4,
+                      std::vector<float>& R21, std::vector<float>& t21, std::vector<float>& vP3D,
+                      std::vector<bool>& vbTriangulated, float minParallax = 1.0f, int minTriangulated = 50) {
+        return reconstruct(0, vbMatchesInliers, F21, K4, R21, t21, vP3D, vbTriangulated, minParallax, minTriangulated);
+    }
+    // Initialize (Initializer.cc:44-119) whole: the reference's signature plus the draws and K.
+    bool Initialize(const std::vector<orb_keypoint_t>& keys2, const std::vector<int>& vMatches12,
+                    const std::vector<int>& rand31, const float* K4, std::vector<float>& R21, std::vector<float>& t21,
+                    std::vector<float>& vP3D, std::vector<bool>& vbTriangulated) {
+        const TwoViewModels m = Initialize(keys2, vMatches12, rand31);
+        R21.clear();
+        t21.clear();
+        // (a model without a winner is empty in the reference and would throw inside Reconstruct*)
+        if (m.bUseH) return !m.H.empty() && ReconstructH(m.vbMatchesInliersH, m.H, K4, R21, t21, vP3D, vbTriangulated, 1.0f, 50);
+        return !m.F.empty() && ReconstructF(m.vbMatchesInliersF, m.F, K4, R21, t21, vP3D, vbTriangulated, 1.0f, 50);
+    }
+
     std::vector<std::pair<int, int> > mvMatches12;  // (index in frame 1, index in frame 2), as the reference's
     std::vector<orb_keypoint_t> mvKeys1, mvKeys2;
     float mSigma;
@@ -478,6 +505,31 @@ private:
         for (int i = 0; i < n; ++i) vbMatchesInliers[(size_t)i] = in[(size_t)i] != 0;
         if (best >= 0) M.assign(src.begin() + (size_t)best * 9, src.begin() + (size_t)best * 9 + 9);
         return best;
+    }
+    bool reconstruct(int use_h, const std::vector<bool>& vbMatchesInliers, const std::vector<float>& M21, const float* K4,
+                     std::vector<float>& R21, std::vector<float>& t21, std::vector<float>& vP3D,
+                     std::vector<bool>& vbTriangulated, float minParallax, int minTriangulated) {
+        if (M21.size() != 9) throw std::runtime_error("orb: the model must hold 9 floats");
+        if (vbMatchesInliers.size() != mvMatches12.size()) throw std::runtime_error("orb: vbMatchesInliers must have one entry per match");
+        const size_t n1 = mvKeys1.size();
+        std::vector<uint8_t> in(vbMatchesInliers.size() + 1, 0), tri(n1 + 1, 0);
+        for (size_t i = 0; i < vbMatchesInliers.size(); ++i) in[i] = vbMatchesInliers[i] ? 1 : 0;
+        std::vector<float> P(3 * n1 + 3, 0.0f);
+        float R[9], t[3];
+        int32_t ok = 0;
+        orb_check(orb_initializer_reconstruct(mvKeys1.data(), (int)n1, mvKeys2.data(), (int)mvKeys2.size(), matches12_.data(),
+                                              M21.data(), use_h, in.data(), K4, mSigma, minParallax, minTriangulated, &ok,
+                                              R, t, P.data(), tri.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, nullptr, device_));
+        R21.clear();
+        t21.clear();
+        if (!ok) return false;
+        R21.assign(R, R + 9);
+        t21.assign(t, t + 3);
+        vP3D.assign(P.begin(), P.begin() + 3 * n1);
+        vbTriangulated.assign(n1, false);
+        for (size_t i = 0; i < n1; ++i) vbTriangulated[i] = tri[i] != 0;
+        return true;
     }
     std::vector<int32_t> matches12_;
     int device_;

@@ -208,6 +208,12 @@ HIP_SIGNATURES = {
     "orb_initializer_compute_hypotheses": (_i, [_vp, _i, _vp, _i, _vp, _i] + [_vp] * 10 + [_pi, _i]),
     "orb_initializer_ransac": (_i, [_vp, _i, _vp, _i, _vp, _f, _i] + [_vp] * 17 + [_pi, _i]),
     "orb_initializer_ransac_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i] + [_vp] * 19),
+    "orb_initializer_reconstruct": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _f, _f, _i] + [_vp] * 13 + [_i]),
+    "orb_initializer_reconstruct_batch_device": (_i, [_vp, _vp, _i, _i] + [_vp] * 10 + [_f, _f, _i] + [_vp] * 14),
+    "orb_initializer_initialize": (_i, [_vp, _i, _vp, _i, _vp, _f, _i, _vp, _vp, _f, _i] + [_vp] * 16 + [_pi] +
+                                   [_vp] * 13 + [_i]),
+    "orb_initializer_initialize_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _f, _i] +
+                                                [_vp] * 31),
     "orb_pnp_check_inliers": (_i, [_i, _vp, _vp, _vp, _f, _d, _d, _d, _d, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "orb_sim3_check_inliers": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "orb_pnp_check_inliers_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _d, _d, _d, _d,

@@ -3,8 +3,9 @@
 // Initializer::CheckHomography (reference src/Initializer.cc:303-386) and CheckFundamental
 // (388-466) for every RANSAC hypothesis of a frame pair at once, plus the "keep the best" rule of
 // FindHomography / FindFundamental (146-169, 197-220).  In orb_initializer_check[_batch_device] the
-// hypotheses (ComputeH21 / ComputeF21, cv::SVDecomp) are the caller's; the second half of this file
-// generates them on the device and runs the same two kernels behind them.
+// hypotheses (ComputeH21 / ComputeF21, cv::SVDecomp) are the caller's; the second part of this file
+// generates them on the device and runs the same two kernels behind them, and the third goes on
+// from the winning model to ReconstructH / ReconstructF (CheckRT, Triangulate, DecomposeE).
 //
 // Arithmetic: plain float, the TU is built -ffp-contract=off and the fused multiply-adds that
 // g++ -O3 -march=native makes of the reference's expressions are written out
@@ -1306,6 +1307,838 @@ int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32
     o.use_h = d_use_h;
     return run_chain(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, sigma, n_hyp, d_rand31, nullptr, true, o,
                      nullptr, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ---- the reconstruction: ReconstructF / ReconstructH, CheckRT, Triangulate, DecomposeE ----------
+//
+// What Initializer::Initialize does with the winning model (Initializer.cc:113-116, 468-745,
+// 796-927); the CPU statement of the same reading is
+// tests/native/initializer_reconstruct_model.cpp, which shares no text with this file.  IEEE f32 /
+// f64 operations, the reference build's five fused multiply-adds written out, one libm call (acosf).
+//
+//   k_init_motion   one workgroup per pair: the matches in index order (frame-1 index of every
+//                   ordinal, N), the count of set mask entries, and on thread 0 the 4 (DecomposeE) or
+//                   8 (Faugeras) motion hypotheses of the model that use_h names.
+//   k_init_checkrt  one lane per (pair, hypothesis, match ordinal), workgroups of one wave:
+//                   Triangulate's 4 x 4 decomposition on the lane's column of LDS ([element][lane],
+//                   hy_jacobi of §16 on the transposed matrix, only vt.row(3) read) and every gate of
+//                   CheckRT; writes the counted / vbGood flags and the cosine.
+//   k_init_stat     one workgroup per (pair, hypothesis): nGood and sorted[min(50, nGood - 1)] of
+//                   the counted cosines by rank counting in LDS (a NaN ranks after every number),
+//                   then the parallax.
+//   k_init_select   one workgroup per pair: the acceptance rule on thread 0, then R21, t21 and the
+//                   winner's vP3D / vbTriangulated rows, its points recomputed with the same function.
+namespace {
+
+constexpr int RC_THREADS = 256;
+constexpr int RC_WAVE_BYTES = 32 * 64 * 4 + 4 * 64 * 8;  // At and Vt (4 x 4 floats each) and W (4 doubles) of 64 lanes
+constexpr double RC_PI = 3.1415926535897932384626433832795;  // CV_PI
+
+struct RecArgs {
+    const orb_keypoint_t* kps;
+    const int32_t* counts;
+    const int32_t* pair_f1;
+    const int32_t* pair_f2;
+    const int32_t* matches12;
+    const float* H21;          // P x 9 each: the winners
+    const float* F21;
+    const int32_t* use_h;      // P
+    const uint8_t* inl_h;      // P x cap, by match ordinal
+    const uint8_t* inl_f;
+    const int32_t* n_matches;  // P, or NULL: every match is walked
+    float fx, fy, cx, cy, th2, min_parallax;
+    int min_triangulated;
+    int32_t* ord_i;            // P x cap (scratch)
+    int32_t* nwalk;            // P (scratch)
+    uint8_t* flags;            // P x 8 x cap (scratch): bit 0 counted, bit 1 vbGood
+    float* cosv;               // P x 8 x cap (scratch)
+    int32_t* n_motion;         // P; none of the following is NULL in the kernels
+    float* motion_R;           // P x 72
+    float* motion_t;           // P x 24
+    int32_t* n_good;           // P x 8
+    float* cos_sel;            // P x 8
+    float* parallax;           // P x 8
+    int32_t* n_inliers;        // P
+    int32_t* best;             // P
+    int32_t* ok;               // P; this and the following may be NULL
+    float* R21;                // P x 9
+    float* t21;                // P x 3
+    float* P3D;                // P x cap x 3
+    uint8_t* triangulated;     // P x cap
+    int cap, P;
+};
+
+__device__ __forceinline__ PairView rec_view(const RecArgs& a, int p) {
+    InitArgs ia{};
+    ia.kps = a.kps;
+    ia.counts = a.counts;
+    ia.pair_f1 = a.pair_f1;
+    ia.pair_f2 = a.pair_f2;
+    ia.matches12 = a.matches12;
+    ia.cap = a.cap;
+    return pair_view(ia, p);
+}
+
+// cv::determinant of a 3 x 3 CV_32F (lapack.cpp's det3): a double
+__device__ __forceinline__ double rc_det3(const M3& s) {
+    const float* m = s.m;
+    return (double)m[0] * ((double)m[4] * (double)m[8] - (double)m[5] * (double)m[7]) -
+           (double)m[1] * ((double)m[3] * (double)m[8] - (double)m[5] * (double)m[6]) +
+           (double)m[2] * ((double)m[3] * (double)m[7] - (double)m[4] * (double)m[6]);
+}
+
+// gemm with a transpose flag: not the 2 <= len <= 4 path but GEMMSingleMul_<float, double>, one
+// double accumulator per element, k ascending
+template <bool TA, bool TB>
+__device__ __forceinline__ M3 rc_gemm_general(const M3& a, const M3& b) {
+    M3 d;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s0 = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                s0 += (double)(TA ? a.m[k * 3 + i] : a.m[i * 3 + k]) * (double)(TB ? b.m[j * 3 + k] : b.m[k * 3 + j]);
+            d.m[i * 3 + j] = (float)s0;
+        }
+    return d;
+}
+
+// (alpha*A)*B: gemm's short path with alpha, (float)((double)t * alpha)
+__device__ __forceinline__ M3 rc_mul3_alpha(const M3& a, const M3& b, double alpha) {
+    M3 d = hy_mul3(a, b);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) d.m[k] = (float)((double)d.m[k] * alpha);
+    return d;
+}
+
+// M / s, M *= s: convertTo with alpha, x * (float)alpha + (float)0
+__device__ __forceinline__ void rc_scale3(const float* x, double alpha, float* out) {
+    const float a = (float)alpha;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = x[k] * a + 0.0f;
+}
+
+__device__ __forceinline__ double rc_norm3(const float* v) {
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s += (double)v[k] * (double)v[k];
+    return __builtin_sqrt(s);
+}
+
+// -M of a Mat: subtract(Scalar(0), M)
+__device__ __forceinline__ M3 rc_neg(const M3& a) {
+    M3 d;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) d.m[k] = 0.0f - a.m[k];
+    return d;
+}
+
+// U * tp (3 x 3 by 3 x 1, the short path), then t / cv::norm(t)
+__device__ __forceinline__ void rc_unit_Ut(const M3& U, const float* tp, float* out) {
+    float t[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) t[r] = U.m[3 * r] * tp[0] + U.m[3 * r + 1] * tp[1] + U.m[3 * r + 2] * tp[2];
+    rc_scale3(t, 1. / rc_norm3(t), out);
+}
+
+// SVD::compute of a 3 x 3 on column 0 of the given LDS regions (the transpose path of §16)
+__device__ void rc_svd3(const M3& S, float* A3, float* Vq, double* W, M3* u, M3* vt, float* w) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) A3[(i * 3 + k) * 64] = S.m[k * 3 + i];
+    hy_jacobi<3, 3, 3, true>(A3, Vq, W);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            u->m[r * 3 + c] = A3[(c * 3 + r) * 64];
+            vt->m[r * 3 + c] = Vq[(r * 3 + c) * 64];
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) w[i] = (float)W[i * 64];
+}
+
+__device__ __forceinline__ void rc_store_motion(const RecArgs& a, int p, int k, const M3& R, const float* t) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.motion_R[(size_t)p * 72 + k * 9 + e] = R.m[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) a.motion_t[(size_t)p * 24 + k * 3 + e] = t[e];
+}
+
+__global__ void __launch_bounds__(RC_THREADS) k_init_motion(RecArgs a) {
+    __shared__ int s_wtot[RC_THREADS / 64];
+    __shared__ int s_cnt;
+    __shared__ float s_a[9 * 64], s_v[9 * 64];
+    __shared__ double s_w[3 * 64];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const PairView v = rec_view(a, p);
+    const bool use_h = a.use_h[p] != 0;
+    if (tid == 0) s_cnt = 0;
+    int32_t* ord = a.ord_i + (size_t)p * a.cap;
+    const int N = compact_matches<RC_THREADS>(v, s_wtot, [&](int o, int i, int) { ord[o] = i; });
+    const int Nw = a.n_matches ? min(N, max(a.n_matches[p], 0)) : N;
+    const uint8_t* mask = (use_h ? a.inl_h : a.inl_f) + (size_t)p * a.cap;
+    int c = 0;
+    for (int o = tid; o < Nw; o += RC_THREADS) c += mask[o] != 0;
+    if (c) atomicAdd(&s_cnt, c);
+    __syncthreads();
+    if (tid != 0) return;
+    a.nwalk[p] = Nw;
+    a.n_inliers[p] = s_cnt;
+    for (int e = 0; e < 72; ++e) a.motion_R[(size_t)p * 72 + e] = 0.0f;
+    for (int e = 0; e < 24; ++e) a.motion_t[(size_t)p * 24 + e] = 0.0f;
+    M3 K, M;
+    {
+        const float k[9] = {a.fx, 0.0f, a.cx, 0.0f, a.fy, a.cy, 0.0f, 0.0f, 1.0f};
+        const float* src = (use_h ? a.H21 : a.F21) + (size_t)p * 9;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+            K.m[e] = k[e];
+            M.m[e] = src[e];
+        }
+    }
+    M3 U, Vt;
+    float w[3];
+    if (!use_h) {
+        // ReconstructF: E21 = K.t()*F21*K (the first product carries GEMM_1_T), DecomposeE
+        const M3 E = hy_mul3(rc_gemm_general<true, false>(K, M), K);
+        rc_svd3(E, s_a, s_v, s_w, &U, &Vt, w);
+        const float col[3] = {U.m[2], U.m[5], U.m[8]};
+        float t1[3], t2[3];
+        rc_scale3(col, 1. / rc_norm3(col), t1);  // t = t/cv::norm(t)
+        M3 W;
+        {
+            const float wm[9] = {0.0f, -1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+#pragma unroll
+            for (int e = 0; e < 9; ++e) W.m[e] = wm[e];
+        }
+        M3 R1 = hy_mul3(hy_mul3(U, W), Vt);
+        if (rc_det3(R1) < 0) R1 = rc_neg(R1);
+        M3 R2 = hy_mul3(rc_gemm_general<false, true>(U, W), Vt);  // u*W.t()*vt: GEMM_2_T
+        if (rc_det3(R2) < 0) R2 = rc_neg(R2);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) t2[e] = 0.0f - t1[e];
+        rc_store_motion(a, p, 0, R1, t1);
+        rc_store_motion(a, p, 1, R2, t1);
+        rc_store_motion(a, p, 2, R1, t2);
+        rc_store_motion(a, p, 3, R2, t2);
+        a.n_motion[p] = 4;
+        return;
+    }
+    // ReconstructH (Faugeras); vn is computed by the reference and never read: skipped
+    const M3 A = hy_mul3(hy_mul3(hy_inv3(K), M), K);
+    rc_svd3(A, s_a, s_v, s_w, &U, &Vt, w);
+    const float s = (float)(rc_det3(U) * rc_det3(Vt));
+    const float d1 = w[0], d2 = w[1], d3 = w[2];
+    if ((double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001) {
+        a.n_motion[p] = 0;
+        return;
+    }
+    const float d22 = d2 * d2, d33 = d3 * d3, d13 = d1 * d3;
+    const float n12 = __builtin_fmaf(d1, d1, -d22), n13 = __builtin_fmaf(d1, d1, -d33), n23 = d22 - d33;
+    const float aux1 = __builtin_sqrtf(n12 / n13);
+    const float aux3 = __builtin_sqrtf(n23 / n13);
+    const float root = __builtin_sqrtf(n12 * n23);
+    const float aux_stheta = root / ((d1 + d3) * d2);
+    const float ctheta = (d22 + d13) / ((d1 + d3) * d2);
+    const float aux_sphi = root / ((d1 - d3) * d2);
+    const float cphi = (d13 - d22) / ((d1 - d3) * d2);
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        const float x1 = i < 2 ? aux1 : -aux1;
+        const float x3 = (i & 1) ? -aux3 : aux3;
+        const float st = (i == 0 || i == 3) ? aux_stheta : -aux_stheta;
+        const float sp = (i == 0 || i == 3) ? aux_sphi : -aux_sphi;
+        M3 Rp;
+        float tp[3], t[3];
+        {
+            const float r[9] = {ctheta, 0.0f, -st, 0.0f, 1.0f, 0.0f, st, 0.0f, ctheta};
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Rp.m[e] = r[e];
+        }
+        tp[0] = x1, tp[1] = 0.0f, tp[2] = -x3;
+        rc_scale3(tp, (double)(d1 - d3), tp);  // tp *= d1-d3
+        rc_unit_Ut(U, tp, t);
+        rc_store_motion(a, p, i, hy_mul3(rc_mul3_alpha(U, Rp, (double)s), Vt), t);  // s*U*Rp*Vt
+        {
+            const float r[9] = {cphi, 0.0f, sp, 0.0f, -1.0f, 0.0f, sp, 0.0f, -cphi};
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Rp.m[e] = r[e];
+        }
+        tp[0] = x1, tp[1] = 0.0f, tp[2] = x3;
+        rc_scale3(tp, (double)(d1 + d3), tp);  // tp *= d1+d3
+        rc_unit_Ut(U, tp, t);
+        rc_store_motion(a, p, 4 + i, hy_mul3(rc_mul3_alpha(U, Rp, (double)s), Vt), t);
+    }
+    a.n_motion[p] = 8;
+}
+
+// What CheckRT prepares once per call: P2 = K*[R|t] and O2 = -R.t()*t
+struct RcPose {
+    float R[9], t[3], P2[12], O2[3];
+};
+
+__device__ __forceinline__ RcPose rc_pose(const RecArgs& a, int p, int h) {
+    RcPose q;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) q.R[e] = a.motion_R[(size_t)p * 72 + h * 9 + e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) q.t[e] = a.motion_t[(size_t)p * 24 + h * 3 + e];
+    const float K[9] = {a.fx, 0.0f, a.cx, 0.0f, a.fy, a.cy, 0.0f, 0.0f, 1.0f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {  // the short path, 3 x 3 by 3 x 4; K's zeros are not skipped (0 * inf)
+            const float b0 = j < 3 ? q.R[j] : q.t[0], b1 = j < 3 ? q.R[3 + j] : q.t[1], b2 = j < 3 ? q.R[6 + j] : q.t[2];
+            q.P2[i * 4 + j] = K[3 * i] * b0 + K[3 * i + 1] * b1 + K[3 * i + 2] * b2;
+        }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // one gemm, GEMM_1_T, alpha = -1
+        double s0 = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s0 += (double)q.R[k * 3 + i] * (double)q.t[k];
+        q.O2[i] = (float)(s0 * -1.0);
+    }
+    return q;
+}
+
+// One match of CheckRT (Initializer.cc:830-891) on the lane's LDS column.  Returns bit 0: counted
+// (nGood, vCosParallax, vP3D), bit 1: vbGood.
+__device__ int rc_check_one(const RecArgs& a, const RcPose& q, float x1, float y1, float x2, float y2, float* At,
+                            float* Vt, double* W, float* cosp, float* pt) {
+    // Triangulate: A.row(r) = x*P.row(2) - P.row(r & 1) is addWeighted_<float, double>(a, x, b, -1, 0)
+    const float P1[12] = {a.fx, 0.0f, a.cx, 0.0f, 0.0f, a.fy, a.cy, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+    const float xs[4] = {x1, y1, x2, y2};
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float* P = r < 2 ? P1 : q.P2;
+            const float e = (float)((double)P[8 + j] * (double)xs[r] + (double)P[(r & 1) * 4 + j] * -1.0 + 0.0);
+            At[(j * 4 + r) * 64] = e;  // the work matrix is the transpose
+        }
+    hy_jacobi<4, 4, 0, true>(At, Vt, W);
+    float vr[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) vr[k] = Vt[(12 + k) * 64];  // vt.row(3)
+    float p3[3];
+    rc_scale3(vr, 1. / (double)vr[3], p3);  // rowRange(0,3)/x3D.at<float>(3): a MatExpr scale
+    if (!__builtin_isfinite(p3[0]) || !__builtin_isfinite(p3[1]) || !__builtin_isfinite(p3[2])) return 0;
+    float n1[3], n2[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        n1[k] = p3[k] - 0.0f;  // O1
+        n2[k] = p3[k] - q.O2[k];
+    }
+    const float dist1 = (float)rc_norm3(n1);
+    const float dist2 = (float)rc_norm3(n2);
+    double dot = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dot += (double)n1[k] * (double)n2[k];
+    const float cosParallax = (float)(dot / (double)(dist1 * dist2));
+    const bool low = (double)cosParallax < 0.99998;
+    if (p3[2] <= 0.0f && low) return 0;
+    float p2[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // R*p3dC1+t: gemm(R, p, 1, t, 1), the short path
+        const float ti = q.R[3 * i] * p3[0] + q.R[3 * i + 1] * p3[1] + q.R[3 * i + 2] * p3[2];
+        p2[i] = (float)((double)ti * 1.0 + (double)q.t[i] * 1.0);
+    }
+    if (p2[2] <= 0.0f && low) return 0;
+    const float invZ1 = (float)(1.0 / (double)p3[2]);
+    const float im1x = __builtin_fmaf(a.fx * p3[0], invZ1, a.cx);
+    const float im1y = __builtin_fmaf(a.fy * p3[1], invZ1, a.cy);
+    const float e1 = __builtin_fmaf(im1x - x1, im1x - x1, (im1y - y1) * (im1y - y1));
+    if (e1 > a.th2) return 0;
+    const float invZ2 = (float)(1.0 / (double)p2[2]);
+    const float im2x = __builtin_fmaf(a.fx * p2[0], invZ2, a.cx);
+    const float im2y = __builtin_fmaf(a.fy * p2[1], invZ2, a.cy);
+    const float e2 = __builtin_fmaf(im2x - x2, im2x - x2, (im2y - y2) * (im2y - y2));
+    if (e2 > a.th2) return 0;
+    *cosp = cosParallax;
+    pt[0] = p3[0], pt[1] = p3[1], pt[2] = p3[2];
+    return low ? 3 : 1;
+}
+
+__global__ void __launch_bounds__(64) k_init_checkrt(RecArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[RC_WAVE_BYTES];
+    const int p = blockIdx.z, h = blockIdx.y, lane = threadIdx.x;
+    const int o = blockIdx.x * 64 + lane;
+    if (h >= a.n_motion[p] || o >= a.nwalk[p]) return;  // (no barrier below: every lane works on its own column)
+    const size_t row = ((size_t)p * 8 + h) * a.cap;
+    const uint8_t* mask = (a.use_h[p] != 0 ? a.inl_h : a.inl_f) + (size_t)p * a.cap;
+    int fl = 0;
+    float cs = 0.0f;
+    if (mask[o] != 0) {
+        const PairView v = rec_view(a, p);
+        const int i = a.ord_i[(size_t)p * a.cap + o];
+        const int m = v.m12[i];
+        const RcPose q = rc_pose(a, p, h);
+        float pt[3];
+        fl = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, (float*)smem + lane,
+                          (float*)smem + 16 * 64 + lane, (double*)(smem + 32 * 64 * 4) + lane, &cs, pt);
+    }
+    a.flags[row + o] = (uint8_t)fl;
+    a.cosv[row + o] = cs;
+}
+
+__global__ void __launch_bounds__(RC_THREADS) k_init_stat(RecArgs a) {
+    __shared__ float s_c[IN_MAX_CAP];
+    __shared__ int s_n;
+    const int h = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
+    const size_t g = (size_t)p * 8 + h;
+    if (h >= a.n_motion[p]) {
+        if (tid == 0) {
+            a.n_good[g] = 0;
+            a.cos_sel[g] = __builtin_nanf("");
+            a.parallax[g] = 0.0f;
+        }
+        return;
+    }
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const int Nw = a.nwalk[p];
+    for (int o = tid; o < Nw; o += RC_THREADS)
+        if (a.flags[g * a.cap + o] & 1) s_c[atomicAdd(&s_n, 1)] = a.cosv[g * a.cap + o];
+    __syncthreads();
+    const int nGood = s_n;
+    if (nGood == 0) {
+        if (tid == 0) {
+            a.n_good[g] = 0;
+            a.cos_sel[g] = __builtin_nanf("");
+            a.parallax[g] = 0.0f;
+        }
+        return;
+    }
+    // sorted[min(50, size - 1)]: the element with exactly that many before it, where "before" is a
+    // smaller value, a number before a NaN, or an equal value in a lower slot
+    const int idx = min(50, nGood - 1);
+    for (int e = tid; e < nGood; e += RC_THREADS) {
+        const float ce = s_c[e];
+        const bool en = ce != ce;
+        int rank = 0;
+        for (int j = 0; j < nGood; ++j) {
+            const float cj = s_c[j];
+            const bool jn = cj != cj;
+            const bool before = cj < ce || (en && !jn) || ((cj == ce || (en && jn)) && j < e);
+            rank += before;
+        }
+        if (rank == idx) {
+            a.n_good[g] = nGood;
+            a.cos_sel[g] = ce;
+            // acos(float) is acosf; * 180 in float; / CV_PI in double; narrowed
+            a.parallax[g] = (float)((double)(acosf(ce) * 180.0f) / RC_PI);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(RC_THREADS) k_init_select(RecArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t smem[(RC_THREADS / 64) * RC_WAVE_BYTES];
+    __shared__ int s_best;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nm = a.n_motion[p];
+    if (tid == 0) {
+        const int32_t* ng = a.n_good + (size_t)p * 8;
+        const float* par = a.parallax + (size_t)p * 8;
+        const int N = a.n_inliers[p];
+        int b = -1;
+        if (nm == 4) {  // ReconstructF (Initializer.cc:497-567)
+            const int maxGood = max(ng[0], max(ng[1], max(ng[2], ng[3])));
+            const int nMinGood = max((int)(0.9 * (double)N), a.min_triangulated);
+            int nsimilar = 0;
+            for (int k = 0; k < 4; ++k) nsimilar += (double)ng[k] > 0.7 * (double)maxGood;
+            if (!(maxGood < nMinGood || nsimilar > 1))
+                for (int k = 0; k < 4; ++k)
+                    if (ng[k] == maxGood) {  // the else-if chain: the first one decides alone
+                        if (par[k] > a.min_parallax) b = k;
+                        break;
+                    }
+        } else if (nm == 8) {  // ReconstructH (687-729)
+            int bestGood = 0, secondBestGood = 0, bestIdx = -1;
+            float bestParallax = -1.0f;
+            for (int k = 0; k < 8; ++k) {
+                if (ng[k] > bestGood) {
+                    secondBestGood = bestGood;
+                    bestGood = ng[k];
+                    bestIdx = k;
+                    bestParallax = par[k];
+                } else if (ng[k] > secondBestGood)
+                    secondBestGood = ng[k];
+            }
+            if ((double)secondBestGood < 0.75 * (double)bestGood && bestParallax >= a.min_parallax &&
+                bestGood > a.min_triangulated && (double)bestGood > 0.9 * (double)N)
+                b = bestIdx;
+        }
+        s_best = b;
+        a.best[p] = b;
+        if (a.ok) a.ok[p] = b >= 0;
+        if (a.R21)
+            for (int e = 0; e < 9; ++e) a.R21[(size_t)p * 9 + e] = b >= 0 ? a.motion_R[(size_t)p * 72 + b * 9 + e] : 0.0f;
+        if (a.t21)
+            for (int e = 0; e < 3; ++e) a.t21[(size_t)p * 3 + e] = b >= 0 ? a.motion_t[(size_t)p * 24 + b * 3 + e] : 0.0f;
+    }
+    float* P3D = a.P3D ? a.P3D + (size_t)p * a.cap * 3 : nullptr;
+    uint8_t* tri = a.triangulated ? a.triangulated + (size_t)p * a.cap : nullptr;
+    for (int i = tid; i < a.cap; i += RC_THREADS) {
+        if (P3D) P3D[3 * i] = P3D[3 * i + 1] = P3D[3 * i + 2] = 0.0f;
+        if (tri) tri[i] = 0;
+    }
+    __syncthreads();
+    const int b = s_best;
+    if (b < 0 || (!P3D && !tri)) return;
+    // vP3D / vbTriangulated of the winner, indexed by the frame-1 keypoint: the counted ordinals'
+    // points again, by the function that counted them
+    const PairView v = rec_view(a, p);
+    const RcPose q = rc_pose(a, p, b);
+    const uint8_t* fl = a.flags + ((size_t)p * 8 + b) * a.cap;
+    uint8_t* sm = smem + wave * RC_WAVE_BYTES;
+    const int Nw = a.nwalk[p];
+    for (int o = tid; o < Nw; o += RC_THREADS) {
+        if (!(fl[o] & 1)) continue;
+        const int i = a.ord_i[(size_t)p * a.cap + o];
+        const int m = v.m12[i];
+        float cs, pt[3] = {0.0f, 0.0f, 0.0f};
+        const int f = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, (float*)sm + lane,
+                                   (float*)sm + 16 * 64 + lane, (double*)(sm + 32 * 64 * 4) + lane, &cs, pt);
+        if (P3D) P3D[3 * i] = pt[0], P3D[3 * i + 1] = pt[1], P3D[3 * i + 2] = pt[2];
+        if (tri) tri[i] = (f & 2) ? 1 : 0;
+    }
+}
+
+struct RecOut {
+    int32_t* ok;
+    float *R21, *t21, *P3D;
+    uint8_t* triangulated;
+    int32_t* n_motion;
+    float *motion_R, *motion_t;
+    int32_t* n_good;
+    float *cos_parallax, *parallax_deg;
+    int32_t *best, *n_inliers;
+};
+
+// What one reconstruct call holds in scratch at most (every optional output absent).
+size_t rec_scratch_bytes(int P, int cap) {
+    const size_t pc = (size_t)P * cap;
+    return orb_align256(pc * 4) + orb_align256((size_t)P * 4) + orb_align256(pc * 8) + orb_align256(pc * 8 * 4) +
+           3 * orb_align256((size_t)P * 4) + orb_align256((size_t)P * 72 * 4) + orb_align256((size_t)P * 24 * 4) +
+           3 * orb_align256((size_t)P * 8 * 4);
+}
+
+int check_rec_params(const std::string& w, const float* K4, float sigma, float min_parallax, int min_triangulated) {
+    if (!K4) return fail(ORB_EINVAL, w + "K4 is NULL");
+    if (int r = orb_check_camera(w.substr(0, w.size() - 2).c_str(), "", K4)) return r;
+    if (!std::isfinite(sigma) || sigma == 0.0f)
+        return fail(ORB_EINVAL, w + "sigma = " + std::to_string(sigma) + " must be finite and not 0");
+    if (!std::isfinite(min_parallax))
+        return fail(ORB_EINVAL, w + "min_parallax = " + std::to_string(min_parallax) + " must be finite");
+    if (min_triangulated < 0)
+        return fail(ORB_EINVAL, w + "min_triangulated = " + std::to_string(min_triangulated) + " is negative");
+    return ORB_OK;
+}
+
+// k_init_motion -> k_init_checkrt -> k_init_stat -> k_init_select, enqueued on `st`.  `scratch`:
+// rec_scratch_bytes() of device memory, or NULL for a stream-ordered allocation freed after the
+// last kernel.
+int run_reconstruct(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
+                    const int32_t* d_pair_f2, const int32_t* d_matches12, const float* d_H21, const float* d_F21,
+                    const int32_t* d_use_h, const uint8_t* d_inl_h, const uint8_t* d_inl_f, const int32_t* d_n_matches,
+                    const float* K4, float sigma, float min_parallax, int min_triangulated, const RecOut& o,
+                    uint8_t* scratch, hipStream_t st) {
+    void* owned = nullptr;
+    if (!scratch) {
+        hipError_t e = hipMallocAsync(&owned, rec_scratch_bytes(P, cap), st);
+        if (e != hipSuccess)
+            return fail(ORB_ENOMEM, std::string("initializer reconstruct: scratch: ") + hipGetErrorString(e));
+        scratch = (uint8_t*)owned;
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* r = scratch + off;
+        off += orb_align256(bytes);
+        return r;
+    };
+    const size_t pc = (size_t)P * cap;
+    RecArgs a{};
+    a.kps = d_kps;
+    a.counts = d_counts;
+    a.pair_f1 = d_pair_f1;
+    a.pair_f2 = d_pair_f2;
+    a.matches12 = d_matches12;
+    a.H21 = d_H21;
+    a.F21 = d_F21;
+    a.use_h = d_use_h;
+    a.inl_h = d_inl_h;
+    a.inl_f = d_inl_f;
+    a.n_matches = d_n_matches;
+    a.fx = K4[0];
+    a.fy = K4[1];
+    a.cx = K4[2];
+    a.cy = K4[3];
+    const float sigma2 = sigma * sigma;  // mSigma2
+    a.th2 = (float)(4.0 * (double)sigma2);  // 4.0*mSigma2, narrowed at the call
+    a.min_parallax = min_parallax;
+    a.min_triangulated = min_triangulated;
+    a.ord_i = (int32_t*)take(pc * 4);
+    a.nwalk = (int32_t*)take((size_t)P * 4);
+    a.flags = take(pc * 8);
+    a.cosv = (float*)take(pc * 8 * 4);
+    a.n_motion = o.n_motion ? o.n_motion : (int32_t*)take((size_t)P * 4);
+    a.n_inliers = o.n_inliers ? o.n_inliers : (int32_t*)take((size_t)P * 4);
+    a.best = o.best ? o.best : (int32_t*)take((size_t)P * 4);
+    a.motion_R = o.motion_R ? o.motion_R : (float*)take((size_t)P * 72 * 4);
+    a.motion_t = o.motion_t ? o.motion_t : (float*)take((size_t)P * 24 * 4);
+    a.n_good = o.n_good ? o.n_good : (int32_t*)take((size_t)P * 8 * 4);
+    a.cos_sel = o.cos_parallax ? o.cos_parallax : (float*)take((size_t)P * 8 * 4);
+    a.parallax = o.parallax_deg ? o.parallax_deg : (float*)take((size_t)P * 8 * 4);
+    a.ok = o.ok;
+    a.R21 = o.R21;
+    a.t21 = o.t21;
+    a.P3D = o.P3D;
+    a.triangulated = o.triangulated;
+    a.cap = cap;
+    a.P = P;
+    hipError_t e = hipSuccess;
+    hipLaunchKernelGGL(k_init_motion, dim3(P), dim3(RC_THREADS), 0, st, a);
+    if ((e = hipGetLastError()) == hipSuccess) {
+        hipLaunchKernelGGL(k_init_checkrt, dim3((cap + 63) / 64, 8, P), dim3(64), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_init_stat, dim3(8, P), dim3(RC_THREADS), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_init_select, dim3(P), dim3(RC_THREADS), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (owned) (void)hipFreeAsync(owned, st);
+    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("initializer reconstruct: ") + hipGetErrorString(e));
+    return ORB_OK;
+}
+
+int check_batch_args(const std::string& w, int cap, int P) {
+    if (P < 0 || cap <= 0) return fail(ORB_EINVAL, w + "bad arguments");
+    if (cap > IN_MAX_CAP) return fail(ORB_ENOTSUP, w + "more than 8192 keypoints per frame");
+    if (P > 65535) return fail(ORB_ENOTSUP, w + "more than 65535 pairs per call");
+    return ORB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orb_initializer_reconstruct_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                             const int32_t* d_pair_f1, const int32_t* d_pair_f2,
+                                             const int32_t* d_matches12, const float* d_best_H21,
+                                             const float* d_best_F21, const int32_t* d_use_h,
+                                             const uint8_t* d_inliers_h, const uint8_t* d_inliers_f,
+                                             const int32_t* d_n_matches, const float* K4, float sigma,
+                                             float min_parallax, int min_triangulated, int32_t* d_ok, float* d_R21,
+                                             float* d_t21, float* d_P3D, uint8_t* d_triangulated, int32_t* d_n_motion,
+                                             float* d_motion_R, float* d_motion_t, int32_t* d_n_good,
+                                             float* d_cos_parallax, float* d_parallax_deg, int32_t* d_best,
+                                             int32_t* d_n_inliers, void* stream) {
+    const std::string w = "initializer reconstruct: ";
+    if (int r = check_batch_args(w, cap, P)) return r;
+    if (int r = check_rec_params(w, K4, sigma, min_parallax, min_triangulated)) return r;
+    if (P == 0) return ORB_OK;
+    if (!d_kps || !d_counts || !d_pair_f1 || !d_pair_f2 || !d_matches12 || !d_best_H21 || !d_best_F21 || !d_use_h ||
+        !d_inliers_h || !d_inliers_f)
+        return fail(ORB_EINVAL, w + "bad arguments");
+    const RecOut o{d_ok, d_R21, d_t21, d_P3D, d_triangulated, d_n_motion, d_motion_R, d_motion_t,
+                   d_n_good, d_cos_parallax, d_parallax_deg, d_best, d_n_inliers};
+    return run_reconstruct(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, d_best_H21, d_best_F21, d_use_h,
+                           d_inliers_h, d_inliers_f, d_n_matches, K4, sigma, min_parallax, min_triangulated, o, nullptr,
+                           (hipStream_t)stream);
+}
+
+int orb_initializer_reconstruct(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                                const int32_t* matches12, const float* M21, int use_h, const uint8_t* inliers,
+                                const float* K4, float sigma, float min_parallax, int min_triangulated, int32_t* ok,
+                                float* R21, float* t21, float* P3D, uint8_t* triangulated, int32_t* n_motion,
+                                float* motion_R, float* motion_t, int32_t* n_good, float* cos_parallax,
+                                float* parallax_deg, int32_t* best, int32_t* n_inliers, int device) {
+    const std::string w = "initializer reconstruct: ";
+    if (n1 < 0 || n2 < 0 || (n1 && (!kps1 || !matches12)) || (n2 && !kps2)) return fail(ORB_EINVAL, w + "bad arguments");
+    if (!M21) return fail(ORB_EINVAL, w + "M21 is NULL");
+    if (use_h != 0 && use_h != 1) return fail(ORB_EINVAL, w + "use_h = " + std::to_string(use_h) + " is not 0 or 1");
+    const int cap = std::max(std::max(n1, n2), 1);
+    if (cap > IN_MAX_CAP) return fail(ORB_ENOTSUP, w + "more than 8192 keypoints per frame");
+    if (int r = check_rec_params(w, K4, sigma, min_parallax, min_triangulated)) return r;
+    int N = 0;
+    for (int i = 0; i < n1; ++i) {
+        if (matches12[i] < -1 || matches12[i] >= n2)
+            return fail(ORB_EINVAL, w + "matches12[" + std::to_string(i) + "] = " + std::to_string(matches12[i]) +
+                                        " is outside [-1, n2)");
+        N += matches12[i] >= 0;
+    }
+    if (N && !inliers) return fail(ORB_EINVAL, w + "inliers is NULL");
+    for (int k = 0; k < N; ++k)
+        if (inliers[k] > 1)
+            return fail(ORB_EINVAL, w + "inliers[" + std::to_string(k) + "] = " + std::to_string((int)inliers[k]) +
+                                        " is not 0 or 1");
+    int ndev = 0;
+    ORB_HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
+    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
+    ORB_HIPCHK(hipSetDevice(device));
+    // in:  [kps 2 x cap | counts 2, f1, f2, use_h | matches12 cap | model 9 | mask cap]
+    // out: [ok, best, n_motion, n_inliers | R21 9, t21 3 | motion_R 72 | motion_t 24 | n_good 8 | cos 8 |
+    //       parallax 8 | P3D cap x 3 | triangulated cap]      then the chain's scratch (device only)
+    auto al = orb_align256;
+    const size_t oK = 0, oC = al(oK + 2 * (size_t)cap * sizeof(orb_keypoint_t)), oM = al(oC + 20),
+                 oMod = al(oM + (size_t)cap * 4), oI = al(oMod + 36), in_end = al(oI + (size_t)cap);
+    const size_t oS = in_end, oR = al(oS + 16), oMR = al(oR + 48), oMT = al(oMR + 288), oG = al(oMT + 96),
+                 oCs = al(oG + 32), oPa = al(oCs + 32), oP = al(oPa + 32), oT = al(oP + (size_t)cap * 12),
+                 out_end = al(oT + (size_t)cap);
+    if (int r = C->reserve(out_end + rec_scratch_bytes(1, cap), out_end)) return r;
+    uint8_t* hp = C->pinned;
+    std::memset(hp, 0, in_end);
+    if (n1) std::memcpy(hp + oK, kps1, (size_t)n1 * sizeof(orb_keypoint_t));
+    if (n2) std::memcpy(hp + oK + (size_t)cap * sizeof(orb_keypoint_t), kps2, (size_t)n2 * sizeof(orb_keypoint_t));
+    const int32_t hdr[5] = {n1, n2, 0, 1, use_h};
+    std::memcpy(hp + oC, hdr, 20);
+    int32_t* hm = (int32_t*)(hp + oM);
+    for (int i = 0; i < cap; ++i) hm[i] = i < n1 ? matches12[i] : -1;
+    std::memcpy(hp + oMod, M21, 36);
+    if (N) std::memcpy(hp + oI, inliers, (size_t)N);
+    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+    uint8_t* d = C->buf;
+    const int32_t* dc = (const int32_t*)(d + oC);
+    int32_t* ds = (int32_t*)(d + oS);
+    const RecOut o{ds, (float*)(d + oR), (float*)(d + oR) + 9, (float*)(d + oP), d + oT, ds + 2, (float*)(d + oMR),
+                   (float*)(d + oMT), (int32_t*)(d + oG), (float*)(d + oCs), (float*)(d + oPa), ds + 1, ds + 3};
+    // the one model and the one mask serve whichever use_h names
+    const int r = run_reconstruct((const orb_keypoint_t*)(d + oK), dc, cap, 1, dc + 2, dc + 3, (const int32_t*)(d + oM),
+                                  (const float*)(d + oMod), (const float*)(d + oMod), dc + 4, d + oI, d + oI, nullptr, K4,
+                                  sigma, min_parallax, min_triangulated, o, d + out_end, C->stream);
+    hipError_t e = hipSuccess;
+    if (r == ORB_OK) e = hipMemcpyAsync(hp + oS, d + oS, out_end - oS, hipMemcpyDeviceToHost, C->stream);
+    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
+    if (r) return r;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ORB_EDEVICE, w + hipGetErrorString(e));
+    const int32_t* hs = (const int32_t*)(hp + oS);
+    if (ok) *ok = hs[0];
+    if (best) *best = hs[1];
+    if (n_motion) *n_motion = hs[2];
+    if (n_inliers) *n_inliers = hs[3];
+    if (R21) std::memcpy(R21, hp + oR, 36);
+    if (t21) std::memcpy(t21, hp + oR + 36, 12);
+    if (motion_R) std::memcpy(motion_R, hp + oMR, 288);
+    if (motion_t) std::memcpy(motion_t, hp + oMT, 96);
+    if (n_good) std::memcpy(n_good, hp + oG, 32);
+    if (cos_parallax) std::memcpy(cos_parallax, hp + oCs, 32);
+    if (parallax_deg) std::memcpy(parallax_deg, hp + oPa, 32);
+    if (P3D && n1) std::memcpy(P3D, hp + oP, (size_t)n1 * 12);
+    if (triangulated && n1) std::memcpy(triangulated, hp + oT, (size_t)n1);
+    return ORB_OK;
+}
+
+int orb_initializer_initialize(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+                               const int32_t* matches12, float sigma, int n_hyp, const int32_t* rand31, const float* K4,
+                               float min_parallax, int min_triangulated, float* H21, float* H12, float* F21,
+                               int32_t* sets_out, float* scores_h, float* scores_f, int32_t* best_h,
+                               float* best_score_h, uint8_t* inliers_h, int32_t* best_f, float* best_score_f,
+                               uint8_t* inliers_f, float* best_H21, float* best_F21, float* RH, int32_t* use_h,
+                               int* n_matches, int32_t* ok, float* R21, float* t21, float* P3D, uint8_t* triangulated,
+                               int32_t* n_motion, float* motion_R, float* motion_t, int32_t* n_good,
+                               float* cos_parallax, float* parallax_deg, int32_t* best, int32_t* n_inliers,
+                               int device) {
+    if (int r = check_rec_params("initializer initialize: ", K4, sigma, min_parallax, min_triangulated)) return r;
+    // the model, the mask and use_h pass through the host between the two chains (the batch form
+    // keeps them on the device)
+    std::vector<uint8_t> ih, jf;
+    float bH[9], bF[9];
+    int32_t uh = 0;
+    if (!inliers_h) {
+        ih.resize((size_t)std::max(n1, 1));
+        inliers_h = ih.data();
+    }
+    if (!inliers_f) {
+        jf.resize((size_t)std::max(n1, 1));
+        inliers_f = jf.data();
+    }
+    if (int r = orb_initializer_ransac(kps1, n1, kps2, n2, matches12, sigma, n_hyp, rand31, H21, H12, F21, sets_out,
+                                       scores_h, scores_f, best_h, best_score_h, inliers_h, best_f, best_score_f,
+                                       inliers_f, bH, bF, RH, &uh, n_matches, device))
+        return r;
+    if (best_H21) std::memcpy(best_H21, bH, 36);
+    if (best_F21) std::memcpy(best_F21, bF, 36);
+    if (use_h) *use_h = uh;
+    return orb_initializer_reconstruct(kps1, n1, kps2, n2, matches12, uh ? bH : bF, uh, uh ? inliers_h : inliers_f, K4,
+                                       sigma, min_parallax, min_triangulated, ok, R21, t21, P3D, triangulated, n_motion,
+                                       motion_R, motion_t, n_good, cos_parallax, parallax_deg, best, n_inliers, device);
+}
+
+int orb_initializer_initialize_batch_device(
+    const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
+    const int32_t* d_pair_f2, const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
+    const float* K4, float min_parallax, int min_triangulated, float* d_H21, float* d_H12, float* d_F21,
+    int32_t* d_sets_out, float* d_scores_h, float* d_scores_f, int32_t* d_best_h, float* d_best_score_h,
+    uint8_t* d_inliers_h, int32_t* d_best_f, float* d_best_score_f, uint8_t* d_inliers_f, int32_t* d_n_matches,
+    float* d_best_H21, float* d_best_F21, float* d_RH, int32_t* d_use_h, int32_t* d_ok, float* d_R21, float* d_t21,
+    float* d_P3D, uint8_t* d_triangulated, int32_t* d_n_motion, float* d_motion_R, float* d_motion_t,
+    int32_t* d_n_good, float* d_cos_parallax, float* d_parallax_deg, int32_t* d_best, int32_t* d_n_inliers,
+    void* stream) {
+    const std::string w = "initializer initialize: ";
+    if (int r = check_batch_args(w, cap, P)) return r;
+    if (int r = check_limits(cap, n_hyp, true, true)) return r;
+    if (int r = check_rec_params(w, K4, sigma, min_parallax, min_triangulated)) return r;
+    if (P == 0) return ORB_OK;
+    if (!d_kps || !d_counts || !d_pair_f1 || !d_pair_f2 || !d_matches12 || !d_rand31)
+        return fail(ORB_EINVAL, w + "bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    // what passes from the first chain to the second and the caller did not ask for
+    const size_t pc = orb_align256((size_t)P * cap), p9 = orb_align256((size_t)P * 36), p1 = orb_align256((size_t)P * 4);
+    void* link = nullptr;
+    const size_t need = (d_inliers_h ? 0 : pc) + (d_inliers_f ? 0 : pc) + (d_best_H21 ? 0 : p9) +
+                        (d_best_F21 ? 0 : p9) + (d_use_h ? 0 : p1) + (d_n_matches ? 0 : p1);
+    if (need) {
+        hipError_t e = hipMallocAsync(&link, need, st);
+        if (e != hipSuccess) return fail(ORB_ENOMEM, w + "scratch: " + hipGetErrorString(e));
+    }
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t* r = (uint8_t*)link + off;
+        off += bytes;
+        return r;
+    };
+    ChainOut o{};
+    o.H21 = d_H21;
+    o.H12 = d_H12;
+    o.F21 = d_F21;
+    o.sets_out = d_sets_out;
+    o.scores_h = d_scores_h;
+    o.scores_f = d_scores_f;
+    o.best_h = d_best_h;
+    o.best_score_h = d_best_score_h;
+    o.inliers_h = d_inliers_h ? d_inliers_h : take(pc);
+    o.best_f = d_best_f;
+    o.best_score_f = d_best_score_f;
+    o.inliers_f = d_inliers_f ? d_inliers_f : take(pc);
+    o.n_matches = d_n_matches ? d_n_matches : (int32_t*)take(p1);
+    o.best_H21 = d_best_H21 ? d_best_H21 : (float*)take(p9);
+    o.best_F21 = d_best_F21 ? d_best_F21 : (float*)take(p9);
+    o.RH = d_RH;
+    o.use_h = d_use_h ? d_use_h : (int32_t*)take(p1);
+    int r = run_chain(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, sigma, n_hyp, d_rand31, nullptr, true, o,
+                      nullptr, st);
+    if (r == ORB_OK) {
+        const RecOut ro{d_ok, d_R21, d_t21, d_P3D, d_triangulated, d_n_motion, d_motion_R, d_motion_t,
+                        d_n_good, d_cos_parallax, d_parallax_deg, d_best, d_n_inliers};
+        r = run_reconstruct(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, o.best_H21, o.best_F21, o.use_h,
+                            o.inliers_h, o.inliers_f, o.n_matches, K4, sigma, min_parallax, min_triangulated, ro, nullptr,
+                            st);
+    }
+    if (link) (void)hipFreeAsync(link, st);
+    return r;
 }
 
 }  // extern "C"

@@ -152,7 +152,10 @@ class InitializerRansac(Initializer):
     """Initializer::Initialize up to the ReconstructH / ReconstructF call (Initializer.cc:44-113) on
     the GPU: the minimal sets from the caller's rand() values, Normalize, ComputeH21 / ComputeF21
     (cv::SVDecomp as OpenCV 2.4's Jacobi SVD is read, DESIGN.md §16) and both checks.  The package
-    owns no random generator: every call takes `rand31`, (n_hyp, 8) values that rand() returned."""
+    owns no random generator: every call takes `rand31`, (n_hyp, 8) values that rand() returned.
+    ``reconstruct`` is ReconstructH / ReconstructF on a given model (CheckRT, Triangulate, DecomposeE,
+    DESIGN.md §18) and ``initialize`` the whole of Initialize; the ``*_batch_device`` forms do the same
+    for P device-resident pairs."""
 
     def _pair(self, F1, F2, matches12):
         k1, k2 = _keys(F1), _keys(F2)
@@ -252,4 +255,163 @@ class InitializerRansac(Initializer):
             ptr(d_rand31), g("H21"), g("H12"), g("F21"), g("sets"), g("scores_h"), g("scores_f"), g("best_h"),
             g("best_score_h"), g("inliers_h"), g("best_f"), g("best_score_f"), g("inliers_f"), g("n_matches"),
             g("best_H21"), g("best_F21"), g("RH"), g("use_h"), ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    # ---- ReconstructH / ReconstructF and the whole Initialize ----
+
+    _REC_SHAPES = (("ok", (), "int32"), ("R21", (9,), "float32"), ("t21", (3,), "float32"), ("P3D", None, "float32"),
+                   ("triangulated", None, "uint8"), ("n_motion", (), "int32"), ("motion_R", (72,), "float32"),
+                   ("motion_t", (24,), "float32"), ("n_good", (8,), "int32"), ("cos_parallax", (8,), "float32"),
+                   ("parallax_deg", (8,), "float32"), ("best", (), "int32"), ("n_inliers", (), "int32"))
+
+    @staticmethod
+    def _K4(K4) -> np.ndarray:
+        K4 = np.ascontiguousarray(K4, np.float32).reshape(-1)
+        if len(K4) != 4:
+            raise ValueError("K4 holds fx, fy, cx, cy")
+        return K4
+
+    @classmethod
+    def _rec_host(cls, n1):
+        o = {}
+        for name, shape, dt in cls._REC_SHAPES:
+            if shape is None:
+                shape = (max(n1, 1), 3) if name == "P3D" else (max(n1, 1),)
+            o[name] = np.zeros(shape if shape else (1,), dt)
+        return o
+
+    @staticmethod
+    def _rec_result(o, n1) -> dict:
+        return dict(ok=bool(o["ok"][0]), R21=o["R21"].reshape(3, 3), t21=o["t21"], P3D=o["P3D"][:n1],
+                    triangulated=o["triangulated"][:n1].astype(bool), n_motion=int(o["n_motion"][0]),
+                    motion_R=o["motion_R"].reshape(8, 3, 3), motion_t=o["motion_t"].reshape(8, 3), n_good=o["n_good"],
+                    cos_parallax=o["cos_parallax"], parallax_deg=o["parallax_deg"], best=int(o["best"][0]),
+                    n_inliers=int(o["n_inliers"][0]))
+
+    def reconstruct(self, F1, F2, matches12, M21, use_h, inliers, K4, min_parallax: float = 1.0,
+                    min_triangulated: int = 50) -> dict:
+        """ReconstructH (use_h) or ReconstructF on a given model (host buffers, synchronous).  M21:
+        (3, 3) float32; inliers: the model's mask over match ordinals as find() returns inliers_h /
+        inliers_f; K4: fx, fy, cx, cy.  Returns ok, R21 (3, 3), t21 (3,), P3D (n1, 3), triangulated
+        (n1 bools) (zeros when not ok) and the diagnostics n_motion, motion_R (8, 3, 3), motion_t
+        (8, 3), n_good, cos_parallax, parallax_deg (8 each), best and n_inliers."""
+        k1, k2, m12 = self._pair(F1, F2, matches12)
+        M = np.ascontiguousarray(M21, np.float32).reshape(-1)
+        if len(M) != 9:
+            raise ValueError("M21 is a 3 x 3 matrix")
+        inl = np.ascontiguousarray(np.asarray(inliers).reshape(-1), np.uint8)
+        n = int((m12 >= 0).sum())
+        if len(inl) < n:
+            raise ValueError(f"inliers holds {len(inl)} entries for {n} matches")
+        n1 = len(k1)
+        K4 = self._K4(K4)  # (kept alive across the call)
+        o = self._rec_host(n1)
+        check(self._lib.orb_initializer_reconstruct(
+            ptr(k1), n1, ptr(k2), len(k2), ptr(m12), ptr(M), int(use_h), ptr(inl), ptr(K4), self.mSigma,
+            float(min_parallax), int(min_triangulated), *[ptr(o[name]) for name, _, _ in self._REC_SHAPES], self.device))
+        return self._rec_result(o, n1)
+
+    def initialize(self, F1, F2, matches12, rand31, K4, min_parallax: float = 1.0, min_triangulated: int = 50) -> dict:
+        """Initializer::Initialize in one call (host buffers, synchronous): what find() returns plus
+        what reconstruct() returns for the model it chose."""
+        k1, k2, m12 = self._pair(F1, F2, matches12)
+        draws = np.ascontiguousarray(rand31, np.int32).reshape(-1, 8)
+        n_hyp, n1 = len(draws), len(k1)
+        hyp = {k: np.zeros((max(n_hyp, 1), 9), np.float32) for k in ("H21", "H12", "F21")}
+        so = np.zeros((max(n_hyp, 1), 8), np.int32)
+        sc = np.zeros((2, max(n_hyp, 1)), np.float32)
+        best = np.full(2, -1, np.int32)
+        bs = np.zeros(2, np.float32)
+        inl = np.zeros((2, max(n1, 1)), np.uint8)
+        bm = np.zeros((2, 9), np.float32)
+        rh = np.zeros(1, np.float32)
+        use = np.zeros(1, np.int32)
+        nm = ctypes.c_int(0)
+        K4 = self._K4(K4)  # (kept alive across the call)
+        o = self._rec_host(n1)
+        check(self._lib.orb_initializer_initialize(
+            ptr(k1), n1, ptr(k2), len(k2), ptr(m12), self.mSigma, n_hyp, ptr(draws), ptr(K4),
+            float(min_parallax), int(min_triangulated), ptr(hyp["H21"]), ptr(hyp["H12"]), ptr(hyp["F21"]), ptr(so),
+            ptr(sc[0]), ptr(sc[1]), ptr(best[0:]), ptr(bs[0:]), ptr(inl[0]), ptr(best[1:]), ptr(bs[1:]), ptr(inl[1]),
+            ptr(bm[0]), ptr(bm[1]), ptr(rh), ptr(use), ctypes.byref(nm),
+            *[ptr(o[name]) for name, _, _ in self._REC_SHAPES], self.device))
+        n = nm.value
+        out = {k: v[:n_hyp] for k, v in hyp.items()}
+        out.update(n_matches=n, sets=so[:n_hyp], scores_h=sc[0, :n_hyp].copy(), scores_f=sc[1, :n_hyp].copy(),
+                   best_h=int(best[0]), best_f=int(best[1]), best_score_h=np.float32(bs[0]),
+                   best_score_f=np.float32(bs[1]), inliers_h=inl[0, :n].astype(bool), inliers_f=inl[1, :n].astype(bool),
+                   H=bm[0].reshape(3, 3), F=bm[1].reshape(3, 3), RH=np.float32(rh[0]), use_h=bool(use[0]))
+        out.update(self._rec_result(o, n1))
+        return out
+
+    @classmethod
+    def _rec_device(cls, torch, P, cap, dev) -> dict:
+        o = {}
+        for name, shape, dt in cls._REC_SHAPES:
+            if shape is None:
+                shape = (cap, 3) if name == "P3D" else (cap,)
+            o[name] = torch.empty((P, *shape), dtype=getattr(torch, dt), device=dev)
+        return o
+
+    def reconstruct_batch_device(self, d_kps, d_counts, pair_f1, pair_f2, d_matches12, found: dict, K4,
+                                 min_parallax: float = 1.0, min_triangulated: int = 50, stream=None) -> dict:
+        """P pairs on what find_batch_device returned (`found`: best_H21, best_F21, use_h, inliers_h,
+        inliers_f, n_matches), orb_initializer_reconstruct_batch_device.  Returns device tensors: ok,
+        n_motion, best, n_inliers (P,) int32, R21 (P, 9), t21 (P, 3), P3D (P, cap, 3), triangulated
+        (P, cap) uint8, motion_R (P, 72), motion_t (P, 24), n_good (P, 8) int32, cos_parallax and
+        parallax_deg (P, 8).  Asynchronous on `stream`."""
+        import torch
+
+        P, cap = int(d_matches12.shape[0]), int(d_kps.shape[1])
+        if int(d_matches12.shape[1]) != cap:
+            raise ValueError("d_matches12 must be (P, cap)")
+        dev = d_kps.device
+        K4 = self._K4(K4)  # (kept alive across the call)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            o = self._rec_device(torch, P, cap, dev)
+        check(self._lib.orb_initializer_reconstruct_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, P, ptr(pair_f1), ptr(pair_f2), ptr(d_matches12), ptr(found["best_H21"]),
+            ptr(found["best_F21"]), ptr(found["use_h"]), ptr(found["inliers_h"]), ptr(found["inliers_f"]),
+            ptr(found.get("n_matches")), ptr(K4), self.mSigma, float(min_parallax), int(min_triangulated),
+            *[ptr(o[name]) for name, _, _ in self._REC_SHAPES], ctypes.c_void_p(s.cuda_stream)))
+        return o
+
+    def initialize_batch_device(self, d_kps, d_counts, pair_f1, pair_f2, d_matches12, d_rand31, K4,
+                                min_parallax: float = 1.0, min_triangulated: int = 50, stream=None) -> dict:
+        """Initialize for P pairs in one call with no host round trip
+        (orb_initializer_initialize_batch_device): the tensors of find_batch_device(hypotheses=False)
+        plus those of reconstruct_batch_device.  Asynchronous on `stream`."""
+        import torch
+
+        P, cap = int(d_matches12.shape[0]), int(d_kps.shape[1])
+        if int(d_matches12.shape[1]) != cap:
+            raise ValueError("d_matches12 must be (P, cap)")
+        if d_rand31.dtype != torch.int32 or d_rand31.dim() != 3 or int(d_rand31.shape[0]) != P or int(d_rand31.shape[2]) != 8:
+            raise ValueError("d_rand31 must be an int32 tensor (P, n_hyp, 8)")
+        d_rand31 = d_rand31.contiguous()
+        n_hyp = int(d_rand31.shape[1])
+        dev = d_kps.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):  # the zero fills are ordered before the kernels
+            out = {"n_matches": torch.zeros((P,), dtype=torch.int32, device=dev)}
+            for t in "hf":
+                out["scores_" + t] = torch.empty((P, n_hyp), dtype=torch.float32, device=dev)
+                out["best_" + t] = torch.empty((P,), dtype=torch.int32, device=dev)
+                out["best_score_" + t] = torch.empty((P,), dtype=torch.float32, device=dev)
+                out["inliers_" + t] = torch.zeros((P, cap), dtype=torch.uint8, device=dev)
+            out["best_H21"] = torch.empty((P, 9), dtype=torch.float32, device=dev)
+            out["best_F21"] = torch.empty((P, 9), dtype=torch.float32, device=dev)
+            out["RH"] = torch.empty((P,), dtype=torch.float32, device=dev)
+            out["use_h"] = torch.empty((P,), dtype=torch.int32, device=dev)
+            o = self._rec_device(torch, P, cap, dev)
+        K4 = self._K4(K4)  # (kept alive across the call)
+        g = lambda k: ptr(out.get(k))  # noqa: E731
+        check(self._lib.orb_initializer_initialize_batch_device(
+            ptr(d_kps), ptr(d_counts), cap, P, ptr(pair_f1), ptr(pair_f2), ptr(d_matches12), self.mSigma, n_hyp,
+            ptr(d_rand31), ptr(K4), float(min_parallax), int(min_triangulated), g("H21"), g("H12"), g("F21"),
+            g("sets"), g("scores_h"), g("scores_f"), g("best_h"), g("best_score_h"), g("inliers_h"), g("best_f"),
+            g("best_score_f"), g("inliers_f"), g("n_matches"), g("best_H21"), g("best_F21"), g("RH"), g("use_h"),
+            *[ptr(o[name]) for name, _, _ in self._REC_SHAPES], ctypes.c_void_p(s.cuda_stream)))
+        out.update(o)
         return out
