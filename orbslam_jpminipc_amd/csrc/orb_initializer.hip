@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/orb_abi.h"
+#include "orb_initializer_scratch.h"
 #include "orb_internal.h"
 
 namespace {
@@ -326,6 +327,39 @@ int check_limits(int cap, int n_hyp, bool has_h, bool has_f) {
     return ORB_OK;
 }
 
+// matches12[i] in [-1, n2) for every i < n1 (`w`: the entry point's prefix); *N: how many are matches.
+int check_matches(const std::string& w, const int32_t* matches12, int n1, int n2, int* N) {
+    *N = 0;
+    for (int i = 0; i < n1; ++i) {
+        if (matches12[i] < -1 || matches12[i] >= n2)
+            return fail(ORB_EINVAL, w + "matches12[" + std::to_string(i) + "] = " + std::to_string(matches12[i]) +
+                                        " is outside [-1, n2)");
+        *N += matches12[i] >= 0;
+    }
+    return ORB_OK;
+}
+
+// The first inputs of every host form: the pair as a 2-frame batch with one pair (0, 1).
+// [kps 2 x cap | counts 2, f1, f2 and what the form adds | matches12 cap, padded with -1]
+struct PairStage {
+    OrbRegion<orb_keypoint_t> kps;
+    OrbRegion<int32_t> hdr, matches;
+    size_t cap;
+    PairStage(OrbStagePlan& P, int cap_, int n_hdr)
+        : kps(P.in<orb_keypoint_t>(2 * (size_t)cap_)), hdr(P.in<int32_t>(n_hdr)), matches(P.in<int32_t>(cap_)), cap(cap_) {}
+    // Zeroes the whole in-span first: the kernels read the padding between n1 / n2 and cap.
+    void fill(const OrbHostCall& c, const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
+              const int32_t* matches12, int use_h = 0) const {
+        c.zero_in();
+        if (n1) std::memcpy(c.host(kps), kps1, (size_t)n1 * sizeof(orb_keypoint_t));
+        if (n2) std::memcpy(c.host(kps) + cap, kps2, (size_t)n2 * sizeof(orb_keypoint_t));
+        const int32_t h[5] = {n1, n2, 0, 1, use_h};
+        c.put(hdr, h);
+        int32_t* hm = c.host(matches);
+        for (size_t i = 0; i < cap; ++i) hm[i] = i < (size_t)n1 ? matches12[i] : -1;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -370,19 +404,15 @@ int orb_initializer_check_batch_device(const orb_keypoint_t* d_kps, const int32_
     a.inv_sigma2 = 1.0f / (sigma * sigma);  // Initializer.cc:333, 409
     // a model whose scores the caller does not want still needs them between the two kernels:
     // stream-ordered scratch, freed after the second kernel
-    void* tmp[2] = {nullptr, nullptr};
-    for (int m = 0; m < 2; ++m)
-        if (a.M21[m] && !a.scores[m]) {
-            hipError_t e = hipMallocAsync(&tmp[m], (size_t)P * n_hyp * sizeof(float), st);
-            if (e != hipSuccess) {
-                if (tmp[0]) (void)hipFreeAsync(tmp[0], st);
-                return fail(ORB_ENOMEM, std::string("initializer: score scratch: ") + hipGetErrorString(e));
-            }
-            a.scores[m] = (float*)tmp[m];
-        }
+    float* const given[2] = {d_scores_h, d_scores_f};
+    void* tmp = nullptr;
+    if (int r = orb_scratch_alloc(&tmp, st, "initializer: score scratch: ", [&](OrbLayout& L) {
+            for (int m = 0; m < 2; ++m)
+                a.scores[m] = given[m] || !a.M21[m] ? given[m] : L.take<float>((size_t)P * n_hyp);
+        }))
+        return r;
     const int r = launch(a, st);
-    for (int m = 0; m < 2; ++m)
-        if (tmp[m]) (void)hipFreeAsync(tmp[m], st);
+    if (tmp) (void)hipFreeAsync(tmp, st);
     return r;
 }
 
@@ -397,84 +427,55 @@ int orb_initializer_check(const orb_keypoint_t* kps1, int n1, const orb_keypoint
         return fail(ORB_EINVAL, "initializer: H21 and H12 are given together or not at all");
     const int cap = std::max(std::max(n1, n2), 1);
     if (int r = check_limits(cap, n_hyp, H21 != nullptr, F21 != nullptr)) return r;
-    for (int i = 0; i < n1; ++i)
-        if (matches12[i] < -1 || matches12[i] >= n2)
-            return fail(ORB_EINVAL, "initializer: matches12[" + std::to_string(i) + "] = " +
-                                        std::to_string(matches12[i]) + " is outside [-1, n2)");
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
-    // the pair as a 2-frame batch with one pair (0, 1); staging:
-    // in:  [kps 2 x cap | counts 2, f1, f2 | matches12 cap | H21 | H12 | F21]
-    // out: [scores_h | scores_f | best 2 | best_score 2 | n_matches | inliers 2 x cap]
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t hyp = (size_t)n_hyp * 9 * sizeof(float);
-    const size_t oK = 0, oC = al(oK + 2 * (size_t)cap * sizeof(orb_keypoint_t)), oM = al(oC + 16),
-                 oH21 = al(oM + (size_t)cap * 4), oH12 = al(oH21 + hyp), oF = al(oH12 + hyp), in_end = al(oF + hyp);
-    const size_t oS = in_end, oB = al(oS + 2 * (size_t)n_hyp * 4), oI = al(oB + 20), total = al(oI + 2 * (size_t)cap);
-    if (int r = C->reserve(total, total)) return r;
-    uint8_t* hp = C->pinned;
-    std::memset(hp, 0, in_end);
-    if (n1) std::memcpy(hp + oK, kps1, (size_t)n1 * sizeof(orb_keypoint_t));
-    if (n2) std::memcpy(hp + oK + (size_t)cap * sizeof(orb_keypoint_t), kps2, (size_t)n2 * sizeof(orb_keypoint_t));
-    const int32_t hdr[4] = {n1, n2, 0, 1};
-    std::memcpy(hp + oC, hdr, 16);
-    int32_t* hm = (int32_t*)(hp + oM);
-    for (int i = 0; i < cap; ++i) hm[i] = i < n1 ? matches12[i] : -1;
-    if (H21) {
-        std::memcpy(hp + oH21, H21, hyp);
-        std::memcpy(hp + oH12, H12, hyp);
-    }
-    if (F21) std::memcpy(hp + oF, F21, hyp);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
+    int N;
+    if (int r = check_matches("initializer: ", matches12, n1, n2, &N)) return r;
+    const size_t nh = (size_t)n_hyp;
+    OrbStagePlan P;
+    const PairStage pair(P, cap, 4);
+    const auto rH21 = P.in<float>(nh * 9), rH12 = P.in<float>(nh * 9), rF = P.in<float>(nh * 9);
+    const auto rS = P.out<float>(2 * nh);       // scores_h | scores_f
+    const auto rB = P.out<int32_t>(5);          // best 2 | best_score 2 (floats) | n_matches
+    const auto rI = P.out<uint8_t>(2 * (size_t)cap);  // inliers_h | inliers_f
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    pair.fill(call, kps1, n1, kps2, n2, matches12);
     InitArgs a{};
-    a.kps = (const orb_keypoint_t*)(d + oK);
-    a.counts = (const int32_t*)(d + oC);
+    a.kps = call.dev(pair.kps);
+    a.counts = call.dev(pair.hdr);
     a.pair_f1 = a.counts + 2;
     a.pair_f2 = a.counts + 3;
-    a.matches12 = (const int32_t*)(d + oM);
-    a.M21[0] = H21 ? (const float*)(d + oH21) : nullptr;
-    a.H12 = H21 ? (const float*)(d + oH12) : nullptr;
-    a.M21[1] = F21 ? (const float*)(d + oF) : nullptr;
+    a.matches12 = call.dev(pair.matches);
+    a.M21[0] = H21 ? call.send(rH21, H21) : nullptr;
+    a.H12 = H21 ? call.send(rH12, H12) : nullptr;
+    a.M21[1] = F21 ? call.send(rF, F21) : nullptr;
     for (int m = 0; m < 2; ++m) {
-        a.scores[m] = (float*)(d + oS) + (size_t)m * n_hyp;
-        a.best[m] = (int32_t*)(d + oB) + m;
-        a.best_score[m] = (float*)(d + oB + 8) + m;
-        a.inliers[m] = d + oI + (size_t)m * cap;
+        a.scores[m] = call.dev(rS) + (size_t)m * n_hyp;
+        a.best[m] = call.dev(rB) + m;
+        a.best_score[m] = (float*)(call.dev(rB) + 2) + m;
+        a.inliers[m] = call.dev(rI) + (size_t)m * cap;
     }
-    a.n_matches = (int32_t*)(d + oB + 16);
+    a.n_matches = call.dev(rB) + 4;
     a.cap = cap;
     a.P = 1;
     a.n_hyp = n_hyp;
     a.inv_sigma2 = 1.0f / (sigma * sigma);  // Initializer.cc:333, 409
-    const int r = launch(a, C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + oS, d + oS, total - oS, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("initializer: ") + hipGetErrorString(e));
-    int32_t nm;
-    std::memcpy(&nm, hp + oB + 16, 4);
-    if (n_matches) *n_matches = nm;
-    const float* hs = (const float*)(hp + oS);
-    const int32_t* hb = (const int32_t*)(hp + oB);
-    const float* hbs = (const float*)(hp + oB + 8);
+    if (int r = call.upload()) return r;
+    if (int r = call.finish(launch(a, call.stream()), hipSuccess, "initializer: ")) return r;
+    const int32_t* hb = call.host(rB);
+    const float* hbs = (const float*)(hb + 2);
+    const size_t nm = (size_t)hb[4];  // the inliers are n_matches long, not cap
+    if (n_matches) *n_matches = hb[4];
     if (H21) {
-        if (scores_h) std::memcpy(scores_h, hs, (size_t)n_hyp * 4);
+        call.get(rS, scores_h, nh);
         if (best_h) *best_h = hb[0];
         if (best_score_h) *best_score_h = hbs[0];
-        if (inliers_h && nm) std::memcpy(inliers_h, hp + oI, (size_t)nm);
+        call.get(rI, inliers_h, nm);
     }
     if (F21) {
-        if (scores_f) std::memcpy(scores_f, hs + n_hyp, (size_t)n_hyp * 4);
+        call.get(rS, scores_f, nh, nh);
         if (best_f) *best_f = hb[1];
         if (best_score_f) *best_score_f = hbs[1];
-        if (inliers_f && nm) std::memcpy(inliers_f, hp + oI + cap, (size_t)nm);
+        call.get(rI, inliers_f, nm, cap);
     }
     return ORB_OK;
 }
@@ -508,7 +509,6 @@ namespace {
 constexpr int HY_A = 144;                                   // floats of the At region (9 x 16)
 constexpr int HY_V = 81;                                    // floats of the Vt region (9 x 9)
 constexpr int HY_LDS = (HY_A + HY_V) * 64 * 4 + 9 * 64 * 8;  // + W: 62208 bytes
-constexpr int HY_NORM = 16;                                 // floats per (pair, side): T, meanX, meanY, sX, sY
 constexpr int HY_MAX_FILL_TRIES = 16;                       // OpenCV's fill-in `while` has no bound; §16
 constexpr int NORM_THREADS = 256;
 
@@ -986,48 +986,24 @@ __global__ void __launch_bounds__(64) k_init_result(ResultArgs a) {
     if (a.use_h) a.use_h[p] = (double)RH > 0.40 ? 1 : 0;  // Initializer.cc:113: a float against the double 0.40
 }
 
-// What one chain call holds in scratch at most (every optional output absent).
-size_t chain_scratch_bytes(int P, int cap, int n_hyp) {
-    const size_t hyp = orb_align256((size_t)P * n_hyp * 9 * 4);
-    return orb_align256((size_t)P * cap * 4) + orb_align256((size_t)P * 4) + orb_align256((size_t)P * 2 * HY_NORM * 4) +
-           3 * hyp + 2 * orb_align256((size_t)P * n_hyp * 4) + 4 * orb_align256((size_t)P * 4);
-}
-
-struct ChainOut {
-    float *H21, *H12, *F21, *Hn, *Fn, *norm;
-    int32_t* sets_out;
-    float *scores_h, *scores_f;
-    int32_t* best_h;
-    float* best_score_h;
-    uint8_t* inliers_h;
-    int32_t* best_f;
-    float* best_score_f;
-    uint8_t* inliers_f;
-    int32_t* n_matches;
-    float *best_H21, *best_F21, *RH;
-    int32_t* use_h;
-};
-
 // normalise -> hypotheses -> (when `score`) k_init_scores, k_init_best, k_init_result, enqueued on
-// `st`.  `scratch`: chain_scratch_bytes() of device memory, or NULL for a stream-ordered allocation
-// freed after the last kernel.
+// `st`.  `scratch`: `scratch_bytes` of device memory for chain_regions(), or NULL for a stream-ordered
+// allocation freed after the last kernel.
 int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
               const int32_t* d_pair_f2, const int32_t* d_matches12, float sigma, int n_hyp, const int32_t* d_rand31,
-              const int32_t* d_sets, bool score, const ChainOut& o, uint8_t* scratch, hipStream_t st) {
-    void* owned = nullptr;
-    if (!scratch) {
-        hipError_t e = hipMallocAsync(&owned, chain_scratch_bytes(P, cap, n_hyp), st);
-        if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("initializer: scratch: ") + hipGetErrorString(e));
-        scratch = (uint8_t*)owned;
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* r = scratch + off;
-        off += orb_align256(bytes);
-        return r;
-    };
-    const size_t hyp = (size_t)P * n_hyp * 9 * 4;
+              const int32_t* d_sets, bool score, const ChainOut& o, uint8_t* scratch, size_t scratch_bytes,
+              hipStream_t st) {
     HypArgs h{};
+    InitArgs a{};
+    void* owned = nullptr;
+    if (scratch) {
+        OrbLayout L(scratch);
+        chain_regions(L, o, score, cap, P, n_hyp, h, a);
+        assert(L.end <= scratch_bytes);
+    } else if (int r = orb_scratch_alloc(&owned, st, "initializer: scratch: ", [&](OrbLayout& L) {
+                   chain_regions(L, o, score, cap, P, n_hyp, h, a);
+               }))
+        return r;
     h.kps = d_kps;
     h.counts = d_counts;
     h.pair_f1 = d_pair_f1;
@@ -1035,12 +1011,6 @@ int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int
     h.matches12 = d_matches12;
     h.rand31 = d_rand31;
     h.sets_in = d_sets;
-    h.ord_i = (int32_t*)take((size_t)P * cap * 4);
-    h.nmatch = o.n_matches ? o.n_matches : (int32_t*)take((size_t)P * 4);
-    h.norm = o.norm ? o.norm : (float*)take((size_t)P * 2 * HY_NORM * 4);
-    h.H21 = o.H21 ? o.H21 : score ? (float*)take(hyp) : nullptr;
-    h.H12 = o.H12 ? o.H12 : score ? (float*)take(hyp) : nullptr;
-    h.F21 = o.F21 ? o.F21 : score ? (float*)take(hyp) : nullptr;
     h.Hn = o.Hn;
     h.Fn = o.Fn;
     h.sets_out = o.sets_out;
@@ -1058,7 +1028,6 @@ int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int
         e = hipGetLastError();
     }
     if (e == hipSuccess && score) {
-        InitArgs a{};
         a.kps = d_kps;
         a.counts = d_counts;
         a.pair_f1 = d_pair_f1;
@@ -1067,12 +1036,6 @@ int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int
         a.M21[0] = h.H21;
         a.M21[1] = h.F21;
         a.H12 = h.H12;
-        a.scores[0] = o.scores_h ? o.scores_h : (float*)take((size_t)P * n_hyp * 4);
-        a.scores[1] = o.scores_f ? o.scores_f : (float*)take((size_t)P * n_hyp * 4);
-        a.best[0] = o.best_h ? o.best_h : (int32_t*)take((size_t)P * 4);
-        a.best[1] = o.best_f ? o.best_f : (int32_t*)take((size_t)P * 4);
-        a.best_score[0] = o.best_score_h ? o.best_score_h : (float*)take((size_t)P * 4);
-        a.best_score[1] = o.best_score_f ? o.best_score_f : (float*)take((size_t)P * 4);
         a.inliers[0] = o.inliers_h;
         a.inliers[1] = o.inliers_f;
         a.n_matches = o.n_matches;
@@ -1095,19 +1058,9 @@ int run_chain(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int
 }
 
 // The host forms: the pair as a 2-frame batch with one pair (0, 1), staged like orb_initializer_check.
-struct HostOut {
-    float *H21, *H12, *F21, *Hn, *Fn, *T1, *T2;
-    int32_t* sets_out;
-    float *scores_h, *scores_f;
-    int32_t* best_h;
-    float* best_score_h;
-    uint8_t* inliers_h;
-    int32_t* best_f;
-    float* best_score_f;
-    uint8_t* inliers_f;
-    float *best_H21, *best_F21, *RH;
-    int32_t* use_h;
-    int* n_matches;
+// Their outputs are the chain's, as host arrays, with the two halves of `norm` apart.
+struct HostOut : ChainOut {
+    float *T1, *T2;
 };
 
 int host_run(const char* who, const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
@@ -1120,13 +1073,8 @@ int host_run(const char* who, const orb_keypoint_t* kps1, int n1, const orb_keyp
     if (cap > IN_MAX_CAP) return fail(ORB_ENOTSUP, w + "more than 8192 keypoints per frame");
     if (n_hyp < 1 || n_hyp > IN_MAX_HYP)
         return fail(ORB_EINVAL, w + "n_hyp must be in [1, 1024] (got " + std::to_string(n_hyp) + ")");
-    int N = 0;
-    for (int i = 0; i < n1; ++i) {
-        if (matches12[i] < -1 || matches12[i] >= n2)
-            return fail(ORB_EINVAL, w + "matches12[" + std::to_string(i) + "] = " + std::to_string(matches12[i]) +
-                                        " is outside [-1, n2)");
-        N += matches12[i] >= 0;
-    }
+    int N;
+    if (int r = check_matches(w, matches12, n1, n2, &N)) return r;
     for (int k = 0; k < n_hyp * 8; ++k) {
         if (rand31 && rand31[k] < 0)
             return fail(ORB_EINVAL, w + "rand31[" + std::to_string(k) + "] = " + std::to_string(rand31[k]) + " is negative");
@@ -1134,93 +1082,76 @@ int host_run(const char* who, const orb_keypoint_t* kps1, int n1, const orb_keyp
             return fail(ORB_EINVAL, w + "sets[" + std::to_string(k) + "] = " + std::to_string(sets[k]) +
                                         " is outside [0, N = " + std::to_string(N) + ")");
     }
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
-    // in:  [kps 2 x cap | counts 2, f1, f2 | matches12 cap | draws n_hyp x 8]
-    // out: [H21 H12 F21 Hn Fn | sets | norm | scores 2 | best 2, best_score 2, n, RH, use_h | best_H21 best_F21 |
-    //       inliers 2 x cap]      then the chain's scratch (device only)
-    auto al = orb_align256;
-    const size_t hyp = al((size_t)n_hyp * 9 * 4);
-    const size_t oK = 0, oC = al(oK + 2 * (size_t)cap * sizeof(orb_keypoint_t)), oM = al(oC + 16),
-                 oD = al(oM + (size_t)cap * 4), in_end = al(oD + (size_t)n_hyp * 32);
-    const size_t oH = in_end, oSet = oH + 5 * hyp, oN = al(oSet + (size_t)n_hyp * 32), oS = al(oN + 2 * HY_NORM * 4),
-                 oB = al(oS + 2 * (size_t)n_hyp * 4), oBH = al(oB + 28), oI = al(oBH + 72),
-                 out_end = al(oI + 2 * (size_t)cap);
-    if (int r = C->reserve(out_end + chain_scratch_bytes(1, cap, n_hyp), out_end)) return r;
-    uint8_t* hp = C->pinned;
-    std::memset(hp, 0, in_end);
-    if (n1) std::memcpy(hp + oK, kps1, (size_t)n1 * sizeof(orb_keypoint_t));
-    if (n2) std::memcpy(hp + oK + (size_t)cap * sizeof(orb_keypoint_t), kps2, (size_t)n2 * sizeof(orb_keypoint_t));
-    const int32_t hdr[4] = {n1, n2, 0, 1};
-    std::memcpy(hp + oC, hdr, 16);
-    int32_t* hm = (int32_t*)(hp + oM);
-    for (int i = 0; i < cap; ++i) hm[i] = i < n1 ? matches12[i] : -1;
-    std::memcpy(hp + oD, sets ? sets : rand31, (size_t)n_hyp * 32);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
+    const size_t nh = (size_t)n_hyp;
+    OrbStagePlan P;
+    const PairStage pair(P, cap, 4);
+    const auto rD = P.in<int32_t>(nh * 8);
+    OrbRegion<float> rHyp[5];  // H21 H12 F21 Hn Fn
+    for (auto& r : rHyp) r = P.out<float>(nh * 9);
+    const auto rSet = P.out<int32_t>(nh * 8);
+    const auto rN = P.out<float>(2 * HY_NORM);  // T1 ..., T2 ...
+    const auto rS = P.out<float>(2 * nh);       // scores_h | scores_f
+    const auto rB = P.out<int32_t>(7);          // best 2 | best_score 2 (floats) | n_matches | RH (float) | use_h
+    const auto rBH = P.out<float>(18);          // best_H21 | best_F21
+    const auto rI = P.out<uint8_t>(2 * (size_t)cap);  // inliers_h | inliers_f
+    HypArgs h0{};  // the chain's scratch at its most, as if no optional output were given
+    InitArgs a0{};
+    const auto rX = P.scratch<uint8_t>(
+        orb_layout_size([&](OrbLayout& L) { chain_regions(L, ChainOut{}, score, cap, 1, n_hyp, h0, a0); }));
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    pair.fill(call, kps1, n1, kps2, n2, matches12);
+    const int32_t *dc = call.dev(pair.hdr), *dd = call.send(rD, sets ? sets : rand31);
+    if (int r = call.upload()) return r;
     ChainOut co{};
-    co.H21 = (float*)(d + oH);
-    co.H12 = (float*)(d + oH + hyp);
-    co.F21 = (float*)(d + oH + 2 * hyp);
-    co.Hn = (float*)(d + oH + 3 * hyp);
-    co.Fn = (float*)(d + oH + 4 * hyp);
-    co.sets_out = (int32_t*)(d + oSet);
-    co.norm = (float*)(d + oN);
-    co.n_matches = (int32_t*)(d + oB + 16);
+    co.H21 = call.dev(rHyp[0]);
+    co.H12 = call.dev(rHyp[1]);
+    co.F21 = call.dev(rHyp[2]);
+    co.Hn = call.dev(rHyp[3]);
+    co.Fn = call.dev(rHyp[4]);
+    co.sets_out = call.dev(rSet);
+    co.norm = call.dev(rN);
+    int32_t* const db = call.dev(rB);
+    co.n_matches = db + 4;
     if (score) {
-        co.scores_h = (float*)(d + oS);
+        co.scores_h = call.dev(rS);
         co.scores_f = co.scores_h + n_hyp;
-        co.best_h = (int32_t*)(d + oB);
-        co.best_f = co.best_h + 1;
-        co.best_score_h = (float*)(d + oB + 8);
+        co.best_h = db;
+        co.best_f = db + 1;
+        co.best_score_h = (float*)(db + 2);
         co.best_score_f = co.best_score_h + 1;
-        co.RH = (float*)(d + oB + 20);
-        co.use_h = (int32_t*)(d + oB + 24);
-        co.best_H21 = (float*)(d + oBH);
+        co.RH = (float*)(db + 5);
+        co.use_h = db + 6;
+        co.best_H21 = call.dev(rBH);
         co.best_F21 = co.best_H21 + 9;
-        co.inliers_h = d + oI;
-        co.inliers_f = d + oI + cap;
+        co.inliers_h = call.dev(rI);
+        co.inliers_f = co.inliers_h + cap;
     }
-    const int32_t* dc = (const int32_t*)(d + oC);
-    const int32_t* dd = (const int32_t*)(d + oD);
-    const int r = run_chain((const orb_keypoint_t*)(d + oK), dc, cap, 1, dc + 2, dc + 3, (const int32_t*)(d + oM), sigma,
-                            n_hyp, rand31 ? dd : nullptr, sets ? dd : nullptr, score, co, d + out_end, C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + oH, d + oH, out_end - oH, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, w + hipGetErrorString(e));
-    const size_t hb = (size_t)n_hyp * 9 * 4;
+    const int r = run_chain(call.dev(pair.kps), dc, cap, 1, dc + 2, dc + 3, call.dev(pair.matches), sigma, n_hyp,
+                            rand31 ? dd : nullptr, sets ? dd : nullptr, score, co, call.dev(rX), rX.count, call.stream());
+    if (int rf = call.finish(r, hipSuccess, w)) return rf;
     float* const ho[5] = {o.H21, o.H12, o.F21, o.Hn, o.Fn};
-    for (int k = 0; k < 5; ++k)
-        if (ho[k]) std::memcpy(ho[k], hp + oH + k * hyp, hb);
-    if (o.sets_out) std::memcpy(o.sets_out, hp + oSet, (size_t)n_hyp * 32);
-    if (o.T1) std::memcpy(o.T1, hp + oN, 36);
-    if (o.T2) std::memcpy(o.T2, hp + oN + HY_NORM * 4, 36);
-    int32_t nm;
-    std::memcpy(&nm, hp + oB + 16, 4);
-    if (o.n_matches) *o.n_matches = nm;
+    for (int k = 0; k < 5; ++k) call.get(rHyp[k], ho[k]);
+    call.get(rSet, o.sets_out);
+    call.get(rN, o.T1, 9);
+    call.get(rN, o.T2, 9, HY_NORM);
+    const int32_t* hb = call.host(rB);
+    const float* hbs = (const float*)(hb + 2);
+    const size_t nm = (size_t)hb[4];  // the inliers are n_matches long, not cap
+    if (o.n_matches) *o.n_matches = hb[4];
     if (!score) return ORB_OK;
-    const float* hs = (const float*)(hp + oS);
-    const int32_t* bi = (const int32_t*)(hp + oB);
-    const float* bs = (const float*)(hp + oB + 8);
-    if (o.scores_h) std::memcpy(o.scores_h, hs, (size_t)n_hyp * 4);
-    if (o.scores_f) std::memcpy(o.scores_f, hs + n_hyp, (size_t)n_hyp * 4);
-    if (o.best_h) *o.best_h = bi[0];
-    if (o.best_f) *o.best_f = bi[1];
-    if (o.best_score_h) *o.best_score_h = bs[0];
-    if (o.best_score_f) *o.best_score_f = bs[1];
-    if (o.inliers_h && nm) std::memcpy(o.inliers_h, hp + oI, (size_t)nm);
-    if (o.inliers_f && nm) std::memcpy(o.inliers_f, hp + oI + cap, (size_t)nm);
-    if (o.RH) std::memcpy(o.RH, hp + oB + 20, 4);
-    if (o.use_h) std::memcpy(o.use_h, hp + oB + 24, 4);
-    if (o.best_H21) std::memcpy(o.best_H21, hp + oBH, 36);
-    if (o.best_F21) std::memcpy(o.best_F21, hp + oBH + 36, 36);
+    call.get(rS, o.scores_h, nh);
+    call.get(rS, o.scores_f, nh, nh);
+    if (o.best_h) *o.best_h = hb[0];
+    if (o.best_f) *o.best_f = hb[1];
+    if (o.best_score_h) *o.best_score_h = hbs[0];
+    if (o.best_score_f) *o.best_score_f = hbs[1];
+    call.get(rI, o.inliers_h, nm);
+    call.get(rI, o.inliers_f, nm, cap);
+    if (o.RH) std::memcpy(o.RH, hb + 5, 4);
+    if (o.use_h) *o.use_h = hb[6];
+    call.get(rBH, o.best_H21, 9);
+    call.get(rBH, o.best_F21, 9, 9);
     return ORB_OK;
 }
 
@@ -1306,7 +1237,7 @@ int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32
     o.RH = d_RH;
     o.use_h = d_use_h;
     return run_chain(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, sigma, n_hyp, d_rand31, nullptr, true, o,
-                     nullptr, (hipStream_t)stream);
+                     nullptr, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1810,25 +1741,6 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_select(RecArgs a) {
     }
 }
 
-struct RecOut {
-    int32_t* ok;
-    float *R21, *t21, *P3D;
-    uint8_t* triangulated;
-    int32_t* n_motion;
-    float *motion_R, *motion_t;
-    int32_t* n_good;
-    float *cos_parallax, *parallax_deg;
-    int32_t *best, *n_inliers;
-};
-
-// What one reconstruct call holds in scratch at most (every optional output absent).
-size_t rec_scratch_bytes(int P, int cap) {
-    const size_t pc = (size_t)P * cap;
-    return orb_align256(pc * 4) + orb_align256((size_t)P * 4) + orb_align256(pc * 8) + orb_align256(pc * 8 * 4) +
-           3 * orb_align256((size_t)P * 4) + orb_align256((size_t)P * 72 * 4) + orb_align256((size_t)P * 24 * 4) +
-           3 * orb_align256((size_t)P * 8 * 4);
-}
-
 int check_rec_params(const std::string& w, const float* K4, float sigma, float min_parallax, int min_triangulated) {
     if (!K4) return fail(ORB_EINVAL, w + "K4 is NULL");
     if (int r = orb_check_camera(w.substr(0, w.size() - 2).c_str(), "", K4)) return r;
@@ -1842,28 +1754,22 @@ int check_rec_params(const std::string& w, const float* K4, float sigma, float m
 }
 
 // k_init_motion -> k_init_checkrt -> k_init_stat -> k_init_select, enqueued on `st`.  `scratch`:
-// rec_scratch_bytes() of device memory, or NULL for a stream-ordered allocation freed after the
-// last kernel.
+// `scratch_bytes` of device memory for rec_regions(), or NULL for a stream-ordered allocation freed
+// after the last kernel.
 int run_reconstruct(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P, const int32_t* d_pair_f1,
                     const int32_t* d_pair_f2, const int32_t* d_matches12, const float* d_H21, const float* d_F21,
                     const int32_t* d_use_h, const uint8_t* d_inl_h, const uint8_t* d_inl_f, const int32_t* d_n_matches,
                     const float* K4, float sigma, float min_parallax, int min_triangulated, const RecOut& o,
-                    uint8_t* scratch, hipStream_t st) {
-    void* owned = nullptr;
-    if (!scratch) {
-        hipError_t e = hipMallocAsync(&owned, rec_scratch_bytes(P, cap), st);
-        if (e != hipSuccess)
-            return fail(ORB_ENOMEM, std::string("initializer reconstruct: scratch: ") + hipGetErrorString(e));
-        scratch = (uint8_t*)owned;
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* r = scratch + off;
-        off += orb_align256(bytes);
-        return r;
-    };
-    const size_t pc = (size_t)P * cap;
+                    uint8_t* scratch, size_t scratch_bytes, hipStream_t st) {
     RecArgs a{};
+    void* owned = nullptr;
+    if (scratch) {
+        OrbLayout L(scratch);
+        rec_regions(L, o, cap, P, a);
+        assert(L.end <= scratch_bytes);
+    } else if (int r = orb_scratch_alloc(&owned, st, "initializer reconstruct: scratch: ",
+                                         [&](OrbLayout& L) { rec_regions(L, o, cap, P, a); }))
+        return r;
     a.kps = d_kps;
     a.counts = d_counts;
     a.pair_f1 = d_pair_f1;
@@ -1883,18 +1789,6 @@ int run_reconstruct(const orb_keypoint_t* d_kps, const int32_t* d_counts, int ca
     a.th2 = (float)(4.0 * (double)sigma2);  // 4.0*mSigma2, narrowed at the call
     a.min_parallax = min_parallax;
     a.min_triangulated = min_triangulated;
-    a.ord_i = (int32_t*)take(pc * 4);
-    a.nwalk = (int32_t*)take((size_t)P * 4);
-    a.flags = take(pc * 8);
-    a.cosv = (float*)take(pc * 8 * 4);
-    a.n_motion = o.n_motion ? o.n_motion : (int32_t*)take((size_t)P * 4);
-    a.n_inliers = o.n_inliers ? o.n_inliers : (int32_t*)take((size_t)P * 4);
-    a.best = o.best ? o.best : (int32_t*)take((size_t)P * 4);
-    a.motion_R = o.motion_R ? o.motion_R : (float*)take((size_t)P * 72 * 4);
-    a.motion_t = o.motion_t ? o.motion_t : (float*)take((size_t)P * 24 * 4);
-    a.n_good = o.n_good ? o.n_good : (int32_t*)take((size_t)P * 8 * 4);
-    a.cos_sel = o.cos_parallax ? o.cos_parallax : (float*)take((size_t)P * 8 * 4);
-    a.parallax = o.parallax_deg ? o.parallax_deg : (float*)take((size_t)P * 8 * 4);
     a.ok = o.ok;
     a.R21 = o.R21;
     a.t21 = o.t21;
@@ -1954,7 +1848,7 @@ int orb_initializer_reconstruct_batch_device(const orb_keypoint_t* d_kps, const 
                    d_n_good, d_cos_parallax, d_parallax_deg, d_best, d_n_inliers};
     return run_reconstruct(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, d_best_H21, d_best_F21, d_use_h,
                            d_inliers_h, d_inliers_f, d_n_matches, K4, sigma, min_parallax, min_triangulated, o, nullptr,
-                           (hipStream_t)stream);
+                           0, (hipStream_t)stream);
 }
 
 int orb_initializer_reconstruct(const orb_keypoint_t* kps1, int n1, const orb_keypoint_t* kps2, int n2,
@@ -1970,74 +1864,53 @@ int orb_initializer_reconstruct(const orb_keypoint_t* kps1, int n1, const orb_ke
     const int cap = std::max(std::max(n1, n2), 1);
     if (cap > IN_MAX_CAP) return fail(ORB_ENOTSUP, w + "more than 8192 keypoints per frame");
     if (int r = check_rec_params(w, K4, sigma, min_parallax, min_triangulated)) return r;
-    int N = 0;
-    for (int i = 0; i < n1; ++i) {
-        if (matches12[i] < -1 || matches12[i] >= n2)
-            return fail(ORB_EINVAL, w + "matches12[" + std::to_string(i) + "] = " + std::to_string(matches12[i]) +
-                                        " is outside [-1, n2)");
-        N += matches12[i] >= 0;
-    }
+    int N;
+    if (int r = check_matches(w, matches12, n1, n2, &N)) return r;
     if (N && !inliers) return fail(ORB_EINVAL, w + "inliers is NULL");
     for (int k = 0; k < N; ++k)
         if (inliers[k] > 1)
             return fail(ORB_EINVAL, w + "inliers[" + std::to_string(k) + "] = " + std::to_string((int)inliers[k]) +
                                         " is not 0 or 1");
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
-    // in:  [kps 2 x cap | counts 2, f1, f2, use_h | matches12 cap | model 9 | mask cap]
-    // out: [ok, best, n_motion, n_inliers | R21 9, t21 3 | motion_R 72 | motion_t 24 | n_good 8 | cos 8 |
-    //       parallax 8 | P3D cap x 3 | triangulated cap]      then the chain's scratch (device only)
-    auto al = orb_align256;
-    const size_t oK = 0, oC = al(oK + 2 * (size_t)cap * sizeof(orb_keypoint_t)), oM = al(oC + 20),
-                 oMod = al(oM + (size_t)cap * 4), oI = al(oMod + 36), in_end = al(oI + (size_t)cap);
-    const size_t oS = in_end, oR = al(oS + 16), oMR = al(oR + 48), oMT = al(oMR + 288), oG = al(oMT + 96),
-                 oCs = al(oG + 32), oPa = al(oCs + 32), oP = al(oPa + 32), oT = al(oP + (size_t)cap * 12),
-                 out_end = al(oT + (size_t)cap);
-    if (int r = C->reserve(out_end + rec_scratch_bytes(1, cap), out_end)) return r;
-    uint8_t* hp = C->pinned;
-    std::memset(hp, 0, in_end);
-    if (n1) std::memcpy(hp + oK, kps1, (size_t)n1 * sizeof(orb_keypoint_t));
-    if (n2) std::memcpy(hp + oK + (size_t)cap * sizeof(orb_keypoint_t), kps2, (size_t)n2 * sizeof(orb_keypoint_t));
-    const int32_t hdr[5] = {n1, n2, 0, 1, use_h};
-    std::memcpy(hp + oC, hdr, 20);
-    int32_t* hm = (int32_t*)(hp + oM);
-    for (int i = 0; i < cap; ++i) hm[i] = i < n1 ? matches12[i] : -1;
-    std::memcpy(hp + oMod, M21, 36);
-    if (N) std::memcpy(hp + oI, inliers, (size_t)N);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
-    const int32_t* dc = (const int32_t*)(d + oC);
-    int32_t* ds = (int32_t*)(d + oS);
-    const RecOut o{ds, (float*)(d + oR), (float*)(d + oR) + 9, (float*)(d + oP), d + oT, ds + 2, (float*)(d + oMR),
-                   (float*)(d + oMT), (int32_t*)(d + oG), (float*)(d + oCs), (float*)(d + oPa), ds + 1, ds + 3};
+    OrbStagePlan P;
+    const PairStage pair(P, cap, 5);  // the header ends with use_h
+    const auto rMod = P.in<float>(9);
+    const auto rI = P.in<uint8_t>(cap);
+    const auto rS = P.out<int32_t>(4);  // ok, best, n_motion, n_inliers
+    const auto rR = P.out<float>(12);   // R21 9, t21 3
+    const auto rMR = P.out<float>(72), rMT = P.out<float>(24);
+    const auto rG = P.out<int32_t>(8);
+    const auto rCs = P.out<float>(8), rPa = P.out<float>(8), rP = P.out<float>((size_t)cap * 3);
+    const auto rT = P.out<uint8_t>(cap);
+    RecArgs a0{};  // the chain's scratch at its most, as if no optional output were given
+    const auto rX = P.scratch<uint8_t>(orb_layout_size([&](OrbLayout& L) { rec_regions(L, RecOut{}, cap, 1, a0); }));
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    pair.fill(call, kps1, n1, kps2, n2, matches12, use_h);
+    const float* d_model = call.send(rMod, M21);
+    call.put(rI, inliers, N);
+    if (int r = call.upload()) return r;
+    const int32_t* dc = call.dev(pair.hdr);
+    int32_t* ds = call.dev(rS);
+    const RecOut o{ds, call.dev(rR), call.dev(rR) + 9, call.dev(rP), call.dev(rT), ds + 2, call.dev(rMR),
+                   call.dev(rMT), call.dev(rG), call.dev(rCs), call.dev(rPa), ds + 1, ds + 3};
     // the one model and the one mask serve whichever use_h names
-    const int r = run_reconstruct((const orb_keypoint_t*)(d + oK), dc, cap, 1, dc + 2, dc + 3, (const int32_t*)(d + oM),
-                                  (const float*)(d + oMod), (const float*)(d + oMod), dc + 4, d + oI, d + oI, nullptr, K4,
-                                  sigma, min_parallax, min_triangulated, o, d + out_end, C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + oS, d + oS, out_end - oS, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, w + hipGetErrorString(e));
-    const int32_t* hs = (const int32_t*)(hp + oS);
-    if (ok) *ok = hs[0];
-    if (best) *best = hs[1];
-    if (n_motion) *n_motion = hs[2];
-    if (n_inliers) *n_inliers = hs[3];
-    if (R21) std::memcpy(R21, hp + oR, 36);
-    if (t21) std::memcpy(t21, hp + oR + 36, 12);
-    if (motion_R) std::memcpy(motion_R, hp + oMR, 288);
-    if (motion_t) std::memcpy(motion_t, hp + oMT, 96);
-    if (n_good) std::memcpy(n_good, hp + oG, 32);
-    if (cos_parallax) std::memcpy(cos_parallax, hp + oCs, 32);
-    if (parallax_deg) std::memcpy(parallax_deg, hp + oPa, 32);
-    if (P3D && n1) std::memcpy(P3D, hp + oP, (size_t)n1 * 12);
-    if (triangulated && n1) std::memcpy(triangulated, hp + oT, (size_t)n1);
+    const int r = run_reconstruct(call.dev(pair.kps), dc, cap, 1, dc + 2, dc + 3, call.dev(pair.matches), d_model,
+                                  d_model, dc + 4, call.dev(rI), call.dev(rI), nullptr, K4, sigma, min_parallax,
+                                  min_triangulated, o, call.dev(rX), rX.count, call.stream());
+    if (int rf = call.finish(r, hipSuccess, w)) return rf;
+    call.get(rS, ok, 1, 0);
+    call.get(rS, best, 1, 1);
+    call.get(rS, n_motion, 1, 2);
+    call.get(rS, n_inliers, 1, 3);
+    call.get(rR, R21, 9);
+    call.get(rR, t21, 3, 9);
+    call.get(rMR, motion_R);
+    call.get(rMT, motion_t);
+    call.get(rG, n_good);
+    call.get(rCs, cos_parallax);
+    call.get(rPa, parallax_deg);
+    call.get(rP, P3D, (size_t)n1 * 3);
+    call.get(rT, triangulated, (size_t)n1);
     return ORB_OK;
 }
 
@@ -2096,20 +1969,7 @@ int orb_initializer_initialize_batch_device(
         return fail(ORB_EINVAL, w + "bad arguments");
     hipStream_t st = (hipStream_t)stream;
     // what passes from the first chain to the second and the caller did not ask for
-    const size_t pc = orb_align256((size_t)P * cap), p9 = orb_align256((size_t)P * 36), p1 = orb_align256((size_t)P * 4);
-    void* link = nullptr;
-    const size_t need = (d_inliers_h ? 0 : pc) + (d_inliers_f ? 0 : pc) + (d_best_H21 ? 0 : p9) +
-                        (d_best_F21 ? 0 : p9) + (d_use_h ? 0 : p1) + (d_n_matches ? 0 : p1);
-    if (need) {
-        hipError_t e = hipMallocAsync(&link, need, st);
-        if (e != hipSuccess) return fail(ORB_ENOMEM, w + "scratch: " + hipGetErrorString(e));
-    }
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t* r = (uint8_t*)link + off;
-        off += bytes;
-        return r;
-    };
+    const size_t p = (size_t)P;
     ChainOut o{};
     o.H21 = d_H21;
     o.H12 = d_H12;
@@ -2119,23 +1979,27 @@ int orb_initializer_initialize_batch_device(
     o.scores_f = d_scores_f;
     o.best_h = d_best_h;
     o.best_score_h = d_best_score_h;
-    o.inliers_h = d_inliers_h ? d_inliers_h : take(pc);
     o.best_f = d_best_f;
     o.best_score_f = d_best_score_f;
-    o.inliers_f = d_inliers_f ? d_inliers_f : take(pc);
-    o.n_matches = d_n_matches ? d_n_matches : (int32_t*)take(p1);
-    o.best_H21 = d_best_H21 ? d_best_H21 : (float*)take(p9);
-    o.best_F21 = d_best_F21 ? d_best_F21 : (float*)take(p9);
     o.RH = d_RH;
-    o.use_h = d_use_h ? d_use_h : (int32_t*)take(p1);
+    void* link = nullptr;
+    if (int r = orb_scratch_alloc(&link, st, w + "scratch: ", [&](OrbLayout& L) {
+            o.inliers_h = L.given_or_take(d_inliers_h, p * cap);
+            o.inliers_f = L.given_or_take(d_inliers_f, p * cap);
+            o.n_matches = L.given_or_take(d_n_matches, p);
+            o.best_H21 = L.given_or_take(d_best_H21, p * 9);
+            o.best_F21 = L.given_or_take(d_best_F21, p * 9);
+            o.use_h = L.given_or_take(d_use_h, p);
+        }))
+        return r;
     int r = run_chain(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, sigma, n_hyp, d_rand31, nullptr, true, o,
-                      nullptr, st);
+                      nullptr, 0, st);
     if (r == ORB_OK) {
         const RecOut ro{d_ok, d_R21, d_t21, d_P3D, d_triangulated, d_n_motion, d_motion_R, d_motion_t,
                         d_n_good, d_cos_parallax, d_parallax_deg, d_best, d_n_inliers};
         r = run_reconstruct(d_kps, d_counts, cap, P, d_pair_f1, d_pair_f2, d_matches12, o.best_H21, o.best_F21, o.use_h,
                             o.inliers_h, o.inliers_f, o.n_matches, K4, sigma, min_parallax, min_triangulated, ro, nullptr,
-                            st);
+                            0, st);
     }
     if (link) (void)hipFreeAsync(link, st);
     return r;

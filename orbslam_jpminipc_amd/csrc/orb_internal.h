@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_staging.h"
 
 // Records `msg` as the calling thread's orb_last_error() and returns `code`.
 __attribute__((visibility("hidden"))) int orb_internal_set_error(int code, const std::string& msg);
@@ -21,9 +22,6 @@ __attribute__((visibility("hidden"))) int orb_internal_set_error(int code, const
         if (e_ != hipSuccess)                                                                               \
             return orb_internal_set_error(ORB_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));  \
     } while (0)
-
-// Sizes of the regions of a staging buffer or a scratch allocation: rounded up to 256 B.
-inline size_t orb_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // fx fy cx cy of an entry point `who`: all finite, the focal lengths not 0; ORB_EINVAL (message set)
 // otherwise.  `which` names the camera where a call takes more than one ("K1"), "" where it takes one.
@@ -56,6 +54,66 @@ struct OrbHostCtx {
     int reserve(size_t dev_bytes, size_t host_bytes);
 };
 __attribute__((visibility("hidden"))) OrbHostCtx* orb_internal_thread_ctx(int device);
+
+// One synchronous host-buffer call on the calling thread's context of `device` (< 0: the current one):
+// the planned arena reserved (device: all of it; pinned staging: in + out, the scratch is not
+// mirrored) and bound, or `err` set (message recorded) and nothing to use.  Then: send() or put() the
+// inputs, upload(), launch on stream() with dev() pointers, finish(), get() the outputs.
+class OrbHostCall : public OrbStage {
+    OrbHostCtx* C = nullptr;
+    int open(const OrbStagePlan& plan, int device) {
+        int ndev = 0;
+        ORB_HIPCHK(hipGetDeviceCount(&ndev));
+        if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
+        C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
+        if (!C) return orb_internal_set_error(ORB_EINVAL, "device ordinal out of range");
+        ORB_HIPCHK(hipSetDevice(device));
+        if (int r = C->reserve(plan.total(), plan.out_end())) return r;
+        bind(plan, C->buf, C->pinned);
+        return ORB_OK;
+    }
+
+public:
+    const int err;
+    OrbHostCall(const OrbStagePlan& plan, int device) : err(open(plan, device)) {}
+    hipStream_t stream() const { return C->stream; }
+    // the in-span to the device, in one copy
+    int upload() const {
+        const uint8_t* hp = h_;
+        const size_t in_end = in_end_;
+        ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
+        return ORB_OK;
+    }
+    // After the launches, which gave `r` (an error of ours, message set) and `e`: the out-span to the
+    // host in one copy when both are clean, and the stream synchronised in every case, because the next
+    // call on this thread reuses the staging.  `r` wins, then `e` or the copy's error, then the
+    // synchronise's; a HIP error is recorded as ORB_EDEVICE with `prefix` before HIP's text.
+    int finish(int r, hipError_t e, const std::string& prefix) const {
+        if (r == ORB_OK && e == hipSuccess)
+            e = hipMemcpyAsync(h_ + in_end_, d_ + in_end_, out_end_ - in_end_, hipMemcpyDeviceToHost, C->stream);
+        const hipError_t es = hipStreamSynchronize(C->stream);
+        if (r) return r;
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) return orb_internal_set_error(ORB_EDEVICE, prefix + hipGetErrorString(e));
+        return ORB_OK;
+    }
+};
+
+// A stream-ordered scratch block for the regions that `regions(OrbLayout&)` names: `regions` runs
+// once without a base, for the size, and once on the allocation, for the pointers.  *block is what to
+// hipFreeAsync after the last kernel (NULL when no region was needed); ORB_ENOMEM with `what` before
+// HIP's text when the allocation fails.
+template <class F>
+int orb_scratch_alloc(void** block, hipStream_t st, const std::string& what, F&& regions) {
+    *block = nullptr;
+    if (const size_t bytes = orb_layout_size(regions)) {
+        const hipError_t e = hipMallocAsync(block, bytes, st);
+        if (e != hipSuccess) return orb_internal_set_error(ORB_ENOMEM, what + hipGetErrorString(e));
+    }
+    OrbLayout L(*block);
+    regions(L);
+    return ORB_OK;
+}
 
 // The device a vocabulary handle lives on (orb_voc.hip), for the units that take one (orb_kfdb.hip).
 struct orb_vocabulary;

@@ -52,7 +52,6 @@
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int PO_MAX_CAP = 8192;
 constexpr int PO_THREADS = 256;
@@ -382,63 +381,47 @@ int orb_pose_optimization(int n, const float* p3d, const float* obs, const float
     for (int k = 0; k < 12; ++k)
         if (!std::isfinite(pose_in[k]))
             return fail(ORB_EINVAL, std::string(who) + ": pose_in[" + std::to_string(k) + "] is not finite");
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
     const int cap = std::max(n, 1);
-    // staging: in  [p3d | obs | inv_sigma2 | has_mp | pose_in]
-    //          out [pose f64 | info | pose f32 | n_inliers | outlier]   then the scratch (device only)
-    const size_t oP = 0, oO = al(oP + (size_t)n * 12), oS = al(oO + (size_t)n * 8), oH = al(oS + (size_t)n * 4),
-                 oT = al(oH + (size_t)n), in_end = al(oT + 48);
-    const size_t o64 = in_end, oI = al(o64 + 96), o32 = al(oI + sizeof(orb_pose_opt_info_t)), oN = al(o32 + 48),
-                 oF = al(oN + 4), out_end = al(oF + (size_t)cap);
-    const size_t oSoa = out_end, oIdx = al(oSoa + (size_t)PO_NV * cap * 8), oCnt = al(oIdx + (size_t)cap * 4),
-                 total = al(oCnt + 4);
-    if (int r = C->reserve(total, out_end)) return r;
-    uint8_t* hp = C->pinned;
-    if (n) {
-        std::memcpy(hp + oP, p3d, (size_t)n * 12);
-        std::memcpy(hp + oO, obs, (size_t)n * 8);
-        std::memcpy(hp + oS, inv_sigma2, (size_t)n * 4);
-        if (has_mp) std::memcpy(hp + oH, has_mp, (size_t)n);
-    }
-    std::memcpy(hp + oT, pose_in, 48);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
+    const size_t N = (size_t)n;
+    OrbStagePlan P;
+    const auto rP = P.in<float>(N * 3), rO = P.in<float>(N * 2), rS = P.in<float>(N);
+    const auto rH = P.in<uint8_t>(N);
+    const auto rT = P.in<float>(12);
+    const auto r64 = P.out<double>(12);
+    const auto rI = P.out<orb_pose_opt_info_t>(1);
+    const auto r32 = P.out<float>(12);
+    const auto rN = P.out<int32_t>(1);
+    const auto rF = P.out<uint8_t>(cap);
+    const auto rSoa = P.scratch<double>((size_t)PO_NV * cap);
+    const auto rIdx = P.scratch<int32_t>(cap), rCnt = P.scratch<int32_t>(1);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
     PoArgs a{};
     a.n_direct = n;
-    a.mp_pos = (const float*)(d + oP);
-    a.obs = (const float*)(d + oO);
-    a.inv_sigma2 = (const float*)(d + oS);
-    a.has_mp = has_mp ? d + oH : nullptr;
+    a.mp_pos = call.send(rP, p3d);
+    a.obs = call.send(rO, obs);
+    a.inv_sigma2 = call.send(rS, inv_sigma2);
+    a.has_mp = has_mp ? call.send(rH, has_mp) : nullptr;
     a.nlevels = 1;
     a.fx = (double)fx, a.fy = (double)fy, a.cx = (double)cx, a.cy = (double)cy;
-    a.pose_in = (const float*)(d + oT);
-    a.pose_out64 = (double*)(d + o64);
-    a.info = (orb_pose_opt_info_t*)(d + oI);
-    a.pose_out = (float*)(d + o32);
-    a.n_inliers = (int32_t*)(d + oN);
-    a.outlier = d + oF;
-    a.soa = (double*)(d + oSoa);
-    a.index = (int32_t*)(d + oIdx);
-    a.n = (int32_t*)(d + oCnt);
+    a.pose_in = call.send(rT, pose_in);
+    a.pose_out64 = call.dev(r64);
+    a.info = call.dev(rI);
+    a.pose_out = call.dev(r32);
+    a.n_inliers = call.dev(rN);
+    a.outlier = call.dev(rF);
+    a.soa = call.dev(rSoa);
+    a.index = call.dev(rIdx);
+    a.n = call.dev(rCnt);
     a.cap = cap;
     a.S = 1;
-    const int r = launch(a, C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + o64, d + o64, out_end - o64, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    std::memcpy(pose_out, hp + o32, 48);
-    if (pose_out_f64) std::memcpy(pose_out_f64, hp + o64, 96);
-    if (info) std::memcpy(info, hp + oI, sizeof *info);
-    std::memcpy(n_inliers, hp + oN, 4);
-    if (n) std::memcpy(outlier, hp + oF, (size_t)n);
+    if (int r = call.upload()) return r;
+    if (int r = call.finish(launch(a, call.stream()), hipSuccess, std::string(who) + ": ")) return r;
+    call.get(r32, pose_out);
+    call.get(r64, pose_out_f64);
+    call.get(rI, info);
+    call.get(rN, n_inliers);
+    call.get(rF, outlier, N);
     return ORB_OK;
 }
 
@@ -478,13 +461,13 @@ int orb_pose_optimization_batch_device(const orb_keypoint_t* d_kps, const int32_
     a.cap = cap;
     a.S = S;
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_soa = al((size_t)S * PO_NV * cap * 8), b_idx = al((size_t)S * cap * 4), b_n = al((size_t)S * 4);
     void* tmp = nullptr;
-    hipError_t e = hipMallocAsync(&tmp, b_soa + b_idx + b_n, st);
-    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string(who) + ": scratch: " + hipGetErrorString(e));
-    a.soa = (double*)tmp;
-    a.index = (int32_t*)((uint8_t*)tmp + b_soa);
-    a.n = (int32_t*)((uint8_t*)tmp + b_soa + b_idx);
+    if (int r = orb_scratch_alloc(&tmp, st, std::string(who) + ": scratch: ", [&](OrbLayout& L) {
+            a.soa = L.take<double>((size_t)S * PO_NV * cap);
+            a.index = L.take<int32_t>((size_t)S * cap);
+            a.n = L.take<int32_t>(S);
+        }))
+        return r;
     const int r = launch(a, st);
     (void)hipFreeAsync(tmp, st);
     return r;

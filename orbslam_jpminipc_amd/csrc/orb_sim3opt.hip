@@ -53,7 +53,6 @@
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int S3_MAX_CAP = 8192;
 constexpr int S3_THREADS = 256;
@@ -522,67 +521,48 @@ int orb_optimize_sim3(int n, const float* x3dc1, const float* x3dc2, const float
     for (int k = 0; k < 13; ++k)
         if (!std::isfinite(sim3_in[k]))
             return fail(ORB_EINVAL, std::string(who) + ": sim3_in[" + std::to_string(k) + "] is not finite");
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
     const int cap = std::max(n, 1);
     const size_t N = (size_t)n;
-    // staging: in  [x1 | x2 | obs1 | obs2 | w1 | w2 | usable | sim3_in]
-    //          out [sim3 f64 | info | sim3 f32 | n_inliers | kept]   then the scratch (device only)
-    const size_t oX1 = 0, oX2 = al(oX1 + N * 12), oO1 = al(oX2 + N * 12), oO2 = al(oO1 + N * 8), oW1 = al(oO2 + N * 8),
-                 oW2 = al(oW1 + N * 4), oU = al(oW2 + N * 4), oT = al(oU + N), in_end = al(oT + 52);
-    const size_t o64 = in_end, oI = al(o64 + 64), o32 = al(oI + sizeof(orb_sim3_opt_info_t)), oN = al(o32 + 52),
-                 oK = al(oN + 4), out_end = al(oK + (size_t)cap);
-    const size_t oSoa = out_end, oIdx = al(oSoa + (size_t)S3_NV * cap * 8), oCnt = al(oIdx + (size_t)cap * 4),
-                 total = al(oCnt + 4);
-    if (int r = C->reserve(total, out_end)) return r;
-    uint8_t* hp = C->pinned;
-    if (n) {
-        std::memcpy(hp + oX1, x3dc1, N * 12);
-        std::memcpy(hp + oX2, x3dc2, N * 12);
-        std::memcpy(hp + oO1, obs1, N * 8);
-        std::memcpy(hp + oO2, obs2, N * 8);
-        std::memcpy(hp + oW1, inv_sigma2_1, N * 4);
-        std::memcpy(hp + oW2, sigma2_2, N * 4);
-        if (usable) std::memcpy(hp + oU, usable, N);
-    }
-    std::memcpy(hp + oT, sim3_in, 52);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
+    OrbStagePlan P;
+    const auto rX1 = P.in<float>(N * 3), rX2 = P.in<float>(N * 3), rO1 = P.in<float>(N * 2), rO2 = P.in<float>(N * 2),
+               rW1 = P.in<float>(N), rW2 = P.in<float>(N);
+    const auto rU = P.in<uint8_t>(N);
+    const auto rT = P.in<float>(13);
+    const auto r64 = P.out<double>(8);
+    const auto rI = P.out<orb_sim3_opt_info_t>(1);
+    const auto r32 = P.out<float>(13);
+    const auto rN = P.out<int32_t>(1);
+    const auto rK = P.out<uint8_t>(cap);
+    const auto rSoa = P.scratch<double>((size_t)S3_NV * cap);
+    const auto rIdx = P.scratch<int32_t>(cap), rCnt = P.scratch<int32_t>(1);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
     S3Args a{};
     a.n_direct = n;
-    a.x1 = (const float*)(d + oX1), a.x2 = (const float*)(d + oX2);
-    a.obs1 = (const float*)(d + oO1), a.obs2 = (const float*)(d + oO2);
-    a.w1 = (const float*)(d + oW1), a.w2 = (const float*)(d + oW2);
-    a.usable = usable ? d + oU : nullptr;
+    a.x1 = call.send(rX1, x3dc1), a.x2 = call.send(rX2, x3dc2);
+    a.obs1 = call.send(rO1, obs1), a.obs2 = call.send(rO2, obs2);
+    a.w1 = call.send(rW1, inv_sigma2_1), a.w2 = call.send(rW2, sigma2_2);
+    a.usable = usable ? call.send(rU, usable) : nullptr;
     a.nlevels = 1;
     for (int k = 0; k < 4; ++k) a.K1[k] = (double)K1[k], a.K2[k] = (double)K2[k];
-    a.sim3_in = (const float*)(d + oT);
-    a.sim3_out64 = (double*)(d + o64);
-    a.info = (orb_sim3_opt_info_t*)(d + oI);
-    a.sim3_out = (float*)(d + o32);
-    a.n_inliers = (int32_t*)(d + oN);
-    a.kept = d + oK;
-    a.soa = (double*)(d + oSoa);
-    a.index = (int32_t*)(d + oIdx);
-    a.n = (int32_t*)(d + oCnt);
+    a.sim3_in = call.send(rT, sim3_in);
+    a.sim3_out64 = call.dev(r64);
+    a.info = call.dev(rI);
+    a.sim3_out = call.dev(r32);
+    a.n_inliers = call.dev(rN);
+    a.kept = call.dev(rK);
+    a.soa = call.dev(rSoa);
+    a.index = call.dev(rIdx);
+    a.n = call.dev(rCnt);
     a.cap = cap;
     a.S = 1;
-    const int r = launch(a, th2, C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + o64, d + o64, out_end - o64, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    if (sim3_out_f64) std::memcpy(sim3_out_f64, hp + o64, 64);
-    if (info) std::memcpy(info, hp + oI, sizeof *info);
-    if (sim3_out) std::memcpy(sim3_out, hp + o32, 52);
-    if (n_inliers) std::memcpy(n_inliers, hp + oN, 4);
-    if (n) std::memcpy(kept, hp + oK, N);
+    if (int r = call.upload()) return r;
+    if (int r = call.finish(launch(a, th2, call.stream()), hipSuccess, std::string(who) + ": ")) return r;
+    call.get(r64, sim3_out_f64);
+    call.get(rI, info);
+    call.get(r32, sim3_out);
+    call.get(rN, n_inliers);
+    call.get(rK, kept, N);
     return ORB_OK;
 }
 
@@ -626,13 +606,13 @@ int orb_optimize_sim3_batch_device(const orb_keypoint_t* d_kps, const int32_t* d
     a.cap = cap;
     a.S = S;
     hipStream_t st = (hipStream_t)stream;
-    const size_t b_soa = al((size_t)S * S3_NV * cap * 8), b_idx = al((size_t)S * cap * 4), b_n = al((size_t)S * 4);
     void* tmp = nullptr;
-    hipError_t e = hipMallocAsync(&tmp, b_soa + b_idx + b_n, st);
-    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string(who) + ": scratch: " + hipGetErrorString(e));
-    a.soa = (double*)tmp;
-    a.index = (int32_t*)((uint8_t*)tmp + b_soa);
-    a.n = (int32_t*)((uint8_t*)tmp + b_soa + b_idx);
+    if (int r = orb_scratch_alloc(&tmp, st, std::string(who) + ": scratch: ", [&](OrbLayout& L) {
+            a.soa = L.take<double>((size_t)S * S3_NV * cap);
+            a.index = L.take<int32_t>((size_t)S * cap);
+            a.n = L.take<int32_t>(S);
+        }))
+        return r;
     const int r = launch(a, th2, st);
     (void)hipFreeAsync(tmp, st);
     return r;

@@ -66,7 +66,6 @@
 namespace {
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
-constexpr auto al = orb_align256;  // (a short name for the layout lines)
 
 constexpr int CS_MAX_CAP = 8192;
 constexpr int CS_MAX_HYP = 1024;
@@ -933,64 +932,63 @@ int check_sigma2(const char* who, const float* s2, int n, bool sim3) {
     return ORB_OK;
 }
 
+// What the consensus reads and writes in every host form: best_in, declared as the last input, and
+// counts | best_at | first, n as the first outputs.  The masks (`rM`, n_hyp x W words) and the SoA
+// scratch are declared by the caller, after its own outputs.
+struct ConsStage {
+    OrbRegion<int32_t> best_in, counts, best_at, first_n;
+    ConsStage(OrbStagePlan& P, size_t nh)
+        : best_in(P.in<int32_t>(1)), counts(P.out<int32_t>(nh)), best_at(P.out<int32_t>(nh)), first_n(P.out<int32_t>(2)) {}
+    void args(const OrbHostCall& c, ConsArgs& a, int n, int best, OrbRegion<uint64_t> rM, OrbRegion<float> rSoa) const {
+        a.n_direct = n;
+        a.best_in = c.send(best_in, &best);
+        a.soa = c.dev(rSoa);
+        a.counts = c.dev(counts);
+        a.best_at = c.dev(best_at);
+        a.first = c.dev(first_n);
+        a.n = a.first + 1;
+        a.index = nullptr;
+        a.W = (n + 63) / 64;
+        a.masks = a.W ? c.dev(rM) : nullptr;  // no pointer to an empty region
+        a.cap = std::max(n, 1);
+        a.S = 1;
+    }
+    void results(const OrbHostCall& c, OrbRegion<uint64_t> rM, int32_t* counts_out, int32_t* best_at_out, int32_t* first,
+                 uint64_t* masks) const {
+        c.get(counts, counts_out);
+        c.get(best_at, best_at_out);
+        c.get(first_n, first, 1);
+        c.get(rM, masks);
+    }
+};
+
 // One solver from compact host arrays: the common part of the two host entry points.  in[k]: the
 // k-th input array with in_bytes[k] bytes (4 correspondence arrays, then the 2 hypothesis arrays).
 template <int MODEL, class HT>
 int run_host(ConsArgs a, const void* const* in, const size_t* in_bytes, int n, int32_t* counts, uint64_t* masks,
              int32_t* best_at, int32_t* first, int best_in, int device) {
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
     const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
+    const size_t nh = (size_t)n_hyp;
     constexpr int NV = MODEL == PNP ? NV_PNP : NV_SIM3;
-    // staging: in  [c0 | c1 | c2 | c3 | HA | HB | best_in]
-    //          out [counts | best_at | first, n | masks]      then the SoA scratch (device only)
-    size_t o_in[7], off = 0;
-    for (int k = 0; k < 6; ++k) {
-        o_in[k] = off;
-        off = al(off + in_bytes[k]);
-    }
-    o_in[6] = off;
-    const size_t in_end = al(off + 4);
-    const size_t oC = in_end, oB = al(oC + (size_t)n_hyp * 4), oF = al(oB + (size_t)n_hyp * 4), oM = al(oF + 8),
-                 out_end = al(oM + (size_t)n_hyp * W * 8), total = al(out_end + (size_t)NV * cap * 4);
-    if (int r = C->reserve(total, out_end)) return r;
-    uint8_t* hp = C->pinned;
-    for (int k = 0; k < 6; ++k)
-        if (in_bytes[k]) std::memcpy(hp + o_in[k], in[k], in_bytes[k]);
-    std::memcpy(hp + o_in[6], &best_in, 4);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
-    a.c0 = (const float*)(d + o_in[0]);
-    a.c1 = (const float*)(d + o_in[1]);
-    a.c2 = (const float*)(d + o_in[2]);
-    a.c3 = (const float*)(d + o_in[3]);
-    a.n_direct = n;
-    a.best_in = (const int32_t*)(d + o_in[6]);
-    a.soa = (float*)(d + out_end);
-    a.counts = (int32_t*)(d + oC);
-    a.best_at = (int32_t*)(d + oB);
-    a.first = (int32_t*)(d + oF);
-    a.n = a.first + 1;
-    a.index = nullptr;
-    a.masks = W ? (uint64_t*)(d + oM) : nullptr;
-    a.cap = cap;
-    a.S = 1;
-    a.W = W;
-    const int r = launch<MODEL, HT>(a, (const HT*)(d + o_in[4]), (const HT*)(d + o_in[5]), C->stream);
-    hipError_t e = hipSuccess;
-    if (r == ORB_OK) e = hipMemcpyAsync(hp + oC, d + oC, out_end - oC, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
-    if (counts) std::memcpy(counts, hp + oC, (size_t)n_hyp * 4);
-    if (best_at) std::memcpy(best_at, hp + oB, (size_t)n_hyp * 4);
-    if (first) std::memcpy(first, hp + oF, 4);
-    if (masks && W) std::memcpy(masks, hp + oM, (size_t)n_hyp * W * 8);
+    OrbStagePlan P;
+    OrbRegion<uint8_t> rIn[6];
+    for (int k = 0; k < 6; ++k) rIn[k] = P.in<uint8_t>(in_bytes[k]);
+    const ConsStage cs(P, nh);
+    const auto rM = P.out<uint64_t>(nh * W);
+    const auto rSoa = P.scratch<float>((size_t)NV * cap);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    const void* d_in[6];
+    for (int k = 0; k < 6; ++k) d_in[k] = call.send(rIn[k], (const uint8_t*)in[k]);
+    a.c0 = (const float*)d_in[0];
+    a.c1 = (const float*)d_in[1];
+    a.c2 = (const float*)d_in[2];
+    a.c3 = (const float*)d_in[3];
+    cs.args(call, a, n, best_in, rM, rSoa);
+    if (int r = call.upload()) return r;
+    const int r = launch<MODEL, HT>(a, (const HT*)d_in[4], (const HT*)d_in[5], call.stream());
+    if (int rf = call.finish(r, hipSuccess, "solvers: ")) return rf;
+    cs.results(call, rM, counts, best_at, first, masks);
     return ORB_OK;
 }
 
@@ -999,14 +997,14 @@ template <int MODEL, class HT>
 int run_batch(ConsArgs a, const HT* HA, const HT* HB, hipStream_t st) {
     constexpr int NV = MODEL == PNP ? NV_PNP : NV_SIM3;
     // stream-ordered scratch: the SoA values, then n and counts where the caller does not want them
-    const size_t b_soa = al((size_t)a.S * NV * a.cap * 4), b_n = al((size_t)a.S * 4),
-                 b_c = al((size_t)a.S * a.n_hyp * 4);
+    int32_t *const d_n = a.n, *const d_counts = a.counts;
     void* tmp = nullptr;
-    hipError_t e = hipMallocAsync(&tmp, b_soa + b_n + b_c, st);
-    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("solvers: scratch: ") + hipGetErrorString(e));
-    a.soa = (float*)tmp;
-    if (!a.n) a.n = (int32_t*)((uint8_t*)tmp + b_soa);
-    if (!a.counts) a.counts = (int32_t*)((uint8_t*)tmp + b_soa + b_n);
+    if (int r = orb_scratch_alloc(&tmp, st, "solvers: scratch: ", [&](OrbLayout& L) {
+            a.soa = L.take<float>((size_t)a.S * NV * a.cap);
+            a.n = L.given_or_take(d_n, (size_t)a.S);
+            a.counts = L.given_or_take(d_counts, (size_t)a.S * a.n_hyp);
+        }))
+        return r;
     const int r = launch<MODEL, HT>(a, HA, HB, st);
     (void)hipFreeAsync(tmp, st);
     return r;
@@ -1040,19 +1038,28 @@ int fill_batch(ConsArgs& a, const char* who, const orb_keypoint_t* d_kps, const 
     return ORB_OK;
 }
 
-// Exactly one of sets / rand31, every value in range (the host forms).
-int check_draws(const char* who, int n, int n_hyp, const int32_t* sets, const int32_t* rand31) {
+// Exactly one of sets / rand31 (n_hyp x K), every value in range (the host forms).  PnP (K = 4) takes
+// n = 0 and then leaves the sets unread; Sim3 (K = 3) refuses every set of an empty problem.
+int check_draws(const char* who, int K, int n, int n_hyp, const int32_t* sets, const int32_t* rand31) {
     if ((sets != nullptr) == (rand31 != nullptr))
         return fail(ORB_EINVAL, std::string(who) + ": exactly one of sets and rand31 must be given");
     const int32_t* v = sets ? sets : rand31;
-    for (size_t k = 0; k < (size_t)n_hyp * 3; ++k) {
-        if (sets && (v[k] < 0 || v[k] >= n))
+    for (size_t k = 0; k < (size_t)n_hyp * K; ++k) {
+        if (sets && (K == 3 || n > 0) && (v[k] < 0 || v[k] >= n))
             return fail(ORB_EINVAL, std::string(who) + ": sets[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
                                         " is outside [0, n)");
         if (rand31 && v[k] < 0)
             return fail(ORB_EINVAL, std::string(who) + ": rand31[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
                                         " is outside [0, 2^31)");
     }
+    return ORB_OK;
+}
+
+// A consensus below the size K of a minimal set accepts hypotheses that nothing supports.
+int check_min_inliers(const char* who, int K, int min_inliers) {
+    if (min_inliers < K)
+        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least " + std::to_string(K) +
+                                    ", the size of a minimal set (got " + std::to_string(min_inliers) + ")");
     return ORB_OK;
 }
 
@@ -1070,92 +1077,60 @@ struct HypHost {  // the host outputs of the generation, each may be NULL
 int run_host_sim3(ConsArgs a, bool score, int n, const float* x1, const float* x2, const float* s1, const float* s2,
                   const int32_t* sets, const int32_t* rand31, const HypHost& o, int32_t* counts, uint64_t* masks,
                   int32_t* best_at, int32_t* first, int best_in, int device) {
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
     const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
-    const size_t nh = (size_t)n_hyp;
-    // staging: in  [x1 | x2 | s1 | s2 | draws | best_in]
-    //          out [counts | best_at | first, n | T12 | T21 | sim3 | quat | sets | accepted | masks]
-    //          then the SoA scratch (device only)
-    const size_t o1 = 0, o2 = al(o1 + (size_t)n * 12), o3 = al(o2 + (size_t)n * 12), o4 = al(o3 + (size_t)n * 4),
-                 oD = al(o4 + (size_t)n * 4), oI = al(oD + nh * 12), in_end = al(oI + 4);
-    const size_t oC = in_end, oB = al(oC + nh * 4), oF = al(oB + nh * 4), oT12 = al(oF + 8), oT21 = al(oT12 + nh * 48),
-                 oS = al(oT21 + nh * 48), oQ = al(oS + nh * 52), oSet = al(oQ + nh * 16), oA = al(oSet + nh * 12),
-                 oM = al(oA + 52), out_end = al(oM + nh * W * 8), total = al(out_end + (size_t)NV_SIM3 * cap * 4);
-    if (int r = C->reserve(total, out_end)) return r;
-    uint8_t* hp = C->pinned;
-    if (n) {
-        std::memcpy(hp + o1, x1, (size_t)n * 12);
-        std::memcpy(hp + o2, x2, (size_t)n * 12);
-        if (s1) std::memcpy(hp + o3, s1, (size_t)n * 4); else std::memset(hp + o3, 0, (size_t)n * 4);
-        if (s2) std::memcpy(hp + o4, s2, (size_t)n * 4); else std::memset(hp + o4, 0, (size_t)n * 4);
-    }
-    std::memcpy(hp + oD, sets ? sets : rand31, nh * 12);
-    std::memcpy(hp + oI, &best_in, 4);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
-    a.c0 = (const float*)(d + o1);
-    a.c1 = (const float*)(d + o2);
-    a.c2 = (const float*)(d + o3);
-    a.c3 = (const float*)(d + o4);
-    a.n_direct = n;
-    a.best_in = (const int32_t*)(d + oI);
-    a.soa = (float*)(d + out_end);
-    a.counts = (int32_t*)(d + oC);
-    a.best_at = (int32_t*)(d + oB);
-    a.first = (int32_t*)(d + oF);
-    a.n = a.first + 1;
-    a.index = nullptr;
-    a.masks = W ? (uint64_t*)(d + oM) : nullptr;
-    a.cap = cap;
-    a.S = 1;
-    a.W = W;
+    const size_t N = (size_t)n, nh = (size_t)n_hyp;
+    OrbStagePlan P;
+    const auto r1 = P.in<float>(N * 3), r2 = P.in<float>(N * 3), r3 = P.in<float>(N), r4 = P.in<float>(N);
+    const auto rD = P.in<int32_t>(nh * 3);
+    const ConsStage cs(P, nh);
+    const auto rT12 = P.out<float>(nh * 12), rT21 = P.out<float>(nh * 12), rS = P.out<float>(nh * 13),
+               rQ = P.out<float>(nh * 4);
+    const auto rSet = P.out<int32_t>(nh * 3);
+    const auto rA = P.out<float>(13);
+    const auto rM = P.out<uint64_t>(nh * W);
+    const auto rSoa = P.scratch<float>((size_t)NV_SIM3 * cap);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    a.c0 = call.send(r1, x1);
+    a.c1 = call.send(r2, x2);
+    a.c2 = call.send(r3, s1);
+    a.c3 = call.send(r4, s2);
+    cs.args(call, a, n, best_in, rM, rSoa);
     HypArgs y{};
-    (sets ? y.sets : y.rand31) = (const int32_t*)(d + oD);
-    y.T12 = (float*)(d + oT12);
-    y.T21 = (float*)(d + oT21);
-    y.sim3 = (float*)(d + oS);
-    y.quat = (float*)(d + oQ);
-    y.sets_out = (int32_t*)(d + oSet);
+    (sets ? y.sets : y.rand31) = call.send(rD, sets ? sets : rand31);
+    y.T12 = call.dev(rT12);
+    y.T21 = call.dev(rT21);
+    y.sim3 = call.dev(rS);
+    y.quat = call.dev(rQ);
+    y.sets_out = call.dev(rSet);
+    if (int r = call.upload()) return r;
     int r = ORB_OK;
     hipError_t e = hipSuccess;
     if (score) {
-        r = launch<SIM3, float>(a, y.T12, y.T21, C->stream, &y);
+        r = launch<SIM3, float>(a, y.T12, y.T21, call.stream(), &y);
         if (r == ORB_OK) {
-            hipLaunchKernelGGL(k_sim3_accepted, dim3(1), dim3(64), 0, C->stream, a, y.sim3, (float*)(d + oA),
+            hipLaunchKernelGGL(k_sim3_accepted, dim3(1), dim3(64), 0, call.stream(), a, y.sim3, call.dev(rA),
                                (uint64_t*)nullptr);
             e = hipGetLastError();
         }
     } else {
-        hipLaunchKernelGGL((k_cons_prepare<SIM3>), dim3(1), dim3(CS_PREP_THREADS), 0, C->stream, a);
+        hipLaunchKernelGGL((k_cons_prepare<SIM3>), dim3(1), dim3(CS_PREP_THREADS), 0, call.stream(), a);
         e = hipGetLastError();
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_sim3_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, C->stream, a, y);
+            hipLaunchKernelGGL(k_sim3_hypotheses, dim3((n_hyp + 63) / 64, 1), dim3(64), 0, call.stream(), a, y);
             e = hipGetLastError();
         }
     }
-    if (r == ORB_OK && e == hipSuccess)
-        e = hipMemcpyAsync(hp + oC, d + oC, out_end - oC, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+    if (int rf = call.finish(r, e, "solvers: ")) return rf;
     if (score) {
-        if (counts) std::memcpy(counts, hp + oC, nh * 4);
-        if (best_at) std::memcpy(best_at, hp + oB, nh * 4);
-        if (first) std::memcpy(first, hp + oF, 4);
-        if (masks && W) std::memcpy(masks, hp + oM, nh * W * 8);
-        if (o.accepted) std::memcpy(o.accepted, hp + oA, 52);
+        cs.results(call, rM, counts, best_at, first, masks);
+        call.get(rA, o.accepted);
     }
-    if (o.T12) std::memcpy(o.T12, hp + oT12, nh * 48);
-    if (o.T21) std::memcpy(o.T21, hp + oT21, nh * 48);
-    if (o.sim3) std::memcpy(o.sim3, hp + oS, nh * 52);
-    if (o.quat) std::memcpy(o.quat, hp + oQ, nh * 16);
-    if (o.sets_out) std::memcpy(o.sets_out, hp + oSet, nh * 12);
+    call.get(rT12, o.T12);
+    call.get(rT21, o.T21);
+    call.get(rS, o.sim3);
+    call.get(rQ, o.quat);
+    call.get(rSet, o.sets_out);
     return ORB_OK;
 }
 
@@ -1186,22 +1161,6 @@ int launch_pnp(const ConsArgs& a, const PnpArgs& y, bool score, hipStream_t st) 
     return ORB_OK;
 }
 
-// Exactly one of sets / rand31 (n_hyp x 4), every value in range (the host forms).
-int check_draws4(const char* who, int n, int n_hyp, const int32_t* sets, const int32_t* rand31) {
-    if ((sets != nullptr) == (rand31 != nullptr))
-        return fail(ORB_EINVAL, std::string(who) + ": exactly one of sets and rand31 must be given");
-    const int32_t* v = sets ? sets : rand31;
-    for (size_t k = 0; k < (size_t)n_hyp * 4; ++k) {
-        if (sets && n > 0 && (v[k] < 0 || v[k] >= n))
-            return fail(ORB_EINVAL, std::string(who) + ": sets[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
-                                        " is outside [0, n)");
-        if (rand31 && v[k] < 0)
-            return fail(ORB_EINVAL, std::string(who) + ": rand31[" + std::to_string(k) + "] = " + std::to_string(v[k]) +
-                                        " is outside [0, 2^31)");
-    }
-    return ORB_OK;
-}
-
 struct PnpHost {  // the host outputs, each may be NULL
     double* R;
     double* t;
@@ -1222,102 +1181,69 @@ enum { PNP_HYP = 0, PNP_RANSAC = 1, PNP_POSE_N = 2 };
 int run_host_pnp(ConsArgs a, int mode, int n, const float* p3d, const float* p2d, const float* sigma2,
                  const int32_t* sets, const int32_t* rand31, const int32_t* sel, int n_sel, const PnpHost& o,
                  int32_t* counts, uint64_t* masks, int32_t* best_at, int32_t* first, int best_in, int device) {
-    int ndev = 0;
-    ORB_HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0) ORB_HIPCHK(hipGetDevice(&device));
-    OrbHostCtx* C = device < ndev ? orb_internal_thread_ctx(device) : nullptr;
-    if (!C) return fail(ORB_EINVAL, "device ordinal out of range");
-    ORB_HIPCHK(hipSetDevice(device));
     const int n_hyp = a.n_hyp, W = (n + 63) / 64, cap = std::max(n, 1);
-    const size_t nh = (size_t)n_hyp;
-    // staging: in  [p3d | p2d | sigma2 | draws | sel | best_in]
-    //          out [counts | best_at | first, n | R | t | rep | sets | refined counts | first_refined, inliers |
-    //               pose | pose mask | masks]
-    //          then, device only, [refined R | refined t | refined masks | the SoA scratch]
-    const size_t o1 = 0, o2 = al(o1 + (size_t)n * 12), o3 = al(o2 + (size_t)n * 8), oD = al(o3 + (size_t)n * 4),
-                 oL = al(oD + nh * 16), oI = al(oL + (size_t)n_sel * 4), in_end = al(oI + 4);
-    const size_t oC = in_end, oB = al(oC + nh * 4), oF = al(oB + nh * 4), oR = al(oF + 8), oT = al(oR + nh * 72),
-                 oE = al(oT + nh * 24), oSet = al(oE + nh * 8), oRC = al(oSet + nh * 16), oFR = al(oRC + nh * 4),
-                 oP = al(oFR + 8), oPM = al(oP + 48), oM = al(oPM + (size_t)W * 8), out_end = al(oM + nh * W * 8);
-    const size_t oRR = out_end, oRT = al(oRR + nh * 72), oRM = al(oRT + nh * 24), oSoa = al(oRM + nh * W * 8),
-                 total = al(oSoa + (size_t)NV_PNP * cap * 4);
-    if (int r = C->reserve(total, out_end)) return r;
-    uint8_t* hp = C->pinned;
-    if (n) {
-        std::memcpy(hp + o1, p3d, (size_t)n * 12);
-        std::memcpy(hp + o2, p2d, (size_t)n * 8);
-        if (sigma2) std::memcpy(hp + o3, sigma2, (size_t)n * 4); else std::memset(hp + o3, 0, (size_t)n * 4);
-    }
-    if (sets || rand31) std::memcpy(hp + oD, sets ? sets : rand31, nh * 16);
-    if (n_sel) std::memcpy(hp + oL, sel, (size_t)n_sel * 4);
-    std::memcpy(hp + oI, &best_in, 4);
-    ORB_HIPCHK(hipMemcpyAsync(C->buf, hp, in_end, hipMemcpyHostToDevice, C->stream));
-    uint8_t* d = C->buf;
-    a.c0 = (const float*)(d + o1);
-    a.c1 = (const float*)(d + o2);
-    a.c2 = (const float*)(d + o3);
-    a.n_direct = n;
-    a.best_in = (const int32_t*)(d + oI);
-    a.soa = (float*)(d + oSoa);
-    a.counts = (int32_t*)(d + oC);
-    a.best_at = (int32_t*)(d + oB);
-    a.first = (int32_t*)(d + oF);
-    a.n = a.first + 1;
-    a.index = nullptr;
-    a.masks = W ? (uint64_t*)(d + oM) : nullptr;
-    a.cap = cap;
-    a.S = 1;
-    a.W = W;
+    const size_t N = (size_t)n, nh = (size_t)n_hyp;
+    OrbStagePlan P;
+    const auto r1 = P.in<float>(N * 3), r2 = P.in<float>(N * 2), r3 = P.in<float>(N);
+    const auto rD = P.in<int32_t>(nh * 4), rL = P.in<int32_t>(n_sel);
+    const ConsStage cs(P, nh);
+    const auto rR = P.out<double>(nh * 9), rT = P.out<double>(nh * 3), rE = P.out<double>(nh);
+    const auto rSet = P.out<int32_t>(nh * 4), rRC = P.out<int32_t>(nh), rFR = P.out<int32_t>(2);  // first_refined, inliers
+    const auto rP = P.out<float>(12);
+    const auto rPM = P.out<uint64_t>(W), rM = P.out<uint64_t>(nh * W);
+    const auto rRR = P.scratch<double>(nh * 9), rRT = P.scratch<double>(nh * 3);  // the refined poses and masks
+    const auto rRM = P.scratch<uint64_t>(nh * W);
+    const auto rSoa = P.scratch<float>((size_t)NV_PNP * cap);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    a.c0 = call.send(r1, p3d);
+    a.c1 = call.send(r2, p2d);
+    a.c2 = call.send(r3, sigma2);
+    call.put(rL, sel);
+    cs.args(call, a, n, best_in, rM, rSoa);
     PnpArgs y{};
-    if (mode != PNP_POSE_N) (sets ? y.sets : y.rand31) = (const int32_t*)(d + oD);
-    y.R = (double*)(d + oR);
-    y.t = (double*)(d + oT);
-    y.rep = (double*)(d + oE);
-    y.sets_out = (int32_t*)(d + oSet);
-    y.rR = (double*)(d + oRR);
-    y.rt = (double*)(d + oRT);
-    y.rcounts = (int32_t*)(d + oRC);
-    y.rmasks = W ? (uint64_t*)(d + oRM) : nullptr;
-    y.first_refined = (int32_t*)(d + oFR);
+    if (mode != PNP_POSE_N) (sets ? y.sets : y.rand31) = call.send(rD, sets ? sets : rand31);
+    y.R = call.dev(rR);
+    y.t = call.dev(rT);
+    y.rep = call.dev(rE);
+    y.sets_out = call.dev(rSet);
+    y.rR = call.dev(rRR);
+    y.rt = call.dev(rRT);
+    y.rcounts = call.dev(rRC);
+    y.rmasks = W ? call.dev(rRM) : nullptr;  // no pointer to an empty region
+    y.first_refined = call.dev(rFR);
     y.pose_inliers = y.first_refined + 1;
-    y.pose = (float*)(d + oP);
-    y.pose_mask = (uint64_t*)(d + oPM);
+    y.pose = call.dev(rP);
+    y.pose_mask = call.dev(rPM);
+    if (int r = call.upload()) return r;
     int r = ORB_OK;
     hipError_t e = hipSuccess;
     if (mode == PNP_POSE_N) {
-        y.sel = (const int32_t*)(d + oL);
+        y.sel = call.dev(rL);
         y.n_sel = n_sel;
         y.rR = y.R, y.rt = y.t;  // the pose goes where the caller reads R and t
         y.rcounts = nullptr;
-        hipLaunchKernelGGL((k_cons_prepare<PNP>), dim3(1), dim3(CS_PREP_THREADS), 0, C->stream, a);
+        hipLaunchKernelGGL((k_cons_prepare<PNP>), dim3(1), dim3(CS_PREP_THREADS), 0, call.stream(), a);
         e = hipGetLastError();
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_pnp_refine, dim3(1, 1), dim3(64), 0, C->stream, a, y);
+            hipLaunchKernelGGL(k_pnp_refine, dim3(1, 1), dim3(64), 0, call.stream(), a, y);
             e = hipGetLastError();
         }
     } else
-        r = launch_pnp(a, y, mode == PNP_RANSAC, C->stream);
-    if (r == ORB_OK && e == hipSuccess)
-        e = hipMemcpyAsync(hp + oC, d + oC, out_end - oC, hipMemcpyDeviceToHost, C->stream);
-    const hipError_t es = hipStreamSynchronize(C->stream);  // the staging is reused by the next call
-    if (r) return r;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
+        r = launch_pnp(a, y, mode == PNP_RANSAC, call.stream());
+    if (int rf = call.finish(r, e, "solvers: ")) return rf;
     if (mode == PNP_RANSAC) {
-        if (counts) std::memcpy(counts, hp + oC, nh * 4);
-        if (best_at) std::memcpy(best_at, hp + oB, nh * 4);
-        if (first) std::memcpy(first, hp + oF, 4);
-        if (masks && W) std::memcpy(masks, hp + oM, nh * W * 8);
-        if (o.refined_counts) std::memcpy(o.refined_counts, hp + oRC, nh * 4);
-        if (o.first_refined) std::memcpy(o.first_refined, hp + oFR, 4);
-        if (o.pose_inliers) std::memcpy(o.pose_inliers, hp + oFR + 4, 4);
-        if (o.pose) std::memcpy(o.pose, hp + oP, 48);
-        if (o.pose_mask && W) std::memcpy(o.pose_mask, hp + oPM, (size_t)W * 8);
+        cs.results(call, rM, counts, best_at, first, masks);
+        call.get(rRC, o.refined_counts);
+        call.get(rFR, o.first_refined, 1);
+        call.get(rFR, o.pose_inliers, 1, 1);
+        call.get(rP, o.pose);
+        call.get(rPM, o.pose_mask);
     }
-    if (o.R) std::memcpy(o.R, hp + oR, nh * 72);
-    if (o.t) std::memcpy(o.t, hp + oT, nh * 24);
-    if (o.rep) std::memcpy(o.rep, hp + oE, nh * 8);
-    if (o.sets_out && mode != PNP_POSE_N) std::memcpy(o.sets_out, hp + oSet, nh * 16);
+    call.get(rR, o.R);
+    call.get(rT, o.t);
+    call.get(rE, o.rep);
+    if (mode != PNP_POSE_N) call.get(rSet, o.sets_out);
     return ORB_OK;
 }
 
@@ -1331,7 +1257,7 @@ int orb_sim3_compute_hypotheses(int n, const float* x3dc1, const float* x3dc2, i
     const char* who = "sim3_compute_hypotheses";
     if (n < 1 || !x3dc1 || !x3dc2) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (int r = check_limits(who, n, n_hyp)) return r;
-    if (int r = check_draws(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_draws(who, 3, n, n_hyp, sets, rand31)) return r;
     if (rand31 && n < 3) return fail(ORB_EINVAL, std::string(who) + ": a minimal set is drawn from n >= 3 correspondences");
     ConsArgs a{};
     a.K1[0] = a.K1[1] = a.K2[0] = a.K2[1] = 1.0f;
@@ -1351,10 +1277,8 @@ int orb_sim3_ransac(int n, const float* x3dc1, const float* x3dc2, const float* 
     if (n < 0 || (n && (!x3dc1 || !x3dc2 || !sigma2_1 || !sigma2_2)) || !K1 || !K2)
         return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (int r = check_limits(who, n, n_hyp)) return r;
-    if (min_inliers < 3)
-        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 3, the size of a minimal set (got " +
-                                    std::to_string(min_inliers) + ")");
-    if (int r = check_draws(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_min_inliers(who, 3, min_inliers)) return r;
+    if (int r = check_draws(who, 3, n, n_hyp, sets, rand31)) return r;
     if (int r = check_sigma2(who, sigma2_1, n, true)) return r;
     if (int r = check_sigma2(who, sigma2_2, n, true)) return r;
     ConsArgs a{};
@@ -1380,9 +1304,7 @@ int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_c
     if (int r = fill_batch(a, who, d_kps, d_counts, cap, S, d_pair_a, d_pair_b, d_match, d_mp_pos, d_mp_bad,
                            level_sigma2, nlevels, n_hyp, true))
         return r;
-    if (min_inliers < 3)
-        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 3, the size of a minimal set (got " +
-                                    std::to_string(min_inliers) + ")");
+    if (int r = check_min_inliers(who, 3, min_inliers)) return r;
     if (S == 0) return ORB_OK;
     if (!d_pose || !K) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (!d_rand31) return fail(ORB_EINVAL, std::string(who) + ": no rand31 values given");
@@ -1397,36 +1319,27 @@ int orb_sim3_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_c
     // did not ask for
     const size_t SH = (size_t)S * n_hyp;
     const bool want_acc = d_accepted || d_accepted_mask;
-    const size_t need[9] = {(size_t)S * NV_SIM3 * cap * 4,
-                            d_n ? 0 : (size_t)S * 4,
-                            d_counts_out ? 0 : SH * 4,
-                            d_T12 ? 0 : SH * 48,
-                            d_T21 ? 0 : SH * 48,
-                            d_sim3 || !d_accepted ? 0 : SH * 52,
-                            d_best_at || !want_acc ? 0 : SH * 4,
-                            d_first_accept || !want_acc ? 0 : (size_t)S * 4,
-                            d_masks || !d_accepted_mask ? 0 : SH * a.W * 8};
-    size_t off[10] = {0};
-    for (int k = 0; k < 9; ++k) off[k + 1] = off[k] + al(need[k]);
-    uint8_t* tmp = nullptr;
-    hipError_t e = hipMallocAsync((void**)&tmp, off[9], st);
-    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("solvers: scratch: ") + hipGetErrorString(e));
-    a.soa = (float*)tmp;
-    a.n = d_n ? d_n : (int32_t*)(tmp + off[1]);
-    a.counts = d_counts_out ? d_counts_out : (int32_t*)(tmp + off[2]);
     HypArgs y{};
     y.rand31 = d_rand31;
-    y.T12 = d_T12 ? d_T12 : (float*)(tmp + off[3]);
-    y.T21 = d_T21 ? d_T21 : (float*)(tmp + off[4]);
-    y.sim3 = d_sim3 ? d_sim3 : (need[5] ? (float*)(tmp + off[5]) : nullptr);
     y.sets_out = d_sets_out;
-    a.best_at = d_best_at ? d_best_at : (need[6] ? (int32_t*)(tmp + off[6]) : nullptr);
-    a.first = d_first_accept ? d_first_accept : (need[7] ? (int32_t*)(tmp + off[7]) : nullptr);
-    a.masks = d_masks ? d_masks : (need[8] ? (uint64_t*)(tmp + off[8]) : nullptr);
+    void* tmp = nullptr;
+    if (int r = orb_scratch_alloc(&tmp, st, "solvers: scratch: ", [&](OrbLayout& L) {
+            a.soa = L.take<float>((size_t)S * NV_SIM3 * cap);
+            a.n = L.given_or_take(d_n, (size_t)S);
+            a.counts = L.given_or_take(d_counts_out, SH);
+            y.T12 = L.given_or_take(d_T12, SH * 12);
+            y.T21 = L.given_or_take(d_T21, SH * 12);
+            // (NULL where the caller gave none and the accepted hypothesis, which reads them, is not wanted)
+            y.sim3 = d_sim3 ? d_sim3 : d_accepted ? L.take<float>(SH * 13) : nullptr;
+            a.best_at = d_best_at ? d_best_at : want_acc ? L.take<int32_t>(SH) : nullptr;
+            a.first = d_first_accept ? d_first_accept : want_acc ? L.take<int32_t>((size_t)S) : nullptr;
+            a.masks = d_masks ? d_masks : d_accepted_mask ? L.take<uint64_t>(SH * a.W) : nullptr;
+        }))
+        return r;
     int r = launch<SIM3, float>(a, y.T12, y.T21, st, &y);
     if (r == ORB_OK && want_acc) {
         hipLaunchKernelGGL(k_sim3_accepted, dim3(S), dim3(64), 0, st, a, y.sim3, d_accepted, d_accepted_mask);
-        e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess) r = fail(ORB_EDEVICE, std::string("solvers: ") + hipGetErrorString(e));
     }
     (void)hipFreeAsync(tmp, st);
@@ -1439,7 +1352,7 @@ int orb_pnp_compute_hypotheses(int n, const float* p3d, const float* p2d, double
     const char* who = "pnp_compute_hypotheses";
     if (n < 1 || !p3d || !p2d) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (int r = check_limits(who, n, n_hyp)) return r;
-    if (int r = check_draws4(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_draws(who, 4, n, n_hyp, sets, rand31)) return r;
     if (rand31 && n < 4) return fail(ORB_EINVAL, std::string(who) + ": a minimal set is drawn from n >= 4 correspondences");
     ConsArgs a{};
     a.fu = fu, a.fv = fv, a.uc = uc, a.vc = vc;
@@ -1477,10 +1390,8 @@ int orb_pnp_ransac(int n, const float* p3d, const float* p2d, const float* sigma
     const char* who = "pnp_ransac";
     if (n < 0 || (n && (!p3d || !p2d || !sigma2))) return fail(ORB_EINVAL, std::string(who) + ": bad arguments");
     if (int r = check_limits(who, n, n_hyp)) return r;
-    if (min_inliers < 4)
-        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 4, the size of a minimal set (got " +
-                                    std::to_string(min_inliers) + ")");
-    if (int r = check_draws4(who, n, n_hyp, sets, rand31)) return r;
+    if (int r = check_min_inliers(who, 4, min_inliers)) return r;
+    if (int r = check_draws(who, 4, n, n_hyp, sets, rand31)) return r;
     if (int r = check_sigma2(who, sigma2, n, false)) return r;
     ConsArgs a{};
     a.th2 = th2;
@@ -1506,9 +1417,7 @@ int orb_pnp_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_co
     if (int r = fill_batch(a, who, d_kps, d_counts, cap, S, d_pair_a, d_pair_b, d_match, d_mp_pos, d_mp_bad,
                            level_sigma2, nlevels, n_hyp, false))
         return r;
-    if (min_inliers < 4)
-        return fail(ORB_EINVAL, std::string(who) + ": min_inliers must be at least 4, the size of a minimal set (got " +
-                                    std::to_string(min_inliers) + ")");
+    if (int r = check_min_inliers(who, 4, min_inliers)) return r;
     if (S == 0) return ORB_OK;
     if (!d_rand31) return fail(ORB_EINVAL, std::string(who) + ": no rand31 values given");
     hipStream_t st = (hipStream_t)stream;
@@ -1520,41 +1429,29 @@ int orb_pnp_ransac_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_co
     // stream-ordered scratch for the SoA values, the refined poses and masks, and for every array the
     // chain needs and the caller did not ask for
     const size_t SH = (size_t)S * n_hyp;
-    const size_t need[11] = {(size_t)S * NV_PNP * cap * 4,
-                             d_n ? 0 : (size_t)S * 4,
-                             d_counts_out ? 0 : SH * 4,
-                             d_R ? 0 : SH * 72,
-                             d_t ? 0 : SH * 24,
-                             d_best_at ? 0 : SH * 4,
-                             d_masks ? 0 : SH * a.W * 8,
-                             d_refined_counts ? 0 : SH * 4,
-                             SH * 72,
-                             SH * 24,
-                             SH * a.W * 8};
-    size_t off[12] = {0};
-    for (int k = 0; k < 11; ++k) off[k + 1] = off[k] + al(need[k]);
-    uint8_t* tmp = nullptr;
-    hipError_t e = hipMallocAsync((void**)&tmp, off[11], st);
-    if (e != hipSuccess) return fail(ORB_ENOMEM, std::string("solvers: scratch: ") + hipGetErrorString(e));
-    a.soa = (float*)tmp;
-    a.n = d_n ? d_n : (int32_t*)(tmp + off[1]);
-    a.counts = d_counts_out ? d_counts_out : (int32_t*)(tmp + off[2]);
     PnpArgs y{};
     y.rand31 = d_rand31;
-    y.R = d_R ? d_R : (double*)(tmp + off[3]);
-    y.t = d_t ? d_t : (double*)(tmp + off[4]);
     y.sets_out = d_sets_out;
-    a.best_at = d_best_at ? d_best_at : (int32_t*)(tmp + off[5]);
     a.first = d_first_ok;
-    a.masks = d_masks ? d_masks : (uint64_t*)(tmp + off[6]);
-    y.rcounts = d_refined_counts ? d_refined_counts : (int32_t*)(tmp + off[7]);
-    y.rR = (double*)(tmp + off[8]);
-    y.rt = (double*)(tmp + off[9]);
-    y.rmasks = (uint64_t*)(tmp + off[10]);
     y.first_refined = d_first_refined;
     y.pose = d_pose;
     y.pose_mask = d_pose_mask;
     y.pose_inliers = d_pose_inliers;
+    void* tmp = nullptr;
+    if (int r = orb_scratch_alloc(&tmp, st, "solvers: scratch: ", [&](OrbLayout& L) {
+            a.soa = L.take<float>((size_t)S * NV_PNP * cap);
+            a.n = L.given_or_take(d_n, (size_t)S);
+            a.counts = L.given_or_take(d_counts_out, SH);
+            y.R = L.given_or_take(d_R, SH * 9);
+            y.t = L.given_or_take(d_t, SH * 3);
+            a.best_at = L.given_or_take(d_best_at, SH);
+            a.masks = L.given_or_take(d_masks, SH * a.W);
+            y.rcounts = L.given_or_take(d_refined_counts, SH);
+            y.rR = L.take<double>(SH * 9);
+            y.rt = L.take<double>(SH * 3);
+            y.rmasks = L.take<uint64_t>(SH * a.W);
+        }))
+        return r;
     const int r = launch_pnp(a, y, true, st);
     (void)hipFreeAsync(tmp, st);
     return r;

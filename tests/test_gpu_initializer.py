@@ -106,6 +106,18 @@ def test_keypoint_counts_and_holes(N, n1, n2):
     assert want["n_matches"] == N
 
 
+def test_staging_reuse_across_sizes():
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and a pair without keypoints, each against the model; n1 != n2 and both
+    below the larger, so the padding between a frame's count and the capacity is read."""
+    for N, n_hyp, n1, n2 in [(40, 1, 65, 50), (100, 65, 110, 130), (1, 1, 1, 3)]:
+        got, want = run_host(*synth_case(N, n_hyp, n1, n2))
+        assert want["n_matches"] == N
+    e, h = np.zeros(0, KEYPOINT_DTYPE), np.zeros((1, 9), f32)
+    got, want = run_host(e, e, np.zeros(0, np.int32), h, h, h)
+    assert want["n_matches"] == 0
+
+
 def test_sigma():
     k1, k2, m12, H21, H12, F21 = synth_case(129, 65)
     a, _ = run_host(k1, k2, m12, H21, H12, F21, 0.7)

@@ -133,6 +133,22 @@ def test_zero_deviation_in_x():
     assert got["n_matches"] == 0 and got["best_h"] == -1
 
 
+def test_staging_reuse_across_sizes():
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and a pair without keypoints, each against the model, for the whole
+    RANSAC and for the hypotheses alone; n1 != n2 and both below the larger of a later call, so the
+    padding between a frame's count and the capacity is read."""
+    e = np.zeros(0, KEYPOINT_DTYPE)
+    seq = [(*two_view_case(40, 65, 50), 1), (*two_view_case(100, 110, 130), 65), (*two_view_case(9, 12, 10), 1),
+           (e, e, np.zeros(0, np.int32), 1)]
+    for k1, k2, m12, n_hyp in seq:
+        r31 = draws(n_hyp, len(k1))
+        got, want = run_find(k1, k2, m12, r31)
+        assert got["n_matches"] == int((m12 >= 0).sum()) and len(got["inliers_h"]) == got["n_matches"]
+        h = orb.InitializerRansac().compute_hypotheses(k1, k2, m12, rand31=r31)
+        same_hypotheses(h, model.hypotheses(k1, k2, m12, rand31=r31))
+
+
 def test_find_equals_compute_hypotheses_then_check_and_the_model():
     k1, k2, m12 = two_view_case(100)
     r31 = draws(200, 8)

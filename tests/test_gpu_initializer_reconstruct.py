@@ -195,6 +195,20 @@ def test_gate_failure_nan_model_and_too_few_matches():
     assert got["n_matches"] == 7 and got["best_h"] == -1 and not got["ok"] and got["n_inliers"] == 0
 
 
+def test_staging_reuse_across_sizes():
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and a pair without keypoints, each against the model; the frames hold
+    different numbers of keypoints, so the padding between a count and the capacity is read."""
+    for name in ("f60", "f130", "f60"):
+        s = scene(name)
+        assert len(s["k1"]) != len(s["k2"])
+        got, _ = run(s["k1"], s["k2"], s["m12"], s["M21"], s["use_h"], scenes.mask_first(s["m12"], 10 ** 6))
+        assert got["ok"] and len(got["P3D"]) == len(s["k1"])
+    none = np.zeros((0, 2), f32)
+    got, _ = run(none, none, np.zeros(0, np.int32), np.eye(3, dtype=f32), False, np.zeros(0, np.uint8))
+    assert not got["ok"] and got["n_inliers"] == 0
+
+
 @pytest.mark.parametrize("name", scenes.SCENE_NAMES)
 def test_golden_fixture(name):
     g = {k[len(name) + 1:]: v for k, v in GOLD.items() if k.startswith(name + ".")}

@@ -167,6 +167,42 @@ def test_ransac_equals_model_and_check_inliers_on_its_own_poses(golden):
     assert int(ck["counts"][0]) == it["pose_inliers"]
 
 
+def iterate_against_model(n, n_hyp, seed, K=(260.0, 260.0, 160.0, 120.0)):
+    """orb_pnp_ransac on n correspondences of a scene against the model, every output bit for bit."""
+    p3, p2, s2 = ransac_of(max(n, 4), seed)
+    p3, p2, s2 = p3[:n], p2[:n], s2[:n]
+    r = np.random.default_rng(seed + n).integers(0, 2 ** 31, (n_hyp, 4)).astype(np.int32)
+    it = orb.PnPRansac(*K, min_inliers=10, th2=float(TH2)).iterate(p3, p2, s2, rand31=r)
+    check_ransac(it, pm.ransac(p3, p2, s2, TH2, np.float64(K), 10, rand31=r), f"n = {n}: ")
+    return it
+
+
+def test_staging_reuse_across_sizes():
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and the empty input, each against the model: a layout that leans on
+    what an earlier call left in the staging, or on where the arena was before it grew, fails.  Then
+    the n-point pose, which shares the arena and lays it out with a selection list."""
+    for n, n_hyp in [(65, 1), (130, 65), (1, 1), (0, 1)]:
+        it = iterate_against_model(n, n_hyp, 5)
+        assert it["masks"].shape == (n_hyp, (n + 63) // 64) and it["pose_mask"].shape == ((n + 63) // 64,)
+    test_n_point_pose(65)
+
+
+def test_three_entry_points_share_one_arena():
+    """PnP RANSAC at the large size, then the initializer's RANSAC on a small pair, then OptimizeSim3, on
+    one thread: each against its own model, so a layout that reads what another entry point left in
+    the arena or the staging fails."""
+    import sim3_optimization_model as s3m
+    import test_gpu_initializer_ransac as tir
+    import test_gpu_sim3_optimization as tso
+
+    iterate_against_model(130, 65, 5)
+    k1, k2, m12 = tir.two_view_case(40, 65, 50)
+    tir.run_find(k1, k2, m12, tir.draws(1, 3))
+    c = s3m.host_cases()["pairs_65"]
+    tso.same_as_model(tso.run_host(orb.Optimizer(0), c), c["model"], "after two other entry points")
+
+
 # (seed, min_inliers, the replacing iterations, their refined counts, first_refined) found with the model
 REFINE_CASES = {"equal: Refine fails": (5, 20, [31], [20], -1),
                 "one more: Refine succeeds": (5, 19, [31], [20], 31),

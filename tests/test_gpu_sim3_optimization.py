@@ -173,6 +173,15 @@ def test_same_call_twice_gives_the_same_bytes(opt, cases):
         assert a["info"] == b["info"]
 
 
+def test_staging_reuse_across_sizes(opt, cases):
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and the empty input, each against the model: a layout that leans on
+    what an earlier call left in the staging, or on where the arena was before it grew, fails."""
+    seq = [cases["pairs_65"], s3m.make_case(230, 130, outliers=0.1), cases["pairs_1"], cases["pairs_0"]]
+    for c in seq:
+        same_as_model(run_host(opt, c), c["model"], f"reuse, n = {len(c['x3dc1'])}")
+
+
 def test_refusals_and_the_call_after(opt, cases):
     def code(fn):
         with pytest.raises(_native.OrbError) as e:

@@ -197,6 +197,36 @@ def test_ransac_equals_check_inliers_on_its_own_hypotheses_and_the_model(golden)
     assert not it["T12"].any() and not it["T21"].any() and not it["sim3"].any() and not it["masks"].any()
 
 
+def iterate_against_model(golden, n, n_hyp, seed):
+    """orb_sim3_ransac on the first n points of a cloud: the sets and the quaternion bit for bit, the
+    hypotheses and the accepted one within the fixture's bound (0), the consensus exact."""
+    tol = {k: float(golden["tol_" + k]) for k in ("T12", "T21", "sim3")}
+    c = s3.cloud(130, seed=seed, outliers=0.3)
+    a = tuple(c[k][:n] for k in ("x3dc1", "x3dc2", "sigma2_1", "sigma2_2"))
+    r = draws(n, n_hyp, seed)
+    rs = orb.Sim3Ransac(K_SMALL, None, 10)
+    it = rs.iterate(*a, rand31=r)
+    want = s3.iterate(*a, K_SMALL, K_SMALL, r, 10)
+    model.same_result(it, want, "first_accept")
+    assert np.array_equal(it["sets"], want["sets"]), f"sets, n = {n}"
+    for k in ("T12", "T21", "sim3"):
+        close(it[k], want[k], tol[k], f"{k}, n = {n}")
+    close(it["accepted"], want["accepted"], tol["sim3"], f"accepted, n = {n}")
+    if n >= 3:
+        hyp = rs.compute_hypotheses(a[0], a[1], rand31=r)
+        same_bits(hyp["quat"], s3.compute(a[0], a[1], hyp["sets"])["quat"], f"quaternion, n = {n}")
+    return it
+
+
+def test_staging_reuse_across_sizes(golden):
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and the empty input, each against the model: a layout that leans on
+    what an earlier call left in the staging, or on where the arena was before it grew, fails."""
+    for n, n_hyp in [(65, 1), (130, 65), (1, 1), (0, 1)]:
+        it = iterate_against_model(golden, n, n_hyp, 8)
+        assert it["masks"].shape == (n_hyp, (n + 63) // 64)
+
+
 def test_null_outputs_host():
     lib, p = _native.hip_lib(), _native.ptr
     c = s3.cloud(130, seed=8, outliers=0.3)

@@ -69,6 +69,23 @@ def test_hypothesis_counts(n_hyp):
         assert len(set(r["best_at"])) > 2 and len(set(q["best_at"])) > 2
 
 
+REUSE = [(65, 1), (130, 65), (1, 1), (0, 1)]  # (n, n_hyp): mask words 2, 3, 1, 0; one and two tiles of hypotheses
+
+
+@pytest.mark.parametrize("which", ["pnp", "sim3"])
+def test_staging_reuse_across_sizes(which):
+    """One thread, one context: a small call, one large enough to grow the device arena and the pinned
+    staging, a small one again and the empty input, each against the model: a layout that leans on
+    what an earlier call left in the staging, or on where the arena was before it grew, fails."""
+    for n, n_hyp in REUSE:
+        if which == "pnp":
+            r = run_pnp(model.pnp_case(n, n_hyp, seed=n), min_inliers=max(4, n // 3))
+        else:
+            r = run_sim3(model.sim3_case(n, n_hyp, seed=n + 1), min_inliers=max(4, n // 3))
+        assert r["masks"].shape == (n_hyp, (n + 63) // 64)
+        _bits_past_n_are_zero(r)
+
+
 def test_golden_fixture():
     g = np.load(ROOT / "tests" / "golden" / "solvers_320x240.npz")
     r = orb.PnPConsensus(*g["K"], min_inliers=int(g["pnp_min"]), th2=float(g["th2"])).check(
