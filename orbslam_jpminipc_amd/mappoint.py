@@ -1,6 +1,8 @@
 """MapPoint-level helpers over the C ABI (csrc/orb_mappoint.hip)."""
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from ._native import check, hip_lib, ptr
@@ -25,3 +27,19 @@ def compute_distinctive_descriptors(offsets, desc, usable=None, current=None, de
     best = np.full(max(M, 1), -1, np.int32)
     check(hip_lib().orb_compute_distinctive_descriptors(M, ptr(off), ptr(d), ptr(u), ptr(best), ptr(out), device))
     return best[:M], out[:M]
+
+
+def compute_distinctive_descriptors_device(d_offsets, d_desc, d_usable, max_obs, d_best_row, d_out_desc, stream=None):
+    """orb_compute_distinctive_descriptors_device on device tensors: d_offsets (M + 1,) int32,
+    d_desc (R, 32) uint8 (16-byte aligned), d_usable (R,) uint8 or None, max_obs >= the largest
+    offsets[m+1] - offsets[m] (the kernel's LDS is sized from it: the caller must not understate
+    it), d_best_row (M,) int32 and d_out_desc (M, 32) uint8 written in place (rows of points with
+    no usable observation are left alone, best_row -1); enqueued on `stream`."""
+    import torch
+
+    M = int(d_offsets.shape[0]) - 1
+    s = stream if stream is not None else torch.cuda.current_stream(d_offsets.device)
+    check(hip_lib().orb_compute_distinctive_descriptors_device(M, ptr(d_offsets), ptr(d_desc), ptr(d_usable),
+                                                               int(max_obs), ptr(d_best_row), ptr(d_out_desc),
+                                                               ctypes.c_void_p(s.cuda_stream)))
+    return d_best_row, d_out_desc

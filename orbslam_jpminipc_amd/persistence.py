@@ -112,17 +112,24 @@ def save_keyframe_streams(keys_path, des_path, keyframes, keys_un_path=None):
         f.write(db)
 
 
-def pack_keyframe_records_device(d_kps, d_desc, d_counts, stream=None):
+def pack_keyframe_records_device(d_kps, d_desc, d_counts, stream=None, keys=None, des=None):
     """Device batch (orb_extract_batch_device layout) -> (keys_stream, des_stream, key_offsets,
-    des_offsets) uint8 / int64 device tensors; stream lengths are offsets[B]."""
+    des_offsets) uint8 / int64 device tensors; stream lengths are offsets[B].  `keys` / `des`:
+    the caller's own 1-D uint8 stream buffers (at least B full records each, 2-byte aligned);
+    bytes past offsets[B] are not written."""
     import torch
 
     B, cap = int(d_kps.shape[0]), int(d_kps.shape[1])
     dev = d_kps.device
     kcap = B * keypoint_record_bytes(cap)
     dcap = B * descriptor_record_bytes(cap)
-    keys = torch.empty(kcap + (kcap & 1), dtype=torch.uint8, device=dev)
-    des = torch.empty(dcap + (dcap & 1), dtype=torch.uint8, device=dev)
+    if keys is None:
+        keys = torch.empty(kcap + (kcap & 1), dtype=torch.uint8, device=dev)
+    if des is None:
+        des = torch.empty(dcap + (dcap & 1), dtype=torch.uint8, device=dev)
+    for t in (keys, des):
+        if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+            raise TypeError("keys / des must be contiguous 1-D uint8 tensors on d_kps's device")
     ko = torch.empty(B + 1, dtype=torch.int64, device=dev)
     do = torch.empty(B + 1, dtype=torch.int64, device=dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev)

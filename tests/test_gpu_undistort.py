@@ -8,7 +8,10 @@ import pytest
 
 import orbslam_jpminipc_amd as orb
 from orbslam_jpminipc_amd import camera
+import undistort_cases as U
 from oracle_lib import Oracle, compute_image_bounds, search_for_initialization, undistort_keypoints, undistort_points
+
+# (the synthetic [B][cap] batches of test_batch_kernel_off_the_extractor_shapes: tests/undistort_cases.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -185,6 +188,46 @@ def test_batch_k1_zero_copies():
     camera.undistort_keypoints_batch_device(k, c, K_VGA, D_SYN, d_kps_un=k)
     torch.cuda.synchronize()
     assert torch.equal(k, ref)
+
+
+def _run_batch(k, counts, K4, d4, in_place=False):
+    """k_undistort on a synthetic (B, cap) batch -> (input bytes after the call, output bytes), both
+    (B, cap, 28) on the host; the output buffer starts as OUT_SENTINEL bytes (in place: it is the input)."""
+    import torch
+
+    B, cap = k.shape
+    d_kps = torch.from_numpy(k.view(np.uint8).reshape(B, cap, 28).copy()).cuda()
+    d_cnt = torch.tensor(counts, dtype=torch.int32, device="cuda")
+    d_out = d_kps if in_place else torch.full((B, cap, 28), U.OUT_SENTINEL, dtype=torch.uint8, device="cuda")
+    ret = camera.undistort_keypoints_batch_device(d_kps, d_cnt, K4, d4, d_kps_un=d_out)
+    torch.cuda.synchronize()
+    assert ret is d_out
+    return d_kps.cpu().numpy(), d_out.cpu().numpy()
+
+
+@pytest.mark.parametrize("cam", [0, 4])  # a barrel camera and the strong pincushion camera
+@pytest.mark.parametrize("case", range(len(U.CASES)))
+def test_batch_kernel_off_the_extractor_shapes(case, cam):
+    """Capacities 1, 255, 257 and 1000 (no multiple of the 256-thread block), counts 0, 1, cap - 1 and
+    cap, points outside the image and on half-integers: every slot below the count is the oracle's
+    record, all seven fields; every slot from the count on keeps what the output buffer held."""
+    B, cap, counts = U.CASES[case]
+    K4, d4 = CAMS[cam]
+    k = U.make_batch(B, cap, counts)
+    raw = k.view(np.uint8).reshape(B, cap, 28)
+    kin, out = _run_batch(k, counts, K4, d4)
+    assert kin.tobytes() == raw.tobytes()  # the input is only read
+    kin2, inpl = _run_batch(k, counts, K4, d4, in_place=True)
+    for b, n in enumerate(counts):
+        want = undistort_keypoints(k[b, :n], K4, d4).tobytes() if n else b""
+        assert out[b, :n].tobytes() == want, b
+        assert (out[b, n:] == U.OUT_SENTINEL).all(), b
+        assert inpl[b, :n].tobytes() == want, b
+        assert (inpl[b, n:] == U.IN_SENTINEL).all(), b
+    # k1 == 0: the records below the count are copied, nothing else is written
+    kin, out = _run_batch(k, counts, K4, (0.0, 0.05, 0.01, 0.0))
+    for b, n in enumerate(counts):
+        assert out[b, :n].tobytes() == raw[b, :n].tobytes() and (out[b, n:] == U.OUT_SENTINEL).all(), b
 
 
 def test_pipeline_extract_undistort_and_match():

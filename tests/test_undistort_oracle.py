@@ -113,6 +113,36 @@ def test_keypoints_keep_every_other_field():
     assert np.stack([out["x"], out["y"]], 1).tobytes() == np_undistort(xy, K4, d4).tobytes()
 
 
+def test_synthetic_batches_for_the_gpu_kernel():
+    """tests/undistort_cases.py: the batches tests/test_gpu_undistort.py feeds k_undistort."""
+    import undistort_cases as U
+
+    caps = {}
+    for B, cap, counts in U.CASES:
+        assert len(counts) == B and all(0 <= n <= cap for n in counts)
+        caps.setdefault(cap, set()).update(counts)
+        k = U.make_batch(B, cap, counts)
+        raw = k.view(np.uint8).reshape(B, cap, 28)
+        for b, n in enumerate(counts):
+            assert (raw[b, n:] == U.IN_SENTINEL).all()
+            assert n == 0 or not (raw[b, :n] == U.IN_SENTINEL).all(axis=1).any()
+    for cap, seen in caps.items():  # every capacity meets counts 0, 1, cap - 1 and cap
+        assert {0, 1, cap - 1, cap} <= seen, cap
+    assert any(cap % 256 for cap in caps) and 1 in caps
+    k = U.make_batch(3, 257, [257, 257, 257]).reshape(-1)
+    x, y = k["x"], k["y"]
+    assert (x < 0).any() and (y < 0).any() and (x > U.W + 100).any() and (y > U.H + 100).any()
+    half = (x - np.floor(x) == 0.5) & (y - np.floor(y) == 0.5)
+    assert half.sum() >= len(k) // 3
+    for K4, d4 in (CAMERAS[2], CAMERAS[3]):  # a barrel and a pincushion camera: the oracle on these points
+        out = undistort_keypoints(k, K4, d4)
+        xy = np.stack([x, y], 1).astype(np.float32)
+        assert np.stack([out["x"], out["y"]], 1).tobytes() == np_undistort(xy, K4, d4).tobytes()
+        for f in ("size", "angle", "response", "octave", "class_id"):
+            assert out[f].tobytes() == k[f].tobytes()
+        assert out["x"].tobytes() != k["x"].tobytes()
+
+
 def test_image_bounds_barrel_distortion():
     """Barrel distortion (k1 < 0) pulls the undistorted corners outward: the bounds grow past
     the image rectangle, floor / ceil of the corner coordinates (Frame.cc:335-338)."""
