@@ -407,6 +407,97 @@ int orb_compute_distinctive_descriptors_device(int M, const int32_t* d_offsets, 
                                                const uint8_t* d_usable, int max_obs, int32_t* d_best_row,
                                                uint8_t* d_out_desc, void* stream);
 
+/* MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:273-312) for M points: point m is seen
+ * from the camera centres obs_Ow rows offsets[m] .. offsets[m+1]-1 (R x 3, GetCameraCenter of each
+ * observing keyframe), in the order of its std::map<KeyFrame*, size_t> observations: the float
+ * sum of the unit vectors depends on that order, which is the caller's, as for the descriptors.
+ * pos M x 3 (mWorldPos), ref_Ow M x 3 (mpRefKF->GetCameraCenter()), ref_level M (the octave of the
+ * point's keypoint in mpRefKF; clamped to the table), scale_factors / nlevels: the reference
+ * keyframe's mvScaleFactors, one table for the call (2..16 levels: GetScaleFactor() is entry 1).
+ * Outputs, each may be NULL: normal M x 3 (mNormalVector), dmin / dmax M (mfMinDistance,
+ * mfMaxDistance).  A point without an observation yields a NaN normal (the reference's 0 * inf);
+ * mbBad points are the caller's to leave out.  <= 4000 observations per point (ORB_ENOTSUP).
+ * Host buffers, synchronous. */
+int orb_update_normal_and_depth(int M, const int32_t* offsets, const float* obs_Ow, const float* pos,
+                                const float* ref_Ow, const int32_t* ref_level, const float* scale_factors, int nlevels,
+                                float* normal, float* dmin, float* dmax, int device);
+/* The same on device buffers (scale_factors stays a host table); max_obs = the largest row count of
+ * a point: no point is walked further.  Asynchronous on `stream`. */
+int orb_update_normal_and_depth_device(int M, const int32_t* d_offsets, const float* d_obs_Ow, const float* d_pos,
+                                       const float* d_ref_Ow, const int32_t* d_ref_level, const float* scale_factors,
+                                       int nlevels, int max_obs, float* d_normal, float* d_dmin, float* d_dmax,
+                                       void* stream);
+
+/* ---- LocalMapping::CreateNewMapPoints (GPU: csrc/orb_localmap.hip) ----- */
+/* LocalMapping::ComputeF12 (reference src/LocalMapping.cc:474-491) from the two views' Rcw, tcw and
+ * calibration: F12 row-major 3 x 3, the matrix orb_search_for_triangulation takes.  Computed on the
+ * host by the function the kernels use; nothing is refused but a NULL argument. */
+int orb_compute_f12(const orb_frame_view_t* KF1, const orb_frame_view_t* KF2, float* F12);
+
+/* KeyFrame::ComputeSceneMedianDepth(q) (reference src/KeyFrame.cc:659-689): sorted depths[(n - 1) / q]
+ * of the MapPoints of KF (mp_pos n x 3 GetWorldPos, has_mp n: mvpMapPoints[i] != NULL).  A NaN depth
+ * sorts after every number.  With no MapPoint the reference indexes an empty vector: ORB_EINVAL.
+ * Host buffers, synchronous. */
+int orb_scene_median_depth(const orb_frame_view_t* KF, const float* mp_pos, const uint8_t* has_mp, int q, float* depth,
+                           int device);
+/* The same for B keyframes on device buffers: d_counts B (clamped to [0, cap]), d_pose B x 12 (Rcw
+ * row-major, tcw), d_mp_pos B x cap x 3, d_has_mp B x cap.  d_depth B (NaN for a keyframe without a
+ * MapPoint) and d_n B (the number of depths) may be NULL.  cap <= 8192, B <= 65535.  Asynchronous on
+ * `stream`. */
+int orb_scene_median_depth_batch_device(const int32_t* d_counts, int cap, int B, const float* d_pose,
+                                        const float* d_mp_pos, const uint8_t* d_has_mp, int q, float* d_depth,
+                                        int32_t* d_n, void* stream);
+
+/* The body of CreateNewMapPoints' neighbour loop for one pair (reference src/LocalMapping.cc:256-265,
+ * 276-391): KF1 = mpCurrentKeyFrame, KF2 = the neighbour, match12[i1] = idx2 or -1 as
+ * orb_search_for_triangulation leaves it (an entry outside [-1, n2) is ORB_EINVAL).  The matches are
+ * walked in ascending i1, the order of vMatchedIndices.  mp_pos2 n2 x 3 / has_mp2 n2 (KF2's MapPoints, as
+ * for orb_scene_median_depth) feed the baseline gate, baseline / ComputeSceneMedianDepth(2) < 0.01; both
+ * NULL: no gate.  Outputs, each may be NULL:
+ *   x3d n1 x 3      the point of slot i1 where the match got as far as the Euclidean point (status 1
+ *                   and 4..9), zeros elsewhere
+ *   status n1       0 no match, 1 accepted (the reference creates a MapPoint), 2 ray parallax, 3 w == 0,
+ *                   4 z1 <= 0, 5 z2 <= 0, 6 reprojection in KF1, 7 reprojection in KF2, 8 a zero
+ *                   distance, 9 scale ratio: the statement that ended the match
+ *   cos_rays n1     cosParallaxRays of every match, NaN elsewhere
+ *   n_new, new_idx1 / new_idx2 n1: the accepted pairs, dense, ascending i1, -1 past n_new
+ *   skipped         0, or 1: the baseline gate's `continue` (nothing is triangulated, n_new = 0)
+ *   median_depth    ComputeSceneMedianDepth(2) of KF2 where the gate ran, NaN otherwise
+ * A NaN fails no comparison of the reference, so a NaN point passes every gate and is reported
+ * accepted; a non-finite Rcw, tcw, Ow or calibration value is therefore refused here (ORB_EINVAL, naming
+ * the argument), as is a gate on a KF2 without a MapPoint.  An octave outside the level table is clamped.
+ * n <= 8192 (ORB_ENOTSUP), nlevels 2..16 (GetScaleFactor() is entry 1 of scale_factors).
+ * Host buffers, synchronous. */
+int orb_create_new_map_points(const orb_frame_view_t* KF1, const orb_frame_view_t* KF2, const int32_t* match12,
+                              const float* mp_pos2, const uint8_t* has_mp2, float* x3d, uint8_t* status,
+                              float* cos_rays, int32_t* n_new, int32_t* new_idx1, int32_t* new_idx2, int32_t* skipped,
+                              float* median_depth, int device);
+/* P pairs on device-resident data, laid out as for orb_optimize_sim3_batch_device: pair p = keyframes
+ * (d_pair_a[p] = current, d_pair_b[p] = neighbour) of a batch (d_kps / d_counts, capacity cap; the
+ * undistorted records), row p of d_match (P x cap, d_match[p][i1] = idx2), d_pose B x 12 (Rcw
+ * row-major, tcw); the camera centres are -Rcw.t()*tcw computed as the reference's one gemm.
+ * d_mp_pos B x cap x 3 and d_has_mp B x cap feed the baseline gate on keyframe d_pair_b[p]; both NULL:
+ * no gate.  scale_factors / level_sigma2: nlevels (2..16) host floats, K4: fx, fy, cx, cy, one table and
+ * one calibration for the call.  Outputs as above with rows of cap, each may be NULL: d_x3d P x cap x 3,
+ * d_status P x cap, d_cos_rays P x cap, d_n_new P, d_new_idx1 / d_new_idx2 P x cap, d_skipped P (2: the
+ * neighbour holds no MapPoint, where the reference indexes an empty vector; nothing is triangulated),
+ * d_median_depth P (written only where the gate runs; NaN with skipped = 2), d_F12 P x 9 (ComputeF12 of
+ * the pair, skipped or not).  Rows are written whole.
+ * The match rows are taken as given because the reference's neighbour loop is sequential: a slot of
+ * the current keyframe that neighbour i filled is not matched by neighbour i + 1, so the rows of one
+ * current keyframe cannot be produced in one matching batch without that dependence.
+ * A match entry outside [0, d_counts[b]), or at an index >= d_counts[a], is no match.  The batch form
+ * cannot see its device-resident poses: a non-finite one ends as NaN points reported accepted, every
+ * loop being bounded.  The pair indices are the caller's to keep in range.  cap <= 8192, P <= 65535
+ * (ORB_ENOTSUP).  Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_create_new_map_points_batch_device(const orb_keypoint_t* d_kps, const int32_t* d_counts, int cap, int P,
+                                           const int32_t* d_pair_a, const int32_t* d_pair_b, const int32_t* d_match,
+                                           const float* d_pose, const float* d_mp_pos, const uint8_t* d_has_mp,
+                                           const float* scale_factors, const float* level_sigma2, int nlevels,
+                                           const float* K4, float* d_x3d, uint8_t* d_status, float* d_cos_rays,
+                                           int32_t* d_n_new, int32_t* d_new_idx1, int32_t* d_new_idx2,
+                                           int32_t* d_skipped, float* d_median_depth, float* d_F12, void* stream);
+
 /* ---- keyframe feature records of the reference's map files (csrc/orb_persist.hip) ---- */
 /* SaveWorldToFile / LoadWroldFromFile (reference include/SaveLoadWorld.h:1254, 2463) store each
  * keyframe's features as one record per stream, little-endian as written on x86-64:

@@ -19,6 +19,8 @@
 // keep-the-best rule of iterate over poses the caller has computed.  gpu::Optimizer::PoseOptimization
 // is Optimizer::PoseOptimization (include/Optimizer.h), the motion-only optimisation, whole, and
 // gpu::Optimizer::OptimizeSim3 is Optimizer::OptimizeSim3, the 7-DoF optimisation of a loop candidate.
+// gpu::LocalMapping is the arithmetic of LocalMapping::CreateNewMapPoints (ComputeF12, the triangulation
+// and its gates) and MapPoint::UpdateNormalAndDepth.
 //
 // Error behaviour: the reference asserts on bad input (ORBextractor.cc:725) and has no
 // status codes; the facade throws std::runtime_error carrying orb_last_error() for any
@@ -939,6 +941,63 @@ public:
         // the reference copies the estimate out only past its early return (Optimizer.cc:1887-1888, 1914)
         if (inf.more_iterations != 0) std::copy(out, out + 13, S12);
         return nIn;
+    }
+};
+
+// LocalMapping::CreateNewMapPoints' arithmetic over POD views (LocalMapping.cc:227-393, 474-491) and
+// MapPoint::UpdateNormalAndDepth (MapPoint.cc:273-312).  The thread, the map mutation, the culling and
+// local BA stay with the caller: outputs are indices and points, where the reference calls
+// `new MapPoint(x3D, ...)`, AddObservation and AddMapPoint.
+class LocalMapping {
+public:
+    // ComputeF12(pKF1, pKF2): row-major 3 x 3, the matrix ORBmatcher::SearchForTriangulation takes.
+    static void ComputeF12(const orb_frame_view_t& KF1, const orb_frame_view_t& KF2, float F12[9]) {
+        orb_check(orb_compute_f12(&KF1, &KF2, F12));
+    }
+
+    // The neighbour-loop body for one pair past the matcher (lines 276-391): vMatches12[i1] = idx2 or -1.
+    // vMatchedIndices: the accepted (idx1, idx2), in the order the reference creates its MapPoints;
+    // vX3D: their points, 3 floats each.  mpPos2 / hasMp2 (KF2's MapPoints, or NULL) feed the baseline gate
+    // of lines 258-265.  Returns false when that gate skips the pair.
+    static bool CreateNewMapPoints(const orb_frame_view_t& KF1, const orb_frame_view_t& KF2,
+                                   const std::vector<int>& vMatches12, const float* mpPos2, const uint8_t* hasMp2,
+                                   std::vector<std::pair<int, int> >& vMatchedIndices, std::vector<float>& vX3D,
+                                   std::vector<uint8_t>* vStatus = nullptr, int device = 0) {
+        const size_t n1 = (size_t)KF1.n;
+        if (vMatches12.size() != n1) throw std::invalid_argument("vMatches12 must have one entry per KF1 keypoint");
+        std::vector<int32_t> m(vMatches12.begin(), vMatches12.end()), i1(n1), i2(n1);
+        std::vector<float> x(3 * n1);
+        std::vector<uint8_t> st(n1);
+        int32_t nNew = 0, skipped = 0;
+        orb_check(orb_create_new_map_points(&KF1, &KF2, m.data(), mpPos2, hasMp2, x.data(), st.data(), nullptr, &nNew,
+                                            i1.data(), i2.data(), &skipped, nullptr, device));
+        vMatchedIndices.clear();
+        vX3D.clear();
+        for (int k = 0; k < nNew; ++k) {
+            vMatchedIndices.push_back(std::make_pair((int)i1[k], (int)i2[k]));
+            vX3D.insert(vX3D.end(), x.begin() + 3 * i1[k], x.begin() + 3 * i1[k] + 3);
+        }
+        if (vStatus) *vStatus = st;
+        return skipped == 0;
+    }
+
+    // MapPoint::UpdateNormalAndDepth for M points with their observations as CSR (orb_abi.h states the
+    // order): normal M x 3, dmin / dmax M.
+    static void UpdateNormalAndDepth(const std::vector<int32_t>& offsets, const std::vector<float>& obsOw,
+                                     const std::vector<float>& pos, const std::vector<float>& refOw,
+                                     const std::vector<int32_t>& refLevel, const std::vector<float>& scaleFactors,
+                                     std::vector<float>& normal, std::vector<float>& dmin, std::vector<float>& dmax,
+                                     int device = 0) {
+        const size_t M = refLevel.size();
+        if (offsets.size() != M + 1 || pos.size() != 3 * M || refOw.size() != 3 * M ||
+            (M && obsOw.size() != 3 * (size_t)offsets[M]))
+            throw std::invalid_argument("UpdateNormalAndDepth: array sizes disagree");
+        normal.assign(3 * M, 0.0f);
+        dmin.assign(M, 0.0f);
+        dmax.assign(M, 0.0f);
+        orb_check(orb_update_normal_and_depth((int)M, offsets.data(), obsOw.data(), pos.data(), refOw.data(),
+                                              refLevel.data(), scaleFactors.data(), (int)scaleFactors.size(),
+                                              normal.data(), dmin.data(), dmax.data(), device));
     }
 };
 

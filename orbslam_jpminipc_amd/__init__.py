@@ -16,6 +16,7 @@ from .extractor import ORBextractor, keypoints_from_bytes
 from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
+from .local_mapping import LocalMapping
 from .initializer import Initializer, InitializerRansac, initializer_minimal_sets
 from .optimizer import Optimizer
 from .solvers import (PnPConsensus, PnPRansac, Sim3Consensus, Sim3Ransac, pnp_minimal_sets, pnp_ransac_parameters,
@@ -31,6 +32,7 @@ __all__ = [
     "InitializerRansac",
     "initializer_minimal_sets",
     "Optimizer",
+    "LocalMapping",
     "PnPConsensus",
     "Sim3Consensus",
     "Sim3Ransac",

@@ -168,6 +168,13 @@ HIP_SIGNATURES = {
     "orb_pipeline_profile_read": (_i, [_vp, _vp, _vp, _i]),
     "orb_compute_distinctive_descriptors": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_compute_distinctive_descriptors_device": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "orb_update_normal_and_depth": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "orb_update_normal_and_depth_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "orb_compute_f12": (_i, [_pv, _pv, _vp]),
+    "orb_scene_median_depth": (_i, [_pv, _vp, _vp, _i, _vp, _i]),
+    "orb_scene_median_depth_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "orb_create_new_map_points": (_i, [_pv, _pv] + [_vp] * 11 + [_i]),
+    "orb_create_new_map_points_batch_device": (_i, [_vp, _vp, _i, _i] + [_vp] * 8 + [_i] + [_vp] * 11),
     "orb_keypoint_record_bytes": (ctypes.c_size_t, [ctypes.c_size_t]),
     "orb_descriptor_record_bytes": (ctypes.c_size_t, [_i]),
     "orb_write_keypoint_record": (_i, [_vp, ctypes.c_size_t, _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),

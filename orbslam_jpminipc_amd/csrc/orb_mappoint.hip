@@ -14,6 +14,12 @@
 //                  BestMedian`, ascending i).
 // Integer arithmetic throughout: the reference's float Distances hold integers <= 256 and
 // are converted back to int (vector<int> vDists, 235), exactly.
+//
+// MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:273-312) for many map points at once:
+//
+//   k_normal_depth one lane per map point: the unit vectors towards the observing keyframes'
+//                  centres summed in observation order, then the two distance bounds from the
+//                  reference keyframe (IEEE f32 / f64, nothing fuses).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,9 +95,122 @@ __global__ void __launch_bounds__(64) k_distinctive(const int32_t* __restrict__ 
     if (lane < 8) ((uint32_t*)(outDesc + (size_t)m * 32))[lane] = s_d[(size_t)bi * 8 + lane];
 }
 
+// MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:273-312), DESIGN.md §20: one lane per
+// point, the observations walked in the caller's order (the float sum depends on it).
+struct NdTables {
+    float sf[ORB_MAX_VIEW_LEVELS];
+    int nlevels, max_obs;
+};
+
+__device__ __forceinline__ double nd_norm3(const float* v) {
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s += (double)v[k] * (double)v[k];
+    return __builtin_sqrt(s);
+}
+
+__global__ void __launch_bounds__(64) k_normal_depth(int M, const int32_t* __restrict__ offsets,
+                                                     const float* __restrict__ obsOw, const float* __restrict__ pos,
+                                                     const float* __restrict__ refOw,
+                                                     const int32_t* __restrict__ refLevel, NdTables t,
+                                                     float* __restrict__ normalOut, float* __restrict__ dmin,
+                                                     float* __restrict__ dmax) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= M) return;
+    float P[3], normal[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) P[k] = pos[(size_t)m * 3 + k];
+    const int r0 = offsets[m];
+    const int n = min(max(offsets[m + 1] - r0, 0), t.max_obs);
+    for (int r = r0; r < r0 + n; ++r) {
+        float normali[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) normali[k] = P[k] - obsOw[(size_t)r * 3 + k];
+        // normal + normali/norm: one addWeighted_<float, double>(normali, 1./norm, normal, 1, 0)
+        const double alpha = 1. / nd_norm3(normali);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) normal[k] = (float)((double)normali[k] * alpha + (double)normal[k] * 1.0 + 0.0);
+    }
+    float PC[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) PC[k] = P[k] - refOw[(size_t)m * 3 + k];
+    const float dist = (float)nd_norm3(PC);
+    const int level = min(max(refLevel[m], 0), t.nlevels - 1);
+    const float scaleFactor = t.sf[1];  // GetScaleFactor(): the level-1 entry
+    const float levelScaleFactor = t.sf[level];
+    if (dmin) dmin[m] = (1.0f / scaleFactor) * dist / levelScaleFactor;
+    if (dmax) dmax[m] = scaleFactor * dist * t.sf[t.nlevels - 1 - level];
+    if (normalOut) {  // normal/n: a MatExpr scale, x * (float)(1./n) + (float)0; n == 0 gives 0 * inf
+        const float a = (float)(1. / (double)n);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) normalOut[(size_t)m * 3 + k] = normal[k] * a + 0.0f;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int orb_update_normal_and_depth_device(int M, const int32_t* d_offsets, const float* d_obs_Ow, const float* d_pos,
+                                       const float* d_ref_Ow, const int32_t* d_ref_level, const float* scale_factors,
+                                       int nlevels, int max_obs, float* d_normal, float* d_dmin, float* d_dmax,
+                                       void* stream) {
+    const std::string w = "update normal and depth: ";
+    if (M < 0 || max_obs < 0 || !scale_factors) return fail(ORB_EINVAL, w + "bad arguments");
+    if (nlevels < 1 || nlevels > ORB_MAX_VIEW_LEVELS)
+        return fail(ORB_EINVAL, w + "nlevels = " + std::to_string(nlevels) + " is not in 1..16");
+    if (nlevels < 2) return fail(ORB_ENOTSUP, w + "nlevels = 1: the reference reads the level-1 scale factor");
+    if (max_obs > DD_MAX_OBS) return fail(ORB_ENOTSUP, w + "more than 4000 observations of one map point");
+    if (M == 0) return ORB_OK;
+    if (!d_offsets || !d_pos || !d_ref_Ow || !d_ref_level || (max_obs > 0 && !d_obs_Ow))
+        return fail(ORB_EINVAL, w + "bad arguments");
+    NdTables t{};
+    for (int k = 0; k < nlevels; ++k) t.sf[k] = scale_factors[k];
+    t.nlevels = nlevels, t.max_obs = max_obs;
+    hipLaunchKernelGGL(k_normal_depth, dim3((M + 63) / 64), dim3(64), 0, (hipStream_t)stream, M, d_offsets, d_obs_Ow,
+                       d_pos, d_ref_Ow, d_ref_level, t, d_normal, d_dmin, d_dmax);
+    ORB_HIPCHK(hipGetLastError());
+    return ORB_OK;
+}
+
+int orb_update_normal_and_depth(int M, const int32_t* offsets, const float* obs_Ow, const float* pos,
+                                const float* ref_Ow, const int32_t* ref_level, const float* scale_factors, int nlevels,
+                                float* normal, float* dmin, float* dmax, int device) {
+    const std::string w = "update normal and depth: ";
+    if (M < 0 || (M > 0 && (!offsets || !pos || !ref_Ow || !ref_level))) return fail(ORB_EINVAL, w + "bad arguments");
+    if (M == 0) return ORB_OK;
+    int max_obs = 0;
+    if (offsets[0] != 0) return fail(ORB_EINVAL, w + "offsets[0] must be 0");
+    for (int m = 0; m < M; ++m) {
+        if (offsets[m + 1] < offsets[m]) return fail(ORB_EINVAL, w + "offsets must be non-decreasing");
+        max_obs = std::max(max_obs, offsets[m + 1] - offsets[m]);
+    }
+    const int R = offsets[M];
+    if (R > 0 && !obs_Ow) return fail(ORB_EINVAL, w + "bad arguments");
+    if (max_obs > DD_MAX_OBS) return fail(ORB_ENOTSUP, w + "more than 4000 observations of one map point");
+    OrbStagePlan P;
+    const auto rOff = P.in<int32_t>((size_t)M + 1);
+    const auto rOw = P.in<float>((size_t)R * 3);
+    const auto rPos = P.in<float>((size_t)M * 3), rRef = P.in<float>((size_t)M * 3);
+    const auto rLev = P.in<int32_t>(M);
+    const auto rN = P.out<float>((size_t)M * 3);
+    const auto rMin = P.out<float>(M), rMax = P.out<float>(M);
+    OrbHostCall call(P, device);
+    if (call.err) return call.err;
+    const int32_t* dOff = call.send(rOff, offsets);
+    const float* dOw = call.send(rOw, obs_Ow);
+    const float* dPos = call.send(rPos, pos);
+    const float* dRef = call.send(rRef, ref_Ow);
+    const int32_t* dLev = call.send(rLev, ref_level);
+    if (int r = call.upload()) return r;
+    const int r = orb_update_normal_and_depth_device(M, dOff, dOw, dPos, dRef, dLev, scale_factors, nlevels, max_obs,
+                                                     call.dev(rN), call.dev(rMin), call.dev(rMax), call.stream());
+    if (int rf = call.finish(r, hipSuccess, w)) return rf;
+    call.get(rN, normal);
+    call.get(rMin, dmin);
+    call.get(rMax, dmax);
+    return ORB_OK;
+}
 
 int orb_compute_distinctive_descriptors_device(int M, const int32_t* d_offsets, const uint8_t* d_desc,
                                                const uint8_t* d_usable, int max_obs, int32_t* d_best_row,

@@ -43,3 +43,45 @@ def compute_distinctive_descriptors_device(d_offsets, d_desc, d_usable, max_obs,
                                                                int(max_obs), ptr(d_best_row), ptr(d_out_desc),
                                                                ctypes.c_void_p(s.cuda_stream)))
     return d_best_row, d_out_desc
+
+
+def update_normal_and_depth(offsets, obs_Ow, pos, ref_Ow, ref_level, scale_factors, device: int = 0):
+    """MapPoint::UpdateNormalAndDepth (reference src/MapPoint.cc:273-312) for many points.
+
+    offsets (M + 1,): point m is observed from the camera centres obs_Ow rows offsets[m] ..
+    offsets[m+1]-1 ((R, 3), GetCameraCenter of each observing keyframe), in the order of its
+    observations map: the float sum of the unit vectors depends on that order, which is the caller's.
+    pos (M, 3), ref_Ow (M, 3) the reference keyframe's centre, ref_level (M,) the octave of the point's
+    keypoint there, scale_factors (nlevels,) the reference keyframe's mvScaleFactors.
+    Returns (normal (M, 3), dmin (M,), dmax (M,)) float32; a point without an observation has a NaN
+    normal, as the reference's 0 * inf gives."""
+    off = np.ascontiguousarray(np.asarray(offsets, np.int32))
+    ow = np.ascontiguousarray(np.asarray(obs_Ow, np.float32).reshape(-1, 3))
+    p = np.ascontiguousarray(np.asarray(pos, np.float32).reshape(-1, 3))
+    ro = np.ascontiguousarray(np.asarray(ref_Ow, np.float32).reshape(-1, 3))
+    lv = np.ascontiguousarray(np.asarray(ref_level, np.int32).reshape(-1))
+    sf = np.ascontiguousarray(np.asarray(scale_factors, np.float32).reshape(-1))
+    M = len(off) - 1
+    if len(p) != M or len(ro) != M or len(lv) != M:
+        raise ValueError("pos, ref_Ow and ref_level must have one row per point")
+    normal, dmin, dmax = np.zeros((max(M, 1), 3), np.float32), np.zeros(max(M, 1), np.float32), np.zeros(max(M, 1), np.float32)
+    check(hip_lib().orb_update_normal_and_depth(M, ptr(off), ptr(ow), ptr(p), ptr(ro), ptr(lv), ptr(sf), len(sf),
+                                                ptr(normal), ptr(dmin), ptr(dmax), device))
+    return normal[:M], dmin[:M], dmax[:M]
+
+
+def update_normal_and_depth_device(d_offsets, d_obs_Ow, d_pos, d_ref_Ow, d_ref_level, scale_factors, max_obs, d_normal,
+                                   d_dmin, d_dmax, stream=None):
+    """orb_update_normal_and_depth_device on device tensors: d_offsets (M + 1,) int32, d_obs_Ow (R, 3),
+    d_pos / d_ref_Ow (M, 3) float32, d_ref_level (M,) int32; scale_factors stays a host table; max_obs >=
+    the largest offsets[m+1] - offsets[m] (no point is walked further); d_normal (M, 3), d_dmin, d_dmax
+    (M,) written in place (any may be None); enqueued on `stream`."""
+    import torch
+
+    M = int(d_offsets.shape[0]) - 1
+    sf = np.ascontiguousarray(np.asarray(scale_factors, np.float32).reshape(-1))
+    s = stream if stream is not None else torch.cuda.current_stream(d_offsets.device)
+    check(hip_lib().orb_update_normal_and_depth_device(M, ptr(d_offsets), ptr(d_obs_Ow), ptr(d_pos), ptr(d_ref_Ow),
+                                                       ptr(d_ref_level), ptr(sf), len(sf), int(max_obs), ptr(d_normal),
+                                                       ptr(d_dmin), ptr(d_dmax), ctypes.c_void_p(s.cuda_stream)))
+    return d_normal, d_dmin, d_dmax
