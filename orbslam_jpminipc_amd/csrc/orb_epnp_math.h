@@ -86,6 +86,13 @@ EPNP_HD inline double cv_hypot(double a, double b) {
 
 // The fill-in `while` has no bound in OpenCV; as in §16 it gives up after this many tries.
 constexpr int MAX_FILL_TRIES = 16;
+// The fill-in's random vector has 1-norm 1 before every projection is taken off.  When what is left has
+// a 1-norm under this, the vector lay in the span of the earlier rows (cv::RNG(0x12345678)'s fifth
+// vector of six signs is the negative of its fourth) and the renormalisation would scale rounding
+// noise back to order 1: a row that is not orthogonal to the earlier ones.  OpenCV keeps that row;
+// here the next random vector is tried instead (the second repair).  A vector that does
+// not collapse goes through the same operations as in OpenCV.
+constexpr double FILL_COLLAPSE = 1e-8;
 
 // JacobiSVDImpl_<double>(At, astep, W, Vt, vstep, m, n, n1, minval = DBL_MIN, eps = DBL_EPSILON*10).
 // At: n1 rows of m, the first n orthogonalised.  OpenCV always passes a Vt here; with vt == false its
@@ -199,6 +206,7 @@ EPNP_HD inline void jacobi_svd(M At, int astep, M W, M Vt, bool vt, int vstep, i
             // a zero singular value: a random vector, its projections on the earlier rows taken off
             // twice, normalised
             br |= BR_SVD_FILL;
+            bool collapsed = false;
             const double val0 = (double)(1. / m);
             for (k = 0; k < m; k++) {
                 rng = (uint64_t)(unsigned)rng * 4164903690U + (unsigned)(rng >> 32);
@@ -215,6 +223,7 @@ EPNP_HD inline void jacobi_svd(M At, int astep, M W, M Vt, bool vt, int vstep, i
                         At[i * astep + k] = t;
                         asum += fabs(t);
                     }
+                    if (asum < FILL_COLLAPSE) collapsed = true;
                     asum = asum ? 1 / asum : 0;
                     for (k = 0; k < m; k++) At[i * astep + k] *= asum;
                 }
@@ -224,6 +233,7 @@ EPNP_HD inline void jacobi_svd(M At, int astep, M W, M Vt, bool vt, int vstep, i
                 sd += t * t;
             }
             sd = sqrt(sd);
+            if (collapsed && tries < MAX_FILL_TRIES) sd = 0;  // another vector; the last try is kept as it is
         }
         s = 1 / sd;
         for (k = 0; k < m; k++) At[i * astep + k] *= s;
@@ -656,7 +666,7 @@ EPNP_HD inline void qr_solve(double* pA, double* pb, double* pX, unsigned& br) {
 }
 
 // The reference's x[4] is uninitialised and is read as it is when qr_solve returns early on its
-// first call; here it starts as zeros (the one repair).
+// first call; here it starts as zeros (the first repair).
 EPNP_HD inline void gauss_newton(const double* l_6x10, const double* rho, double* betas, unsigned& br) {
     double a[6 * 4], b[6], x[4] = {0, 0, 0, 0};
 #pragma unroll 1

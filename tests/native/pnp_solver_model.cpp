@@ -3,11 +3,13 @@
 // on a real std::vector (it shares nothing with the closed-form mapping of the kernels) and
 // CheckInliers (280-311) as DESIGN.md §12 states its arithmetic.  EPnP's compute_pose and the OpenCV
 // 2.4 routines under it are csrc/orb_epnp_math.h compiled for the host with plain arrays: the one
-// statement of that arithmetic, checked here against an independent numpy EPnP
-// (tests/test_pnp_solver_model.py).  Built -ffp-contract=off, the fused multiply-adds written out.
-// Every call can export the bitmask of the branches it visited.  Single-threaded;
-// scripts/pnp_solver_timing.py also times it.  -DPNP_SOLVER_MODEL_MAIN adds a main() for the
-// sanitizer run.
+// statement of that arithmetic.  pnp_solver_model_stages exports what every step of
+// compute_pose left behind and pnp_solver_model_jacobi_svd runs the Jacobi SVD on a caller's matrix;
+// tests/test_epnp_stages.py holds each to tests/epnp_reference.py, a numpy float64 EPnP written from
+// the construction that shares no statement with the header.  Built -ffp-contract=off, the fused
+// multiply-adds written out.  Every call can export the bitmask of the branches it visited.
+// Single-threaded; scripts/pnp_solver_timing.py also times it.  -DPNP_SOLVER_MODEL_MAIN adds a main()
+// for the sanitizer run.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -69,6 +71,62 @@ struct Solver {
         const double r = orb_epnp::compute_pose(e, &R[0][0], t);
         br |= e.br;
         return r;
+    }
+    // compute_pose's steps in compute_pose's order, each one's result copied out (any pointer may be
+    // NULL).  Only the header's functions are called; the one thing written here is the strict `<` of
+    // PnPsolver.cc:478-484 on the three errors, which the caller compares with compute_pose itself.
+    // br[0]: control points, barycentric coordinates and the 12 x 12; br[1..3]: find_betas_approx_N,
+    // gauss_newton and compute_R_and_t of N = 1, 2, 3; br[4]: all of them with BR_N2 / BR_N3.
+    void stages(double* o_cws, double* o_ci, double* o_alphas, double* o_ut, double* o_w, double* o_l, double* o_rho,
+                double* o_betas0, double* o_betas, double* o_R, double* o_t, double* o_rep, int32_t* o_N,
+                uint32_t* o_br) {
+        const int n = number_of_correspondences;
+        alphas.assign((size_t)4 * n, 0.0);
+        pcs.assign((size_t)3 * n, 0.0);
+        double wk[WK_DOUBLES];
+        Epnp<Mat<1>, PtsHost> e;
+        e.wk = Mat<1>{wk};
+        e.pt = PtsHost{n, pws.data(), us.data(), alphas.data(), pcs.data()};
+        e.fu = fu, e.fv = fv, e.uc = uc, e.vc = vc;
+        e.br = 0;
+        uint32_t brs[5] = {0, 0, 0, 0, 0};
+        choose_control_points(e);
+        if (o_cws) std::memcpy(o_cws, e.cws, sizeof(e.cws));
+        compute_barycentric_coordinates(e);
+        if (o_ci) std::memcpy(o_ci, e.ci, sizeof(e.ci));
+        if (o_alphas && n) std::memcpy(o_alphas, alphas.data(), sizeof(double) * 4 * n);
+        mtm_svd(e);
+        if (o_ut) std::memcpy(o_ut, wk, sizeof(double) * 144);
+        if (o_w) std::memcpy(o_w, wk + WK_W, sizeof(double) * 12);
+        brs[0] = e.br;
+        double l_6x10[6 * 10], rho[6];
+        compute_L_6x10(e, l_6x10);
+        compute_rho(e, rho);
+        if (o_l) std::memcpy(o_l, l_6x10, sizeof(l_6x10));
+        if (o_rho) std::memcpy(o_rho, rho, sizeof(rho));
+        double rep[3];
+        for (int k = 0; k < 3; k++) {
+            double Betas[4], Rk[9], tk[3];
+            e.br = 0;
+            if (k == 0) find_betas_approx_1(e, l_6x10, rho, Betas);
+            if (k == 1) find_betas_approx_2(e, l_6x10, rho, Betas);
+            if (k == 2) find_betas_approx_3(e, l_6x10, rho, Betas);
+            if (o_betas0) std::memcpy(o_betas0 + 4 * k, Betas, sizeof(Betas));
+            gauss_newton(l_6x10, rho, Betas, e.br);
+            if (o_betas) std::memcpy(o_betas + 4 * k, Betas, sizeof(Betas));
+            rep[k] = compute_R_and_t(e, Betas, Rk, tk);
+            if (o_R) std::memcpy(o_R + 9 * k, Rk, sizeof(Rk));
+            if (o_t) std::memcpy(o_t + 3 * k, tk, sizeof(tk));
+            if (o_rep) o_rep[k] = rep[k];
+            brs[1 + k] = e.br;
+        }
+        int N = 1;
+        if (rep[1] < rep[0]) N = 2;
+        if (rep[2] < rep[N - 1]) N = 3;
+        if (o_N) *o_N = N;
+        brs[4] = brs[0] | brs[1] | brs[2] | brs[3] | (N == 2 ? BR_N2 : 0u) | (N == 3 ? BR_N3 : 0u);
+        if (o_br) std::memcpy(o_br, brs, sizeof(brs));
+        br |= brs[4];
     }
     // PnPsolver.cc:280-311 as the reference build contracts it
     void CheckInliers() {
@@ -176,6 +234,32 @@ unsigned pnp_solver_model_compute_pose(int n, const float* p3d, const float* p2d
     std::memcpy(t, tm, sizeof(tm));
     if (rep_error) *rep_error = e;
     return s.br;
+}
+
+// The stages of the same call (Solver::stages): cws 4 x 3, ci 3 x 3, alphas n_used x 4, ut 12 x 12 and
+// w 12 as mtm_svd left them, l_6x10 6 x 10, rho 6, then for N = 1, 2, 3 the betas after
+// find_betas_approx_N (betas0, 3 x 4) and after gauss_newton (betas, 3 x 4), R (3 x 9), t (3 x 3) and the
+// reprojection error (3) of compute_R_and_t; N_sel is the N the strict `<` picks, br 5 branch masks.
+// Returns the whole mask, which is compute_pose's.
+unsigned pnp_solver_model_stages(int n, const float* p3d, const float* p2d, const double* K, int n_sel,
+                                 const int32_t* sel, double* cws, double* ci, double* alphas, double* ut, double* w,
+                                 double* l_6x10, double* rho, double* betas0, double* betas, double* R, double* t,
+                                 double* rep_error, int32_t* N_sel, uint32_t* br) {
+    Solver s;
+    s.N = n, s.p3d = p3d, s.p2d = p2d;
+    s.fu = K[0], s.fv = K[1], s.uc = K[2], s.vc = K[3];
+    s.reset_correspondences();
+    for (int i = 0; i < (sel ? n_sel : n); i++) s.add_index(sel ? sel[i] : i);
+    s.stages(cws, ci, alphas, ut, w, l_6x10, rho, betas0, betas, R, t, rep_error, N_sel, br);
+    return s.br;
+}
+
+// jacobi_svd on a caller's matrix: At is n1 rows of m (overwritten: the first n become the left
+// singular vectors), W n singular values, Vt n x n (written when want_vt).  Returns the branch mask.
+unsigned pnp_solver_model_jacobi_svd(int m, int n, int n1, int want_vt, double* At, double* W, double* Vt) {
+    unsigned br = 0;
+    jacobi_svd(Mat<1>{At}, m, Mat<1>{W}, Mat<1>{Vt}, want_vt != 0, n, m, n, n1, br);
+    return br;
 }
 
 // PnPsolver::iterate over n_hyp iterations (the caller's max(mRansacMaxIts - mnIterations,
@@ -331,7 +415,28 @@ int main() {
         }
         if (c % 19 == 4) p3[1] = std::numeric_limits<float>::quiet_NaN();
         double R[9], t[3], e;
-        all |= pnp_solver_model_compute_pose(n, p3.data(), p2.data(), K, 0, nullptr, R, t, &e);
+        const unsigned cb = pnp_solver_model_compute_pose(n, p3.data(), p2.data(), K, 0, nullptr, R, t, &e);
+        all |= cb;
+        // the same input stage by stage (its mask must be compute_pose's), with and without outputs, then
+        // the Jacobi SVD alone on what the stages exported; none of these adds to `all`
+        std::vector<double> al(4 * n);
+        double cws[12], ci[9], ut[144], w[12], l[60], rho[6], b0[12], b[12], R3[27], t3[9], e3[3];
+        int32_t N;
+        uint32_t br5[5];
+        const unsigned sb = pnp_solver_model_stages(n, p3.data(), p2.data(), K, 0, nullptr, cws, ci, al.data(), ut, w, l,
+                                                    rho, b0, b, R3, t3, e3, &N, br5);
+        const unsigned nb = pnp_solver_model_stages(n, p3.data(), p2.data(), K, 0, nullptr, nullptr, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr);
+        if (sb != cb || nb != cb || sb != br5[4] || N < 1 || N > 3) {
+            std::printf("stages: mask 0x%x / 0x%x against compute_pose's 0x%x, N %d\n", sb, nb, cb, (int)N);
+            return 2;
+        }
+        double w12[12], vt12[144], a65[30], w5[5], vt5[25];
+        pnp_solver_model_jacobi_svd(12, 12, 12, c & 1, ut, w12, vt12);
+        for (int k = 0; k < 30; k++) a65[k] = l[k];
+        pnp_solver_model_jacobi_svd(6, 5, 5, 1, a65, w5, vt5);
+        pnp_solver_model_jacobi_svd(3, 3, 3, 1, ci, w5, vt5);
     }
     {  // a whole RANSAC, with the sampler on the vector
         const int n = 40, n_hyp = 50;

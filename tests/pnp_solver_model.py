@@ -1,6 +1,8 @@
 """ctypes loader of the CPU model of the PnPsolver hypotheses and RANSAC (tests/native/pnp_solver_model.cpp,
 built to build/libpnp_solver_model.so by __graft_entry__.build()): the sampler of PnPsolver::iterate
-on a std::vector, EPnP's compute_pose, CheckInliers, the keep-the-best rule and Refine, restated.
+on a std::vector, EPnP's compute_pose, CheckInliers, the keep-the-best rule and Refine, restated; and
+what every step of compute_pose left behind (stages) and the header's Jacobi SVD on its own
+(jacobi_svd), for tests/epnp_reference.py to be compared with.
 
 Also the shared synthetic scenes of the PnP solver tests and an independent float64 EPnP in numpy."""
 import ctypes
@@ -29,21 +31,31 @@ def lib() -> ctypes.CDLL:
 
             LIB.parent.mkdir(exist_ok=True)
             subprocess.run(ge.PNP_SOLVER_MODEL_CMD(LIB), check=True)
-        _lib = ctypes.CDLL(str(LIB))
-        vp, i, u = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
-        _lib.pnp_solver_model_random_int.restype = i
-        _lib.pnp_solver_model_random_int.argtypes = [i, i]
-        _lib.pnp_solver_model_sets.restype = i
-        _lib.pnp_solver_model_sets.argtypes = [i, i, vp, vp]
-        _lib.pnp_solver_model_mapping.restype = i
-        _lib.pnp_solver_model_mapping.argtypes = [i, i, i, vp, vp]
-        _lib.pnp_solver_model_qr_solve.restype = u
-        _lib.pnp_solver_model_qr_solve.argtypes = [vp, vp, vp]
-        _lib.pnp_solver_model_compute_pose.restype = u
-        _lib.pnp_solver_model_compute_pose.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp]
-        _lib.pnp_solver_model_ransac.restype = i
-        _lib.pnp_solver_model_ransac.argtypes = [i, vp, vp, vp, ctypes.c_float, vp, i, vp, vp, i, i] + [vp] * 17
+        _lib = load(LIB)
     return _lib
+
+
+def load(path) -> ctypes.CDLL:
+    """A build of the model with its prototypes (lib() is this on build/; the mutant test loads others)."""
+    so = ctypes.CDLL(str(path))
+    vp, i, u = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
+    so.pnp_solver_model_random_int.restype = i
+    so.pnp_solver_model_random_int.argtypes = [i, i]
+    so.pnp_solver_model_sets.restype = i
+    so.pnp_solver_model_sets.argtypes = [i, i, vp, vp]
+    so.pnp_solver_model_mapping.restype = i
+    so.pnp_solver_model_mapping.argtypes = [i, i, i, vp, vp]
+    so.pnp_solver_model_qr_solve.restype = u
+    so.pnp_solver_model_qr_solve.argtypes = [vp, vp, vp]
+    so.pnp_solver_model_compute_pose.restype = u
+    so.pnp_solver_model_compute_pose.argtypes = [i, vp, vp, vp, i, vp, vp, vp, vp]
+    so.pnp_solver_model_stages.restype = u
+    so.pnp_solver_model_stages.argtypes = [i, vp, vp, vp, i, vp] + [vp] * 14
+    so.pnp_solver_model_jacobi_svd.restype = u
+    so.pnp_solver_model_jacobi_svd.argtypes = [i, i, i, i, vp, vp, vp]
+    so.pnp_solver_model_ransac.restype = i
+    so.pnp_solver_model_ransac.argtypes = [i, vp, vp, vp, ctypes.c_float, vp, i, vp, vp, i, i] + [vp] * 17
+    return so
 
 
 def _p(a):
@@ -88,6 +100,41 @@ def compute_pose(p3d, p2d, K, sel=None) -> dict:
     br = lib().pnp_solver_model_compute_pose(len(p3d), _p(p3d), _p(p2d), _p(Kd), 0 if s is None else len(s), _p(s),
                                              _p(R), _p(t), _p(e))
     return {"R": R, "t": t, "rep_error": float(e[0]), "branches": int(br)}
+
+
+def stages(p3d, p2d, K, sel=None) -> dict:
+    """What every step of compute_pose left behind on the correspondences `sel` (all when None): cws, ci,
+    alphas, ut and w of mtm_svd, l_6x10, rho; per N = 1, 2, 3 (first axis) betas0 after
+    find_betas_approx_N, betas after gauss_newton, R, t, rep_error; N the strict `<` picks; br_front,
+    br_n (3) and branches, the masks of the steps before the betas, of each N and of the whole call."""
+    p3d, p2d = _f32(p3d, 3), _f32(p2d, 2)
+    Kd = np.ascontiguousarray(K, np.float64).reshape(4)
+    s = None if sel is None else np.ascontiguousarray(sel, np.int32).reshape(-1)
+    n = len(p3d) if s is None else len(s)
+    o = {"cws": np.zeros((4, 3)), "ci": np.zeros((3, 3)), "alphas": np.zeros((n, 4)), "ut": np.zeros((12, 12)),
+         "w": np.zeros(12), "l_6x10": np.zeros((6, 10)), "rho": np.zeros(6), "betas0": np.zeros((3, 4)),
+         "betas": np.zeros((3, 4)), "R": np.zeros((3, 3, 3)), "t": np.zeros((3, 3)), "rep_error": np.zeros(3),
+         "N": np.zeros(1, np.int32), "br": np.zeros(5, np.uint32)}
+    br = lib().pnp_solver_model_stages(len(p3d), _p(p3d), _p(p2d), _p(Kd), 0 if s is None else len(s), _p(s),
+                                       *[_p(v) for v in o.values()])
+    br5 = o.pop("br")
+    assert int(br5[4]) == br
+    o["N"] = int(o["N"][0])
+    o.update(br_front=int(br5[0]), br_n=[int(b) for b in br5[1:4]], branches=int(br))
+    return o
+
+
+def jacobi_svd(A, want_vt=True, n1=None):
+    """The header's jacobi_svd on A (m x n, n <= m): its work matrix is transpose(A), n1 >= n rows of m.
+    Returns (Ut n1 x m, W n, Vt n x n or None, branch mask): A = Ut[:n].T @ diag(W) @ Vt."""
+    A = np.array(A, np.float64)
+    m, n = A.shape
+    n1 = n if n1 is None else int(n1)
+    At = np.zeros((n1, m))
+    At[:n] = A.T
+    W, Vt = np.zeros(n), np.zeros((n, n))
+    br = lib().pnp_solver_model_jacobi_svd(m, n, n1, int(bool(want_vt)), _p(At), _p(W), _p(Vt))
+    return At, W, (Vt if want_vt else None), int(br)
 
 
 def ransac(p3d, p2d, sigma2, th2, K, min_inliers, sets=None, rand31=None, best_in=0) -> dict:
