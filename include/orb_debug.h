@@ -23,6 +23,10 @@ int orb_debug_nth_element_u32(uint32_t* a, int n, int nth);
 int orb_debug_nth_element_wave_u32(uint32_t* a, int n, int nth, int device);
 /* Padded pyramid level l of batch frame b after the last extraction (device sync). */
 int orb_debug_level_image(orb_extractor_t* h, int b, int l, uint8_t* out, int* w, int* hgt);
+/* The rest of each of that level's rows up to the row pitch: (h+32) rows of pitch - (w+32) bytes
+ * (the return value, 0 .. 15; out may be NULL to ask for it).  Every pyramid builder writes zeros
+ * there, so that the workspace is the same bytes whichever builder ran (device sync). */
+int orb_debug_level_row_slack(orb_extractor_t* h, int b, int l, uint8_t* out);
 /* Descriptor image (blurred ROI + un-blurred padding ring) of level l, frame b, padded
  * (w+32) x (h+32) layout; defined over [-3, w+3) x [-3, h+3) at least (wider where a dense
  * cell grid lets keypoints sit past the FAST border) (device sync). */
@@ -42,6 +46,17 @@ int orb_debug_set_fast_corner_list(orb_extractor_t* h, int cap);
 /* The current geometry's k_pyr_stream plan: returns 1 (and level-0 rows per round, rounds,
  * LDS bytes) when there is one, 0 when the geometry only runs per-level launches. */
 int orb_debug_pyramid_plan(const orb_extractor_t* h, int* rows_per_round, int* rounds, int* lds_bytes);
+/* Per level of that plan (0 and nothing written when there is none; else the number of levels,
+ * the first min(levels, cap) written): nq = tasks per padded row (16-byte chunks at level 0,
+ * 4-pixel quads above), n_waves = the workgroup's waves that build the level (a level whose
+ * nq <= 64 * n_waves decodes its columns once, hoisted out of the rounds; the others decode per
+ * round), ring_rows = rows of the level's LDS ring (0 for the last level, which has none). */
+int orb_debug_pyramid_plan_levels(const orb_extractor_t* h, int* nq, int* n_waves, int* ring_rows, int cap);
+/* Set every byte of the handle's pyramid workspace (all levels of all max_batch frames, padding
+ * and slack included) to `value` (0 .. 255), ordered after the handle's last launch and before
+ * its next.  A test that poisons the workspace before a build then compares bytes that this
+ * build wrote, not what an earlier one left.  The pyramid of phase 1 is gone afterwards. */
+int orb_debug_fill_pyramid(orb_extractor_t* h, int value);
 /* Per-slot tables of the database's last host query (q = 0) or of query q of its last batch, for
  * slots 0 .. min(cap, highest id used + 1) - 1 (the return value): common = shared words (0 for a
  * slot that is not live), first_word = the smallest shared word (0xFFFFFFFF: none), seq = the

@@ -256,6 +256,9 @@ HIP_SIGNATURES = {
     "orb_debug_blur_image": (_i, [_vp, _i, _i, _vp]),
     "orb_debug_set_pyramid_path": (_i, [_vp, _i]),
     "orb_debug_pyramid_plan": (_i, [_vp, _pi, _pi, _pi]),
+    "orb_debug_pyramid_plan_levels": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "orb_debug_fill_pyramid": (_i, [_vp, _i]),
+    "orb_debug_level_row_slack": (_i, [_vp, _i, _i, _vp]),
 }
 
 _hip = None

@@ -132,6 +132,7 @@ struct LevelGeom {
     float size;             // (int)(31 * mvScaleFactor[l])
     int cellW, cellH;       // detection-area size of the (non-last) cells: corner -> cell bucket
     int cellWm, cellHm;     // ceil(2^32 / cellW), ceil(2^32 / cellH): n / cell = umulhi(n, m), n < 4096
+                            // (2^32 - 1 for a 1-px cell, applied to n + 1: ceil(2^32 / 1) does not fit)
     int candBase, capMax;   // cell c of the level owns candidate slots candBase + c * capMax (capMax = the
                             // level's largest NMS-survivor bound), so k_fast needs no cell table
     int detX1, detY1;       // FAST detection region [16, detX1) x [16, detY1): union of the cells' areas
@@ -2178,13 +2179,19 @@ __global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ pyr, G
     // (4) in-cell NMS.  Cell (i, j) has the detection area [16 + j*cellW, j == cols-1 ? w-16 :
     // 16 + (j+1)*cellW) in x (likewise in y), ORBextractor.cc:572-597; cell of a detection pixel:
     // ((y-16) / cellH, (x-16) / cellW) by exact reciprocal multiplies (host-checked).
+    // (A 1-px cell -- a level 33 px high or wide has a 1-px detection area -- has no such
+    // reciprocal: ceil(2^32 / 1) does not fit 32 bits.  The host sends 2^32 - 1 instead, and
+    // umulhi(n + 1, 2^32 - 1) = n: the coordinate's origin moves by one, in an SGPR, at no VALU cost.)
+    const int orgY = lg.cellHm == -1 ? EDGE - 1 : EDGE, orgX = lg.cellWm == -1 ? EDGE - 1 : EDGE;
+    auto cell_row = [&](int y) { return (int)__umulhi((uint32_t)(y - orgY), (uint32_t)lg.cellHm); };
+    auto cell_col = [&](int x) { return (int)__umulhi((uint32_t)(x - orgX), (uint32_t)lg.cellWm); };
     int* fcount = cellCount + (long long)b * g.nCells + lg.cell0;
     uint32_t* fcand = cand + (long long)b * g.candPerFrame + lg.candBase;
     // the tile's cells: rows ciT0 .. ciT1, columns cjT0 .. cjT0 + ncT - 1 (wave-uniform)
-    const int ciT0 = (int)__umulhi((uint32_t)(t.y0 - EDGE), (uint32_t)lg.cellHm);
-    const int ciT1 = (int)__umulhi((uint32_t)(t.y0 + t.th - 1 - EDGE), (uint32_t)lg.cellHm);
-    const int cjT0 = (int)__umulhi((uint32_t)(t.x0 - EDGE), (uint32_t)lg.cellWm);
-    const int cjT1 = (int)__umulhi((uint32_t)(min(t.x0 + 4 * t.tw4, lg.detX1) - 1 - EDGE), (uint32_t)lg.cellWm);
+    const int ciT0 = cell_row(t.y0);
+    const int ciT1 = cell_row(t.y0 + t.th - 1);
+    const int cjT0 = cell_col(t.x0);
+    const int cjT1 = cell_col(min(t.x0 + 4 * t.tw4, lg.detX1) - 1);
     const int ncT = cjT1 - cjT0 + 1, nT = (ciT1 - ciT0 + 1) * ncT;
     // KF_AGG: the survivors' cell slots taken per workgroup -- an LDS count per cell of the tile,
     // one global atomicAdd per cell, each survivor at the cell's base + its LDS rank -- instead of
@@ -2211,8 +2218,8 @@ __global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ pyr, G
                 e = list[k];
                 const int rt = e >> 9, ct = e & 511;
                 const int X = t.x0 + ct, Y = t.y0 + rt;
-                const int ci = (int)__umulhi((uint32_t)(Y - EDGE), (uint32_t)lg.cellHm);
-                const int cj = (int)__umulhi((uint32_t)(X - EDGE), (uint32_t)lg.cellWm);
+                const int ci = cell_row(Y);
+                const int cj = cell_col(X);
                 if (ci < lg.rows && cj < lg.cols) {
                     const int xlo = EDGE + cj * lg.cellW, xhi = cj == lg.cols - 1 ? lg.w - EDGE : xlo + lg.cellW;
                     const int ylo = EDGE + ci * lg.cellH, yhi = ci == lg.rows - 1 ? lg.h - EDGE : ylo + lg.cellH;
@@ -2249,8 +2256,8 @@ __global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ pyr, G
             const uint16_t e = pq[k];
             const int rt = e >> 9, ct = e & 511;
             const int X = t.x0 + ct, Y = t.y0 + rt;
-            const int ci = (int)__umulhi((uint32_t)(Y - EDGE), (uint32_t)lg.cellHm);
-            const int cj = (int)__umulhi((uint32_t)(X - EDGE), (uint32_t)lg.cellWm);
+            const int ci = cell_row(Y);
+            const int cj = cell_col(X);
             if constexpr (AGG) {
                 s_rk[wave * FT_CL + k] = (uint16_t)atomicAdd(&s_cc[(ci - ciT0) * ncT + (cj - cjT0)], 1);
             } else {
@@ -2281,8 +2288,8 @@ __global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ pyr, G
             const uint16_t e = pq[k];
             const int rt = e >> 9, ct = e & 511;
             const int X = t.x0 + ct, Y = t.y0 + rt;
-            const int ci = (int)__umulhi((uint32_t)(Y - EDGE), (uint32_t)lg.cellHm);
-            const int cj = (int)__umulhi((uint32_t)(X - EDGE), (uint32_t)lg.cellWm);
+            const int ci = cell_row(Y);
+            const int cj = cell_col(X);
             const int S = s_S[(rt + 1) * spw + ct + 4];
             const int pos = s_base[(ci - ciT0) * ncT + (cj - cjT0)] + s_rk[wave * FT_CL + k];
             if (pos < lg.capMax)
@@ -3718,12 +3725,15 @@ struct orb_extractor {
     StreamGeom sgeom{};
     size_t streamLds = 0;
     int streamK0 = 0;
+    std::vector<StreamLevel> streamLv;  // host copy of d_slv (orb_debug_pyramid_plan_levels)
+    std::vector<int> streamCap;         // ring rows of levels 0 .. L-2
     uint32_t* d_scol = nullptr;
     uint4* d_srows = nullptr;
     StreamLevel* d_slv = nullptr;
     uint32_t* d_srounds = nullptr;
     // device workspace
     uint8_t* d_pyr = nullptr;
+    size_t pyrAlloc = 0;  // bytes of d_pyr (orb_debug_fill_pyramid)
     FastTile* d_tiles = nullptr;
     int nTiles = 0;
     uint32_t* d_cand = nullptr;
@@ -3807,6 +3817,7 @@ struct orb_extractor {
         d_srounds = nullptr;
         streamOk = false;
         d_pyr = nullptr;
+        pyrAlloc = 0;
         d_tiles = nullptr;
         nTiles = 0;
         d_cand = nullptr;
@@ -3924,8 +3935,9 @@ struct orb_extractor {
             lg.nfc = (int)std::ceil((float)nD / nCells);
             lg.cellW = cellW;
             lg.cellH = cellH;
-            lg.cellWm = (int)(uint32_t)((0x100000000ull + cellW - 1) / (uint64_t)cellW);
-            lg.cellHm = (int)(uint32_t)((0x100000000ull + cellH - 1) / (uint64_t)cellH);
+            // (a 1-px cell's reciprocal 2^32 does not fit: 2^32 - 1, which k_fast applies to n + 1)
+            lg.cellWm = cellW == 1 ? -1 : (int)(uint32_t)((0x100000000ull + cellW - 1) / (uint64_t)cellW);
+            lg.cellHm = cellH == 1 ? -1 : (int)(uint32_t)((0x100000000ull + cellH - 1) / (uint64_t)cellH);
             lg.detX1 = std::max(maxBX, levelCols > 1 ? 16 + (levelCols - 1) * cellW : 0);
             lg.detY1 = std::max(maxBY, levelRows > 1 ? 16 + (levelRows - 1) * cellH : 0);
             // keypoints of non-last cells can sit past maxBorder (ORBextractor.cc:560-597); the
@@ -4109,6 +4121,7 @@ struct orb_extractor {
         // + slack: k_orient_desc's 64-byte window rows and k_rerun's 16-B ROI units may over-read
         // the last row's pitch
         HIP_TRY(hipMalloc(&d_pyr, (size_t)pyrBytes + 256));
+        pyrAlloc = (size_t)pyrBytes + 256;
         // k_fast tiles over each level's detection region: the width split evenly into
         // ceil(width / 256) tiles of a multiple of 4 columns, as many rows as the LDS budgets
         // (staged tile, strength plane) and the 16-bit queue codes allow
@@ -4398,6 +4411,8 @@ struct orb_extractor {
         HIP_TRY(hipMalloc(&d_srounds, rounds.size() * 4));
         HIP_TRY(hipMemcpy(d_srounds, rounds.data(), rounds.size() * 4, hipMemcpyHostToDevice));
         sgeom = sg;
+        streamLv = lv;
+        streamCap = cap;
         streamLds = lds;
         streamK0 = K0;
         streamOk = true;
@@ -5209,6 +5224,28 @@ int orb_debug_pyramid_plan(const orb_extractor_t* h, int* rows_per_round, int* r
     return 1;
 }
 
+int orb_debug_pyramid_plan_levels(const orb_extractor_t* h, int* nq, int* n_waves, int* ring_rows, int cap) {
+    if (!h || cap < 0) return set_err(ORB_EINVAL, "bad arguments");
+    if (!h->streamOk) return 0;
+    const int L = (int)h->streamLv.size();
+    for (int l = 0; l < L && l < cap; ++l) {
+        if (nq) nq[l] = h->streamLv[l].nq;
+        if (n_waves) n_waves[l] = h->streamLv[l].nWaves;
+        if (ring_rows) ring_rows[l] = l + 1 < L ? h->streamCap[l] : 0;
+    }
+    return L;
+}
+
+int orb_debug_fill_pyramid(orb_extractor_t* h, int value) {
+    if (!h || !h->d_pyr || value < 0 || value > 255) return set_err(ORB_EINVAL, "bad arguments");
+    HIP_TRY(hipSetDevice(h->device));
+    // ordered like a launch: after the handle's last one, and before its next on any stream
+    if (int r = h->order_after_last(h->stream)) return r;
+    HIP_TRY(hipMemsetAsync(h->d_pyr, value, h->pyrAlloc, h->stream));
+    h->pyrBatch = 0;
+    return ORB_OK;
+}
+
 int orb_extract_set_phases(orb_extractor_t* h, unsigned phase_mask) {
     if (!h) return set_err(ORB_EINVAL, "bad handle");
     if (phase_mask == 0u || (phase_mask & ~3u)) return set_err(ORB_EINVAL, "phase_mask must be 1, 2 or 3");
@@ -5300,6 +5337,21 @@ int orb_debug_level_image(orb_extractor_t* h, int b, int l, uint8_t* out, int* w
     HIP_TRY(hipMemcpy2D(out, lg.w + 32, h->d_pyr + lg.base + (long long)b * lg.fstride, lg.pitch, lg.w + 32, lg.ph,
                         hipMemcpyDeviceToHost));
     return ORB_OK;
+}
+
+// The bytes of the same level's rows between the padded image and the row pitch: (h+32) rows of
+// pitch - (w+32) bytes (the return value, 0 .. 15), tightly packed.  Every builder writes zeros there.
+int orb_debug_level_row_slack(orb_extractor_t* h, int b, int l, uint8_t* out) {
+    if (!h || b < 0 || b >= h->maxBatch || l < 0 || l >= h->nlevels || !h->d_pyr)
+        return set_err(ORB_EINVAL, "bad arguments");
+    const LevelGeom& lg = h->g.lv[l];
+    const int slack = lg.pitch - (lg.w + 32);
+    if (!out || slack == 0) return slack;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy2D(out, slack, h->d_pyr + lg.base + (long long)b * lg.fstride + lg.w + 32, lg.pitch, slack, lg.ph,
+                        hipMemcpyDeviceToHost));
+    return slack;
 }
 
 // Descriptor image of level l, frame b (blurred ROI + raw padding), padded layout, computed by

@@ -124,6 +124,10 @@ def test_pyramid_and_descriptor_image_parity(W, H):
     ext = orb.ORBextractor(1000 if W >= 320 else 300, 1.2, nl, orb.FAST_SCORE, 20, device=0)
     ora = Oracle(1000 if W >= 320 else 300, 1.2, nl, 1, 20)
     img = orb.synth_stream(W, H, stream=13, count=1)[0]
+    ext(img)  # (the workspace exists after the first extraction)
+    # a fresh handle's workspace may be memory that an earlier handle of this geometry filled with
+    # these very levels: poison it, so that the levels read below are the ones this build wrote
+    assert orb.hip_lib().orb_debug_fill_pyramid(ext._h, 0xA5) == 0
     ext(img)
     ora.extract(img)
     lib = orb.hip_lib()
