@@ -1131,6 +1131,66 @@ int orb_optimize_sim3_batch_device(const orb_keypoint_t* d_kps, const int32_t* d
                                    float* d_sim3_out, double* d_sim3_out_f64, int32_t* d_n_inliers,
                                    orb_sim3_opt_info_t* d_info, void* stream);
 
+/* Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536, csrc/orb_localba.hip): the
+ * graph of lines 356-447 as flat arrays, both optimize() calls and both classifications in one
+ * launch, one workgroup per problem.  The map stays with the caller.
+ *   keyframes  n_kf, local ones first, then fixed: kf_pose n_kf x 12 floats (Rcw row-major, tcw), kf_K
+ *              n_kf x 4 (fx fy cx cy), kf_fixed n_kf u8 (mnId == 0, or a camera of lFixedCameras)
+ *   points     n_pt: pt_pos n_pt x 3 (GetWorldPos), pt_nobs n_pt (mObservations.size() at entry,
+ *              observations in bad keyframes included)
+ *   edges      n_edge in the order lines 399-447 create them, the edges of a point contiguous and the
+ *              points ascending: edge_pt, edge_kf (indices), edge_obs n_edge x 2 (kpUn.pt),
+ *              edge_inv_sigma2 n_edge (GetInvSigma2(octave))
+ * Outputs, each may be NULL: kf_pose_out n_kf x 12 (to_homogeneous_matrix narrowed; a fixed
+ * keyframe's is its input after the quaternion round trip) and kf_pose_out_f64; pt_pos_out n_pt x 3
+ * and pt_pos_out_f64; edge_erased n_edge u8 (0 kept, 1 / 2 the round after which the edge was erased:
+ * walk them in edge order with EraseMapPointMatch + EraseObservation to reproduce the reference's map
+ * mutation); pt_bad n_pt u8 (0, or the round after which the point's count reached 2); info.
+ * ORB_EINVAL: an index out of range, edges not grouped by ascending point, a (point, keyframe) pair
+ * twice, more edges of a point than pt_nobs, a non-finite pose or calibration value, fx or fy == 0.
+ * ORB_ENOTSUP, with nothing written: no free keyframe, or more than ORB_LBA_MAX_FREE_KF of them.
+ * n_edge == 0 or n_pt == 0: ORB_OK, the inputs after the round trip.  The reference's pbStopFlag is
+ * not served: a call runs its schedule to the end. */
+#define ORB_LBA_MAX_FREE_KF 64
+typedef struct {
+    int32_t iterations;       /* Levenberg iterations run by this optimize()                      */
+    int32_t trials;           /* trial steps in all                                               */
+    int32_t active_edges;     /* edges, points and free keyframes in this round's optimisation    */
+    int32_t active_points;
+    int32_t active_keyframes;
+    int32_t refused;          /* trials whose reduced system was not positive definite            */
+    double lambda;            /* lambda at the end (-1: nothing ran)                              */
+    double chi2_before;       /* the robust chi2 the round started from ...                       */
+    double chi2_after;        /* ... and ended with                                               */
+} orb_local_ba_round_t;
+typedef struct {
+    int32_t status;           /* ORB_OK, or why the problem was refused (the batch form's report) */
+    int32_t n_free_kf;
+    orb_local_ba_round_t round[2];
+} orb_local_ba_info_t;
+/* One problem on host buffers, synchronous. */
+int orb_local_bundle_adjustment(int n_kf, const float* kf_pose, const float* kf_K, const uint8_t* kf_fixed, int n_pt,
+                                const float* pt_pos, const int32_t* pt_nobs, int n_edge, const int32_t* edge_pt,
+                                const int32_t* edge_kf, const float* edge_obs, const float* edge_inv_sigma2,
+                                float* kf_pose_out, double* kf_pose_out_f64, float* pt_pos_out, double* pt_pos_out_f64,
+                                uint8_t* edge_erased, uint8_t* pt_bad, orb_local_ba_info_t* info, int device);
+/* S problems on device arrays: problem s owns the keyframes [d_kf_off[s], d_kf_off[s + 1]) of the
+ * concatenated keyframe arrays (n_kf_total rows), likewise its points and edges (S + 1 offsets each);
+ * edge_pt / edge_kf are problem-local.  The outputs have the same concatenated layout; pose rows as
+ * orb_pose_optimization_batch_device takes them and positions as orb_update_normal_and_depth does.
+ * A problem that the host form would refuse is left unwritten and reports its status in d_info[s]
+ * (the call itself returns ORB_OK); offsets that leave the arrays count as ORB_EINVAL and nothing of
+ * that problem is read.  Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_local_bundle_adjustment_batch_device(int S, const int32_t* d_kf_off, const int32_t* d_pt_off,
+                                             const int32_t* d_edge_off, int n_kf_total, int n_pt_total, int n_edge_total,
+                                             const float* d_kf_pose, const float* d_kf_K, const uint8_t* d_kf_fixed,
+                                             const float* d_pt_pos, const int32_t* d_pt_nobs, const int32_t* d_edge_pt,
+                                             const int32_t* d_edge_kf, const float* d_edge_obs,
+                                             const float* d_edge_inv_sigma2, float* d_kf_pose_out,
+                                             double* d_kf_pose_out_f64, float* d_pt_pos_out, double* d_pt_pos_out_f64,
+                                             uint8_t* d_edge_erased, uint8_t* d_pt_bad, orb_local_ba_info_t* d_info,
+                                             void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

@@ -868,8 +868,8 @@ private:
 };
 
 // ORB_SLAM::Optimizer::PoseOptimization(Frame*) (Optimizer.cc:154-285) and Optimizer::OptimizeSim3
-// (Optimizer.cc:1721-1917) over PODs; bundle adjustment and the essential graph stay with the
-// reference's g2o.
+// (Optimizer.cc:1721-1917) and Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536) over PODs; global
+// bundle adjustment and the essential graph stay with the reference's g2o.
 class Optimizer {
 public:
     // F.keysUn = pFrame->mvKeysUn (N of them), invLevelSigma2 = mvInvLevelSigma2, fx..cy the
@@ -942,12 +942,45 @@ public:
         if (inf.more_iterations != 0) std::copy(out, out + 13, S12);
         return nIn;
     }
+
+    // The graph of ORB_SLAM::Optimizer::LocalBundleAdjustment (Optimizer.cc:356-447) as the caller's
+    // flattening loop fills it, and what lines 453-535 read back.
+    struct LocalBAGraph {
+        std::vector<float> kfPose;        // 12 per keyframe (Rcw row-major, tcw): lLocalKeyFrames, then lFixedCameras
+        std::vector<float> kfK;           // fx fy cx cy per keyframe
+        std::vector<uint8_t> kfFixed;     // mnId == 0, or a fixed camera
+        std::vector<float> ptPos;         // GetWorldPos() of lLocalMapPoints, in list order
+        std::vector<int32_t> ptNObs;      // GetObservations().size(), bad keyframes included
+        std::vector<int32_t> edgePt, edgeKf;  // one edge per observation in a keyframe that is not bad
+        std::vector<float> edgeObs;       // kpUn.pt
+        std::vector<float> edgeInvSigma2; // GetInvSigma2(kpUn.octave)
+    };
+    struct LocalBAResult {
+        std::vector<float> kfPose, ptPos;      // what SetPose / SetWorldPos receive (lines 520-535)
+        std::vector<uint8_t> edgeErased;       // 0, or the round after which the edge was erased: walk in edge order
+        std::vector<uint8_t> ptBad;
+        orb_local_ba_info_t info;
+    };
+    // pbStopFlag is not served: the call runs both rounds.
+    static void LocalBundleAdjustment(const LocalBAGraph& G, LocalBAResult& R, int device = 0) {
+        const size_t nk = G.kfFixed.size(), np = G.ptNObs.size(), ne = G.edgePt.size();
+        if (G.kfPose.size() != nk * 12 || G.kfK.size() != nk * 4 || G.ptPos.size() != np * 3 || G.edgeKf.size() != ne ||
+            G.edgeObs.size() != ne * 2 || G.edgeInvSigma2.size() != ne)
+            throw std::invalid_argument("LocalBundleAdjustment: array sizes disagree");
+        R.kfPose.assign(nk * 12, 0.0f), R.ptPos.assign(np * 3, 0.0f);
+        R.edgeErased.assign(ne, 0), R.ptBad.assign(np, 0);
+        orb_check(orb_local_bundle_adjustment((int)nk, G.kfPose.data(), G.kfK.data(), G.kfFixed.data(), (int)np,
+                                              G.ptPos.data(), G.ptNObs.data(), (int)ne, G.edgePt.data(), G.edgeKf.data(),
+                                              G.edgeObs.data(), G.edgeInvSigma2.data(), R.kfPose.data(), nullptr,
+                                              R.ptPos.data(), nullptr, R.edgeErased.data(), R.ptBad.data(), &R.info,
+                                              device));
+    }
 };
 
 // LocalMapping::CreateNewMapPoints' arithmetic over POD views (LocalMapping.cc:227-393, 474-491) and
-// MapPoint::UpdateNormalAndDepth (MapPoint.cc:273-312).  The thread, the map mutation, the culling and
-// local BA stay with the caller: outputs are indices and points, where the reference calls
-// `new MapPoint(x3D, ...)`, AddObservation and AddMapPoint.
+// MapPoint::UpdateNormalAndDepth (MapPoint.cc:273-312).  The thread, the map mutation and the culling
+// stay with the caller (local BA is gpu::Optimizer::LocalBundleAdjustment): outputs are indices and points,
+// where the reference calls `new MapPoint(x3D, ...)`, AddObservation and AddMapPoint.
 class LocalMapping {
 public:
     // ComputeF12(pKF1, pKF2): row-major 3 x 3, the matrix ORBmatcher::SearchForTriangulation takes.

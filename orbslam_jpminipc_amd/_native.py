@@ -243,6 +243,8 @@ HIP_SIGNATURES = {
     "orb_optimize_sim3": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_optimize_sim3_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_local_bundle_adjustment": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 7 + [_i]),
+    "orb_local_bundle_adjustment_batch_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i] + [_vp] * 17),
     "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),

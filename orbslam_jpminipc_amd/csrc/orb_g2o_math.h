@@ -1,5 +1,6 @@
 // orb_g2o_math.h — the double-precision restatement of g2o and Eigen that the GPU optimizers share
-// (orb_optimizer.hip: PoseOptimization; orb_sim3opt.hip: OptimizeSim3, §14).
+// (orb_optimizer.hip: PoseOptimization; orb_sim3opt.hip: OptimizeSim3, §14;
+// orb_localba.hip: LocalBundleAdjustment, §21).
 //
 // One definition each of the quaternion / rotation helpers, the Huber kernel, Eigen's dense LDLT
 // solve, the Levenberg bookkeeping of optimization_algorithm_levenberg.cpp, the workgroup sum and
@@ -293,6 +294,60 @@ __device__ static inline void rodrigues(const double* O, const double* O2, doubl
 #pragma unroll
         for (int k = 0; k < 9; ++k) R[k] = ((k % 4 == 0 ? 1.0 : 0.0) + a * O[k]) + b * O2[k];
     }
+}
+
+// The SE3 state of a VertexSE3Expmap: SE3Quat as quaternion plus translation (PoseOptimization,
+// LocalBundleAdjustment)
+struct Pose {
+    double q[4];  // x y z w
+    double t[3];
+};
+
+__device__ __forceinline__ void normalize_rotation(Pose& p) {  // se3quat.h:280-285
+    if (p.q[3] < 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p.q[k] *= -1;
+    }
+    const double n = sqrt(p.q[0] * p.q[0] + p.q[1] * p.q[1] + p.q[2] * p.q[2] + p.q[3] * p.q[3]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p.q[k] /= n;
+}
+
+// VertexSE3Expmap::oplusImpl: exp(x) * T with x = (omega, upsilon)
+__device__ Pose exp_update(const double* x, const Pose& T) {
+    const double* om = x;
+    const double* up = x + 3;
+    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+    double O[9], O2[9], R[9], V[9];
+    hat_sq(om, O, O2);
+    rodrigues(O, O2, theta, R);
+    if (theta < 0.00001) {  // se3quat.h:237-243
+#pragma unroll
+        for (int k = 0; k < 9; ++k) V[k] = R[k];
+    } else {
+        const double b = (1 - cos(theta)) / (theta * theta), c = (theta - sin(theta)) / pow(theta, 3.0);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) V[k] = ((k % 4 == 0 ? 1.0 : 0.0) + b * O[k]) + c * O2[k];
+    }
+    Pose e;
+    quat_from_matrix(R, e.q);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double s = V[3 * i] * up[0];
+        s += V[3 * i + 1] * up[1];
+        s += V[3 * i + 2] * up[2];
+        e.t[i] = s;
+    }
+    normalize_rotation(e);
+    // SE3Quat::operator* (se3quat.h:104-110): t += r * T.t; r *= T.r; normalizeRotation
+    Pose r = e;
+    double rt[3];
+    rotate(e.q, T.t, rt);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.t[k] += rt[k];
+    quat_mul(e.q, T.q, r.q);
+    normalize_rotation(r);
+    return r;
 }
 
 constexpr int G2O_WAVES = 4;  // both optimizers run 256-thread workgroups

@@ -17,8 +17,9 @@
 //   dense solver    linear_solver_dense.h:104-112: Eigen::LDLT, refused when not positive
 //   four rounds     Optimizer.cc:242-276
 // The quaternion and rotation helpers, the Huber kernel, ldlt<6>, the Levenberg bookkeeping, the
-// workgroup sum and the compaction step are those of csrc/orb_g2o_math.h, shared with
-// csrc/orb_sim3opt.hip; this unit holds the SE3 state, its edge and the schedule.
+// workgroup sum, the compaction step and the SE3 state with exp(x) * T are those of
+// csrc/orb_g2o_math.h, shared with csrc/orb_sim3opt.hip and csrc/orb_localba.hip; this unit holds
+// the edge and the schedule.
 //
 // Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
 // prepare step.  Sums over edges are taken in a fixed order (thread-strided partial sums, an
@@ -121,58 +122,6 @@ __global__ void __launch_bounds__(PO_THREADS) k_po_prepare(PoArgs a) {
         }
     }
     if (tid == 0) a.n[s] = base;
-}
-
-struct Pose {
-    double q[4];  // x y z w
-    double t[3];
-};
-
-__device__ __forceinline__ void normalize_rotation(Pose& p) {  // se3quat.h:280-285
-    if (p.q[3] < 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) p.q[k] *= -1;
-    }
-    const double n = sqrt(p.q[0] * p.q[0] + p.q[1] * p.q[1] + p.q[2] * p.q[2] + p.q[3] * p.q[3]);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p.q[k] /= n;
-}
-
-// VertexSE3Expmap::oplusImpl: exp(x) * T with x = (omega, upsilon)
-__device__ Pose exp_update(const double* x, const Pose& T) {
-    const double* om = x;
-    const double* up = x + 3;
-    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    double O[9], O2[9], R[9], V[9];
-    hat_sq(om, O, O2);
-    rodrigues(O, O2, theta, R);
-    if (theta < 0.00001) {  // se3quat.h:237-243
-#pragma unroll
-        for (int k = 0; k < 9; ++k) V[k] = R[k];
-    } else {
-        const double b = (1 - cos(theta)) / (theta * theta), c = (theta - sin(theta)) / pow(theta, 3.0);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) V[k] = ((k % 4 == 0 ? 1.0 : 0.0) + b * O[k]) + c * O2[k];
-    }
-    Pose e;
-    quat_from_matrix(R, e.q);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double s = V[3 * i] * up[0];
-        s += V[3 * i + 1] * up[1];
-        s += V[3 * i + 2] * up[2];
-        e.t[i] = s;
-    }
-    normalize_rotation(e);
-    // SE3Quat::operator* (se3quat.h:104-110): t += r * T.t; r *= T.r; normalizeRotation
-    Pose r = e;
-    double rt[3];
-    rotate(e.q, T.t, rt);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r.t[k] += rt[k];
-    quat_mul(e.q, T.q, r.q);
-    normalize_rotation(r);
-    return r;
 }
 
 struct Cam {

@@ -1,7 +1,8 @@
 """LocalMapping::CreateNewMapPoints over the C ABI (csrc/orb_localmap.hip):
 ComputeF12, ComputeSceneMedianDepth, the triangulation of a matched pair with all its gates, and the
-reference's neighbour loop on top of ORBmatcher.SearchForTriangulation.  The thread, the map mutation,
-the culling and local BA stay with the caller: results are indices, points and status codes."""
+reference's neighbour loop on top of ORBmatcher.SearchForTriangulation.  The thread, the map mutation
+and the culling stay with the caller (local BA is Optimizer.local_bundle_adjustment): results are
+indices, points and status codes."""
 from __future__ import annotations
 
 import ctypes

@@ -1,12 +1,15 @@
-"""Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285, csrc/orb_optimizer.hip)
-and Optimizer::OptimizeSim3 (Optimizer.cc:1721-1917, csrc/orb_sim3opt.hip) on the GPU, over the C
+"""Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285, csrc/orb_optimizer.hip),
+Optimizer::OptimizeSim3 (Optimizer.cc:1721-1917, csrc/orb_sim3opt.hip) and
+Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536, csrc/orb_localba.hip) on the GPU, over the C
 ABI of ``include/orb_abi.h``.
 
 The motion-only optimisation of one frame's pose against its keypoint <-> MapPoint associations:
 the whole g2o schedule (four rounds of Levenberg with the outlier classification between them)
 runs in one launch per call, one workgroup per problem.  The Sim3 optimisation of a loop candidate
-(two optimize() calls with the pair classification between and after them) likewise.  Local and
-global bundle adjustment are not part of this package.
+(two optimize() calls with the pair classification between and after them) likewise, and so does
+the local bundle adjustment of a window of keyframes and points (both optimize() calls with the
+Schur complement, and both outlier classifications).  Global bundle adjustment and
+the essential graph are not part of this package.
 """
 from __future__ import annotations
 
@@ -53,6 +56,37 @@ SIM3_INFO_DTYPE = np.dtype([("n_correspondences", "<i4"), ("n_bad", "<i4"), ("mo
 assert SIM3_INFO_DTYPE.itemsize == ctypes.sizeof(Sim3OptInfo) == 40
 
 
+class LocalBARound(ctypes.Structure):
+    """orb_local_ba_round_t."""
+
+    _fields_ = [("iterations", ctypes.c_int32), ("trials", ctypes.c_int32), ("active_edges", ctypes.c_int32),
+                ("active_points", ctypes.c_int32), ("active_keyframes", ctypes.c_int32), ("refused", ctypes.c_int32),
+                ("lambda_", ctypes.c_double), ("chi2_before", ctypes.c_double), ("chi2_after", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"iterations": self.iterations, "trials": self.trials, "active_edges": self.active_edges,
+                "active_points": self.active_points, "active_keyframes": self.active_keyframes,
+                "refused": self.refused, "lambda": self.lambda_, "chi2_before": self.chi2_before,
+                "chi2_after": self.chi2_after}
+
+
+class LocalBAInfo(ctypes.Structure):
+    """orb_local_ba_info_t."""
+
+    _fields_ = [("status", ctypes.c_int32), ("n_free_kf", ctypes.c_int32), ("round", LocalBARound * 2)]
+
+    def as_dict(self) -> dict:
+        return {"status": self.status, "n_free_kf": self.n_free_kf, "round": [r.as_dict() for r in self.round]}
+
+
+LOCAL_BA_ROUND_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("active_edges", "<i4"),
+                                 ("active_points", "<i4"), ("active_keyframes", "<i4"), ("refused", "<i4"),
+                                 ("lambda", "<f8"), ("chi2_before", "<f8"), ("chi2_after", "<f8")])
+LOCAL_BA_INFO_DTYPE = np.dtype([("status", "<i4"), ("n_free_kf", "<i4"), ("round", LOCAL_BA_ROUND_DTYPE, (2,))])
+assert LOCAL_BA_INFO_DTYPE.itemsize == ctypes.sizeof(LocalBAInfo) == 104
+LOCAL_BA_MAX_FREE_KF = 64  # ORB_LBA_MAX_FREE_KF
+
+
 def _sim3_13(sim3) -> np.ndarray:
     """13 floats (R row-major, t, s) from that, or from a (R, t, s) triple."""
     if isinstance(sim3, (tuple, list)) and len(sim3) == 3:
@@ -75,8 +109,8 @@ def _pose12(pose) -> np.ndarray:
 
 
 class Optimizer:
-    """The GPU half of the reference's Optimizer: ``pose_optimization``, ``optimize_sim3`` and their
-    batch forms."""
+    """The GPU half of the reference's Optimizer: ``pose_optimization``, ``optimize_sim3``,
+    ``local_bundle_adjustment`` and their batch forms."""
 
     def __init__(self, device: int = 0):
         self._lib = hip_lib()
@@ -245,4 +279,91 @@ class Optimizer:
             ptr(d_pose.contiguous()), ptr(tab), ptr(inv), len(tab), ptr(K4), float(th2), ptr(d_sim3_in.contiguous()),
             ptr(out["match"]), ptr(out["sim3"]), ptr(out.get("sim3_f64")), ptr(out["n_inliers"]),
             ptr(out.get("info")), ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+    def local_bundle_adjustment(self, kf_pose, kf_K, kf_fixed, pt_pos, pt_nobs, edge_pt, edge_kf, edge_obs,
+                                edge_inv_sigma2, want_info: bool = True) -> dict:
+        """One window (host buffers, synchronous): Optimizer::LocalBundleAdjustment on the graph of
+        Optimizer.cc:356-447 as flat arrays.  kf_pose (n_kf, 12) (Rcw row-major, tcw) or (n_kf, 4, 4),
+        local keyframes first, then fixed; kf_K (n_kf, 4) fx fy cx cy; kf_fixed (n_kf,) flags; pt_pos
+        (n_pt, 3); pt_nobs (n_pt,) = mObservations.size() at entry; the edges in creation order, those
+        of a point contiguous and the points ascending: edge_pt / edge_kf (n_edge,) indices, edge_obs
+        (n_edge, 2) undistorted positions, edge_inv_sigma2 (n_edge,).  Returns kf_pose (n_kf, 12)
+        float32, kf_pose_f64, pt_pos (n_pt, 3) float32, pt_pos_f64, edge_erased (n_edge,) uint8 (0
+        kept, 1 / 2 the round after which the edge was erased; walk it in edge order to mutate the
+        map as the reference does), pt_bad (n_pt,) uint8 and info."""
+        kp = np.asarray(kf_pose, np.float32)
+        if kp.ndim == 3 and kp.shape[1:] == (4, 4):
+            kp = np.concatenate([kp[:, :3, :3].reshape(-1, 9), kp[:, :3, 3]], 1)
+        kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 12)
+        kK = np.ascontiguousarray(kf_K, np.float32).reshape(-1, 4)
+        kf = np.ascontiguousarray(kf_fixed, np.uint8).reshape(-1)
+        pp = np.ascontiguousarray(pt_pos, np.float32).reshape(-1, 3)
+        pn = np.ascontiguousarray(pt_nobs, np.int32).reshape(-1)
+        ep = np.ascontiguousarray(edge_pt, np.int32).reshape(-1)
+        ek = np.ascontiguousarray(edge_kf, np.int32).reshape(-1)
+        eo = np.ascontiguousarray(edge_obs, np.float32).reshape(-1, 2)
+        es = np.ascontiguousarray(edge_inv_sigma2, np.float32).reshape(-1)
+        nk, npt, ne = len(kp), len(pp), len(ep)
+        if len(kK) != nk or len(kf) != nk or len(pn) != npt or len(ek) != ne or len(eo) != ne or len(es) != ne:
+            raise ValueError("the keyframe, point and edge arrays must hold one entry per keyframe, point and edge")
+        out = {"kf_pose": np.zeros((nk, 12), np.float32), "kf_pose_f64": np.zeros((nk, 12), np.float64),
+               "pt_pos": np.zeros((npt, 3), np.float32), "pt_pos_f64": np.zeros((npt, 3), np.float64),
+               "edge_erased": np.zeros(ne, np.uint8), "pt_bad": np.zeros(npt, np.uint8)}
+        info = LocalBAInfo()
+        check(self._lib.orb_local_bundle_adjustment(
+            nk, ptr(kp), ptr(kK), ptr(kf), npt, ptr(pp), ptr(pn), ne, ptr(ep), ptr(ek), ptr(eo), ptr(es),
+            ptr(out["kf_pose"]), ptr(out["kf_pose_f64"]), ptr(out["pt_pos"]), ptr(out["pt_pos_f64"]),
+            ptr(out["edge_erased"]), ptr(out["pt_bad"]), ctypes.addressof(info) if want_info else None, self.device))
+        if want_info:
+            out["info"] = info.as_dict()
+        return out
+
+    def local_bundle_adjustment_batch_device(self, kf_off, pt_off, edge_off, d_kf_pose, d_kf_K, d_kf_fixed, d_pt_pos,
+                                             d_pt_nobs, d_edge_pt, d_edge_kf, d_edge_obs, d_edge_inv_sigma2,
+                                             want_f64: bool = True, want_info: bool = True, stream=None,
+                                             out: dict = None) -> dict:
+        """S windows on device arrays (orb_local_bundle_adjustment_batch_device).  kf_off / pt_off /
+        edge_off: (S + 1,) int32 device tensors of offsets into the concatenated keyframe, point and
+        edge tensors (d_kf_pose (NK, 12), d_kf_K (NK, 4), d_kf_fixed (NK,) uint8, d_pt_pos (NP, 3),
+        d_pt_nobs (NP,) int32, d_edge_pt / d_edge_kf (NE,) int32 problem-local, d_edge_obs (NE, 2),
+        d_edge_inv_sigma2 (NE,)); rows past the last offset are not read.  Returns device tensors in
+        the same layout: kf_pose (NK, 12) float32, kf_pose_f64, pt_pos (NP, 3), pt_pos_f64,
+        edge_erased (NE,) uint8, pt_bad (NP,) uint8 and info (S, 104) uint8 (view it as
+        LOCAL_BA_INFO_DTYPE on the host; its status names a problem that was refused and left
+        unwritten).  `out`: tensors to write into instead of new ones.  Asynchronous on `stream`."""
+        import torch
+
+        S = int(kf_off.shape[0]) - 1
+        if S < 0 or int(pt_off.shape[0]) != S + 1 or int(edge_off.shape[0]) != S + 1:
+            raise ValueError("kf_off, pt_off and edge_off must hold S + 1 offsets each")
+        for t, dt, tail in ((kf_off, torch.int32, ()), (pt_off, torch.int32, ()), (edge_off, torch.int32, ()),
+                            (d_kf_pose, torch.float32, (12,)), (d_kf_K, torch.float32, (4,)),
+                            (d_kf_fixed, torch.uint8, ()), (d_pt_pos, torch.float32, (3,)), (d_pt_nobs, torch.int32, ()),
+                            (d_edge_pt, torch.int32, ()), (d_edge_kf, torch.int32, ()), (d_edge_obs, torch.float32, (2,)),
+                            (d_edge_inv_sigma2, torch.float32, ())):
+            if t.dtype != dt or tuple(t.shape[1:]) != tail or not t.is_contiguous():
+                raise ValueError("a tensor has the wrong dtype or shape, or is not contiguous")
+        NK, NP, NE = int(d_kf_pose.shape[0]), int(d_pt_pos.shape[0]), int(d_edge_pt.shape[0])
+        if int(d_kf_K.shape[0]) != NK or int(d_kf_fixed.shape[0]) != NK or int(d_pt_nobs.shape[0]) != NP or \
+                int(d_edge_kf.shape[0]) != NE or int(d_edge_obs.shape[0]) != NE or int(d_edge_inv_sigma2.shape[0]) != NE:
+            raise ValueError("the keyframe, point and edge tensors must hold one row per keyframe, point and edge")
+        dev = d_kf_pose.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if out is None:
+            with torch.cuda.stream(s):
+                out = {"kf_pose": torch.empty((NK, 12), dtype=torch.float32, device=dev),
+                       "pt_pos": torch.empty((NP, 3), dtype=torch.float32, device=dev),
+                       "edge_erased": torch.empty((NE,), dtype=torch.uint8, device=dev),
+                       "pt_bad": torch.empty((NP,), dtype=torch.uint8, device=dev)}
+                if want_f64:
+                    out["kf_pose_f64"] = torch.empty((NK, 12), dtype=torch.float64, device=dev)
+                    out["pt_pos_f64"] = torch.empty((NP, 3), dtype=torch.float64, device=dev)
+                if want_info:
+                    out["info"] = torch.empty((S, LOCAL_BA_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        check(self._lib.orb_local_bundle_adjustment_batch_device(
+            S, ptr(kf_off), ptr(pt_off), ptr(edge_off), NK, NP, NE, ptr(d_kf_pose), ptr(d_kf_K), ptr(d_kf_fixed),
+            ptr(d_pt_pos), ptr(d_pt_nobs), ptr(d_edge_pt), ptr(d_edge_kf), ptr(d_edge_obs), ptr(d_edge_inv_sigma2),
+            ptr(out.get("kf_pose")), ptr(out.get("kf_pose_f64")), ptr(out.get("pt_pos")), ptr(out.get("pt_pos_f64")),
+            ptr(out.get("edge_erased")), ptr(out.get("pt_bad")), ptr(out.get("info")), ctypes.c_void_p(s.cuda_stream)))
         return out
