@@ -24,6 +24,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "orb_cv_math.h"
+
 #if defined(__HIPCC__)
 #define EPNP_HD __host__ __device__
 #else
@@ -69,20 +71,7 @@ EPNP_HD inline double fma_(double a, double b, double c) { return __builtin_fma(
 
 // ---- OpenCV 2.4, as read ---------------------------------------------------------------------------
 
-// lapack.cpp's own hypot
-EPNP_HD inline double cv_hypot(double a, double b) {
-    a = fabs(a);
-    b = fabs(b);
-    if (a > b) {
-        b /= a;
-        return a * sqrt(1 + b * b);
-    }
-    if (b > 0) {
-        a /= b;
-        return b * sqrt(1 + a * a);
-    }
-    return 0;
-}
+// (lapack.cpp's own hypot: orb_cv::cv_hypot of csrc/orb_cv_math.h)
 
 // The fill-in `while` has no bound in OpenCV; as in §16 it gives up after this many tries.
 constexpr int MAX_FILL_TRIES = 16;
@@ -131,7 +120,7 @@ EPNP_HD inline void jacobi_svd(M At, int astep, M W, M Vt, bool vt, int vstep, i
                     continue;
                 }
                 p *= 2;
-                double beta = a - b, gamma = cv_hypot(p, beta);
+                double beta = a - b, gamma = orb_cv::cv_hypot(p, beta);
                 if (beta < 0) {
                     br |= BR_SVD_BETA_NEG;
                     double delta = (gamma - beta) * 0.5;

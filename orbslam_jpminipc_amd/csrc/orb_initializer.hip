@@ -15,6 +15,8 @@
 //   dx*dx + dy*dy, a*a + b*b   ->  fmaf(dx, dx, dy*dy)
 //   1.0/(float)                ->  a float divide (correctly rounded; equal to the double divide
 //                                  rounded to float for every float divisor)
+// The cv::Mat arithmetic of the second and third part (3 x 3 products, inv(), determinant, norm, scale) is
+// csrc/orb_cv_math.h's, Triangulate csrc/orb_jacobi_svd.h's.
 // `score` is ONE float accumulated in match order, first-image term before second-image term;
 // the terms are computed in parallel, the adds of one hypothesis form one chain on one lane.
 //
@@ -41,6 +43,17 @@
 #include "orb_jacobi_svd.h"
 
 namespace {
+
+// cv::Mat arithmetic on 3-vectors and 3 x 3 matrices: csrc/orb_cv_math.h
+using orb_cv::det3;
+using orb_cv::gemm3;
+using orb_cv::inv3;
+using orb_cv::M3;
+using orb_cv::mul3;
+using orb_cv::mul3_alpha;
+using orb_cv::neg3x3;
+using orb_cv::norm3;
+using orb_cv::scale3;
 
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
@@ -611,50 +624,6 @@ __global__ void __launch_bounds__(NORM_THREADS) k_init_normalize(HypArgs a) {
     }
 }
 
-struct M3 {
-    float m[9];
-};
-
-// gemm's 2 <= len <= 4 path, alpha = 1, no C: (float)((double)t * 1.0) is t
-__device__ __forceinline__ M3 hy_mul3(const M3& a, const M3& b) {
-    M3 d;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d.m[3 * i + 0] = a.m[3 * i] * b.m[0] + a.m[3 * i + 1] * b.m[3] + a.m[3 * i + 2] * b.m[6];
-        d.m[3 * i + 1] = a.m[3 * i] * b.m[1] + a.m[3 * i + 1] * b.m[4] + a.m[3 * i + 2] * b.m[7];
-        d.m[3 * i + 2] = a.m[3 * i] * b.m[2] + a.m[3 * i + 1] * b.m[5] + a.m[3 * i + 2] * b.m[8];
-    }
-    return d;
-}
-
-// Mat::inv() of a 3x3 CV_32F: the closed form in double, zeros when det == 0
-__device__ __forceinline__ M3 hy_inv3(const M3& S) {
-#define SF(y, x) S.m[(y)*3 + (x)]
-#define DD(a, b, c, d) ((double)(a) * (double)(b) - (double)(c) * (double)(d))
-    double d = (double)SF(0, 0) * DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) -
-               (double)SF(0, 1) * DD(SF(1, 0), SF(2, 2), SF(1, 2), SF(2, 0)) +
-               (double)SF(0, 2) * DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0));
-    M3 D;
-    if (d != 0.) {
-        d = 1. / d;
-        D.m[0] = (float)(DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) * d);
-        D.m[1] = (float)(DD(SF(0, 2), SF(2, 1), SF(0, 1), SF(2, 2)) * d);
-        D.m[2] = (float)(DD(SF(0, 1), SF(1, 2), SF(0, 2), SF(1, 1)) * d);
-        D.m[3] = (float)(DD(SF(1, 2), SF(2, 0), SF(1, 0), SF(2, 2)) * d);
-        D.m[4] = (float)(DD(SF(0, 0), SF(2, 2), SF(0, 2), SF(2, 0)) * d);
-        D.m[5] = (float)(DD(SF(0, 2), SF(1, 0), SF(0, 0), SF(1, 2)) * d);
-        D.m[6] = (float)(DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0)) * d);
-        D.m[7] = (float)(DD(SF(0, 1), SF(2, 0), SF(0, 0), SF(2, 1)) * d);
-        D.m[8] = (float)(DD(SF(0, 0), SF(1, 1), SF(0, 1), SF(1, 0)) * d);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) D.m[k] = 0.0f;
-    }
-#undef DD
-#undef SF
-    return D;
-}
-
 __device__ __forceinline__ void hy_store9(float* dst, long long g, const M3& v) {
     if (!dst) return;
 #pragma unroll
@@ -767,10 +736,10 @@ __global__ void __launch_bounds__(64) k_init_hypotheses(HypArgs a, int tiles) {
         M3 Hn;
 #pragma unroll
         for (int k = 0; k < 9; ++k) Hn.m[k] = V[(8 * 9 + k) * 64];  // vt.row(8)
-        const M3 H21 = hy_mul3(hy_mul3(hy_inv3(T2), Hn), T1);       // T2inv*Hn*T1
+        const M3 H21 = mul3(mul3(inv3(T2), Hn), T1);       // T2inv*Hn*T1
         hy_store9(a.Hn, g, Hn);
         hy_store9(a.H21, g, H21);
-        hy_store9(a.H12, g, hy_inv3(H21));
+        hy_store9(a.H12, g, inv3(H21));
     } else {
 #pragma unroll
         for (int c = 0; c < 9; ++c) A[(8 * 9 + c) * 64] = 0.0f;
@@ -794,14 +763,14 @@ __global__ void __launch_bounds__(64) k_init_hypotheses(HypArgs a, int tiles) {
             }
         D.m[0] = (float)W[0];
         D.m[4] = (float)W[64];  // w[2] = 0
-        const M3 Fn = hy_mul3(hy_mul3(u, D), vt);
+        const M3 Fn = mul3(mul3(u, D), vt);
         M3 T2t;
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c) T2t.m[r * 3 + c] = T2.m[c * 3 + r];
         hy_store9(a.Fn, g, Fn);
-        hy_store9(a.F21, g, hy_mul3(hy_mul3(T2t, Fn), T1));  // T2t*Fn*T1
+        hy_store9(a.F21, g, mul3(mul3(T2t, Fn), T1));  // T2t*Fn*T1
     }
 }
 
@@ -1110,7 +1079,6 @@ int orb_initializer_ransac_batch_device(const orb_keypoint_t* d_kps, const int32
 namespace {
 
 constexpr int RC_THREADS = 256;
-constexpr int RC_WAVE_BYTES = 32 * 64 * 4 + 4 * 64 * 8;  // At and Vt (4 x 4 floats each) and W (4 doubles) of 64 lanes
 constexpr double RC_PI = 3.1415926535897932384626433832795;  // CV_PI
 
 struct RecArgs {
@@ -1158,68 +1126,12 @@ __device__ __forceinline__ PairView rec_view(const RecArgs& a, int p) {
     return pair_view(ia, p);
 }
 
-// cv::determinant of a 3 x 3 CV_32F (lapack.cpp's det3): a double
-__device__ __forceinline__ double rc_det3(const M3& s) {
-    const float* m = s.m;
-    return (double)m[0] * ((double)m[4] * (double)m[8] - (double)m[5] * (double)m[7]) -
-           (double)m[1] * ((double)m[3] * (double)m[8] - (double)m[5] * (double)m[6]) +
-           (double)m[2] * ((double)m[3] * (double)m[7] - (double)m[4] * (double)m[6]);
-}
-
-// gemm with a transpose flag: not the 2 <= len <= 4 path but GEMMSingleMul_<float, double>, one
-// double accumulator per element, k ascending
-template <bool TA, bool TB>
-__device__ __forceinline__ M3 rc_gemm_general(const M3& a, const M3& b) {
-    M3 d;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s0 = 0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                s0 += (double)(TA ? a.m[k * 3 + i] : a.m[i * 3 + k]) * (double)(TB ? b.m[j * 3 + k] : b.m[k * 3 + j]);
-            d.m[i * 3 + j] = (float)s0;
-        }
-    return d;
-}
-
-// (alpha*A)*B: gemm's short path with alpha, (float)((double)t * alpha)
-__device__ __forceinline__ M3 rc_mul3_alpha(const M3& a, const M3& b, double alpha) {
-    M3 d = hy_mul3(a, b);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) d.m[k] = (float)((double)d.m[k] * alpha);
-    return d;
-}
-
-// M / s, M *= s: convertTo with alpha, x * (float)alpha + (float)0
-__device__ __forceinline__ void rc_scale3(const float* x, double alpha, float* out) {
-    const float a = (float)alpha;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k] = x[k] * a + 0.0f;
-}
-
-__device__ __forceinline__ double rc_norm3(const float* v) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s += (double)v[k] * (double)v[k];
-    return __builtin_sqrt(s);
-}
-
-// -M of a Mat: subtract(Scalar(0), M)
-__device__ __forceinline__ M3 rc_neg(const M3& a) {
-    M3 d;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) d.m[k] = 0.0f - a.m[k];
-    return d;
-}
-
 // U * tp (3 x 3 by 3 x 1, the short path), then t / cv::norm(t)
 __device__ __forceinline__ void rc_unit_Ut(const M3& U, const float* tp, float* out) {
     float t[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) t[r] = U.m[3 * r] * tp[0] + U.m[3 * r + 1] * tp[1] + U.m[3 * r + 2] * tp[2];
-    rc_scale3(t, 1. / rc_norm3(t), out);
+    scale3(t, 1. / norm3(t), out);
 }
 
 // SVD::compute of a 3 x 3 on column 0 of the given LDS regions (the transpose path of §16)
@@ -1283,21 +1195,21 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_motion(RecArgs a) {
     float w[3];
     if (!use_h) {
         // ReconstructF: E21 = K.t()*F21*K (the first product carries GEMM_1_T), DecomposeE
-        const M3 E = hy_mul3(rc_gemm_general<true, false>(K, M), K);
+        const M3 E = mul3(gemm3<true, false>(K, M, 1.0), K);
         rc_svd3(E, s_a, s_v, s_w, &U, &Vt, w);
         const float col[3] = {U.m[2], U.m[5], U.m[8]};
         float t1[3], t2[3];
-        rc_scale3(col, 1. / rc_norm3(col), t1);  // t = t/cv::norm(t)
+        scale3(col, 1. / norm3(col), t1);  // t = t/cv::norm(t)
         M3 W;
         {
             const float wm[9] = {0.0f, -1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
 #pragma unroll
             for (int e = 0; e < 9; ++e) W.m[e] = wm[e];
         }
-        M3 R1 = hy_mul3(hy_mul3(U, W), Vt);
-        if (rc_det3(R1) < 0) R1 = rc_neg(R1);
-        M3 R2 = hy_mul3(rc_gemm_general<false, true>(U, W), Vt);  // u*W.t()*vt: GEMM_2_T
-        if (rc_det3(R2) < 0) R2 = rc_neg(R2);
+        M3 R1 = mul3(mul3(U, W), Vt);
+        if (det3(R1) < 0) R1 = neg3x3(R1);
+        M3 R2 = mul3(gemm3<false, true>(U, W, 1.0), Vt);  // u*W.t()*vt: GEMM_2_T
+        if (det3(R2) < 0) R2 = neg3x3(R2);
 #pragma unroll
         for (int e = 0; e < 3; ++e) t2[e] = 0.0f - t1[e];
         rc_store_motion(a, p, 0, R1, t1);
@@ -1308,9 +1220,9 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_motion(RecArgs a) {
         return;
     }
     // ReconstructH (Faugeras); vn is computed by the reference and never read: skipped
-    const M3 A = hy_mul3(hy_mul3(hy_inv3(K), M), K);
+    const M3 A = mul3(mul3(inv3(K), M), K);
     rc_svd3(A, s_a, s_v, s_w, &U, &Vt, w);
-    const float s = (float)(rc_det3(U) * rc_det3(Vt));
+    const float s = (float)(det3(U) * det3(Vt));
     const float d1 = w[0], d2 = w[1], d3 = w[2];
     if ((double)(d1 / d2) < 1.00001 || (double)(d2 / d3) < 1.00001) {
         a.n_motion[p] = 0;
@@ -1339,18 +1251,18 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_motion(RecArgs a) {
             for (int e = 0; e < 9; ++e) Rp.m[e] = r[e];
         }
         tp[0] = x1, tp[1] = 0.0f, tp[2] = -x3;
-        rc_scale3(tp, (double)(d1 - d3), tp);  // tp *= d1-d3
+        scale3(tp, (double)(d1 - d3), tp);  // tp *= d1-d3
         rc_unit_Ut(U, tp, t);
-        rc_store_motion(a, p, i, hy_mul3(rc_mul3_alpha(U, Rp, (double)s), Vt), t);  // s*U*Rp*Vt
+        rc_store_motion(a, p, i, mul3(mul3_alpha(U, Rp, (double)s), Vt), t);  // s*U*Rp*Vt
         {
             const float r[9] = {cphi, 0.0f, sp, 0.0f, -1.0f, 0.0f, sp, 0.0f, -cphi};
 #pragma unroll
             for (int e = 0; e < 9; ++e) Rp.m[e] = r[e];
         }
         tp[0] = x1, tp[1] = 0.0f, tp[2] = x3;
-        rc_scale3(tp, (double)(d1 + d3), tp);  // tp *= d1+d3
+        scale3(tp, (double)(d1 + d3), tp);  // tp *= d1+d3
         rc_unit_Ut(U, tp, t);
-        rc_store_motion(a, p, 4 + i, hy_mul3(rc_mul3_alpha(U, Rp, (double)s), Vt), t);
+        rc_store_motion(a, p, 4 + i, mul3(mul3_alpha(U, Rp, (double)s), Vt), t);
     }
     a.n_motion[p] = 8;
 }
@@ -1374,58 +1286,33 @@ __device__ __forceinline__ RcPose rc_pose(const RecArgs& a, int p, int h) {
             const float b0 = j < 3 ? q.R[j] : q.t[0], b1 = j < 3 ? q.R[3 + j] : q.t[1], b2 = j < 3 ? q.R[6 + j] : q.t[2];
             q.P2[i * 4 + j] = K[3 * i] * b0 + K[3 * i + 1] * b1 + K[3 * i + 2] * b2;
         }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {  // one gemm, GEMM_1_T, alpha = -1
-        double s0 = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s0 += (double)q.R[k * 3 + i] * (double)q.t[k];
-        q.O2[i] = (float)(s0 * -1.0);
-    }
+    orb_cv::camera_centre(q.R, q.t, q.O2);
     return q;
 }
 
 // One match of CheckRT (Initializer.cc:830-891) on the lane's LDS column.  Returns bit 0: counted
 // (nGood, vCosParallax, vP3D), bit 1: vbGood.
-__device__ int rc_check_one(const RecArgs& a, const RcPose& q, float x1, float y1, float x2, float y2, float* At,
-                            float* Vt, double* W, float* cosp, float* pt) {
-    // Triangulate: A.row(r) = x*P.row(2) - P.row(r & 1) is addWeighted_<float, double>(a, x, b, -1, 0)
+__device__ int rc_check_one(const RecArgs& a, const RcPose& q, float x1, float y1, float x2, float y2,
+                            const TriColumn& col, float* cosp, float* pt) {
+    // Triangulate with P1 = K[I|0] and P2
     const float P1[12] = {a.fx, 0.0f, a.cx, 0.0f, 0.0f, a.fy, a.cy, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
     const float xs[4] = {x1, y1, x2, y2};
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float* P = r < 2 ? P1 : q.P2;
-            const float e = (float)((double)P[8 + j] * (double)xs[r] + (double)P[(r & 1) * 4 + j] * -1.0 + 0.0);
-            At[(j * 4 + r) * 64] = e;  // the work matrix is the transpose
-        }
-    hy_jacobi<4, 4, 0, true>(At, Vt, W);
     float vr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) vr[k] = Vt[(12 + k) * 64];  // vt.row(3)
+    triangulate_vt3(P1, q.P2, xs, col, vr);
     float p3[3];
-    rc_scale3(vr, 1. / (double)vr[3], p3);  // rowRange(0,3)/x3D.at<float>(3): a MatExpr scale
+    scale3(vr, 1. / (double)vr[3], p3);  // rowRange(0,3)/x3D.at<float>(3): a MatExpr scale
     if (!__builtin_isfinite(p3[0]) || !__builtin_isfinite(p3[1]) || !__builtin_isfinite(p3[2])) return 0;
+    const float O1[3] = {0.0f, 0.0f, 0.0f};
     float n1[3], n2[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        n1[k] = p3[k] - 0.0f;  // O1
-        n2[k] = p3[k] - q.O2[k];
-    }
-    const float dist1 = (float)rc_norm3(n1);
-    const float dist2 = (float)rc_norm3(n2);
-    double dot = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dot += (double)n1[k] * (double)n2[k];
-    const float cosParallax = (float)(dot / (double)(dist1 * dist2));
+    orb_cv::sub3(p3, O1, n1);
+    orb_cv::sub3(p3, q.O2, n2);
+    const float dist1 = (float)norm3(n1);
+    const float dist2 = (float)norm3(n2);
+    const float cosParallax = (float)(orb_cv::dot3(n1, n2) / (double)(dist1 * dist2));
     const bool low = (double)cosParallax < 0.99998;
     if (p3[2] <= 0.0f && low) return 0;
     float p2[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {  // R*p3dC1+t: gemm(R, p, 1, t, 1), the short path
-        const float ti = q.R[3 * i] * p3[0] + q.R[3 * i + 1] * p3[1] + q.R[3 * i + 2] * p3[2];
-        p2[i] = (float)((double)ti * 1.0 + (double)q.t[i] * 1.0);
-    }
+    orb_cv::gemm3_add(q.R, p3, q.t, p2);  // R*p3dC1+t
     if (p2[2] <= 0.0f && low) return 0;
     const float invZ1 = (float)(1.0 / (double)p3[2]);
     const float im1x = __builtin_fmaf(a.fx * p3[0], invZ1, a.cx);
@@ -1443,7 +1330,7 @@ __device__ int rc_check_one(const RecArgs& a, const RcPose& q, float x1, float y
 }
 
 __global__ void __launch_bounds__(64) k_init_checkrt(RecArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[RC_WAVE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[TRI_WAVE_BYTES];
     const int p = blockIdx.z, h = blockIdx.y, lane = threadIdx.x;
     const int o = blockIdx.x * 64 + lane;
     if (h >= a.n_motion[p] || o >= a.nwalk[p]) return;  // (no barrier below: every lane works on its own column)
@@ -1457,8 +1344,7 @@ __global__ void __launch_bounds__(64) k_init_checkrt(RecArgs a) {
         const int m = v.m12[i];
         const RcPose q = rc_pose(a, p, h);
         float pt[3];
-        fl = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, (float*)smem + lane,
-                          (float*)smem + 16 * 64 + lane, (double*)(smem + 32 * 64 * 4) + lane, &cs, pt);
+        fl = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, TriColumn(smem, lane), &cs, pt);
     }
     a.flags[row + o] = (uint8_t)fl;
     a.cosv[row + o] = cs;
@@ -1515,7 +1401,7 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_stat(RecArgs a) {
 }
 
 __global__ void __launch_bounds__(RC_THREADS) k_init_select(RecArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[(RC_THREADS / 64) * RC_WAVE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[(RC_THREADS / 64) * TRI_WAVE_BYTES];
     __shared__ int s_best;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nm = a.n_motion[p];
@@ -1573,15 +1459,14 @@ __global__ void __launch_bounds__(RC_THREADS) k_init_select(RecArgs a) {
     const PairView v = rec_view(a, p);
     const RcPose q = rc_pose(a, p, b);
     const uint8_t* fl = a.flags + ((size_t)p * 8 + b) * a.cap;
-    uint8_t* sm = smem + wave * RC_WAVE_BYTES;
+    const TriColumn col(smem + wave * TRI_WAVE_BYTES, lane);
     const int Nw = a.nwalk[p];
     for (int o = tid; o < Nw; o += RC_THREADS) {
         if (!(fl[o] & 1)) continue;
         const int i = a.ord_i[(size_t)p * a.cap + o];
         const int m = v.m12[i];
         float cs, pt[3] = {0.0f, 0.0f, 0.0f};
-        const int f = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, (float*)sm + lane,
-                                   (float*)sm + 16 * 64 + lane, (double*)(sm + 32 * 64 * 4) + lane, &cs, pt);
+        const int f = rc_check_one(a, q, v.k1[i].x, v.k1[i].y, v.k2[m].x, v.k2[m].y, col, &cs, pt);
         if (P3D) P3D[3 * i] = pt[0], P3D[3 * i + 1] = pt[1], P3D[3 * i + 2] = pt[2];
         if (tri) tri[i] = (f & 2) ? 1 : 0;
     }

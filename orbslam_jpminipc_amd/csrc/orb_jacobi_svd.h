@@ -1,26 +1,13 @@
 // orb_jacobi_svd.h — OpenCV 2.4's JacobiSVDImpl_<float> as read, on one lane's
 // column of LDS.  Device code shared by orb_initializer.hip (ComputeH21 / ComputeF21, DecomposeE,
 // ReconstructH, Triangulate) and orb_localmap.hip (CreateNewMapPoints' triangulation): one text, so
-// the two units cannot drift apart.
+// the two units cannot drift apart.  The scalar arithmetic (hypot, addWeighted) is csrc/orb_cv_math.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
-constexpr int HY_MAX_FILL_TRIES = 16;                       // OpenCV's fill-in `while` has no bound; §16
+#include "orb_cv_math.h"
 
-// lapack.cpp's own hypot (found before libm's inside namespace cv)
-__device__ __forceinline__ double hy_hypot(double a, double b) {
-    a = fabs(a);
-    b = fabs(b);
-    if (a > b) {
-        b /= a;
-        return a * __builtin_sqrt(1 + b * b);
-    }
-    if (b > 0) {
-        a /= b;
-        return b * __builtin_sqrt(1 + a * a);
-    }
-    return 0;
-}
+constexpr int HY_MAX_FILL_TRIES = 16;                       // OpenCV's fill-in `while` has no bound; §16
 
 // JacobiSVDImpl_<float> on the lane's column of LDS: A = At, N rows of M (N1 rows when the rows
 // past N are filled in), V = Vt (N x N) when HASV, W = N doubles.  Element e of a region is at
@@ -53,7 +40,7 @@ __device__ void hy_jacobi(float* A, float* V, double* W) {
                 for (int k = 0; k < M; ++k) p += (double)Ai[k * 64] * (double)Aj[k * 64];
                 if (fabs(p) <= (double)eps * __builtin_sqrt(a * b)) continue;
                 p *= 2;
-                const double beta = a - b, gamma = hy_hypot(p, beta);
+                const double beta = a - b, gamma = orb_cv::cv_hypot(p, beta);
                 float c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;
@@ -159,4 +146,31 @@ __device__ void hy_jacobi(float* A, float* V, double* W) {
         const float s = (float)(1 / sd);
         for (int k = 0; k < M; ++k) Ai[k * 64] *= s;
     }
+}
+
+// ---- Triangulate (Initializer.cc:734-751, LocalMapping.cc:304-320) ---------------------------------
+// The lane's column of a wave's TRI_WAVE_BYTES of LDS: At and Vt (4 x 4 floats each), then W (4
+// doubles), element e of a region at [e * 64].
+constexpr int TRI_WAVE_BYTES = 32 * 64 * 4 + 4 * 64 * 8;
+struct TriColumn {
+    float *At, *Vt;
+    double* W;
+    __device__ __forceinline__ TriColumn(uint8_t* wave_base, int lane)
+        : At((float*)wave_base + lane), Vt(At + 16 * 64), W((double*)(wave_base + 32 * 64 * 4) + lane) {}
+};
+
+// A.row(r) = xs[r]*P.row(2) - P.row(r & 1) with P = Pa for r < 2 and Pb after (row-major 3 x 4), each
+// element one addWeighted; the SVD of A on the column (the work matrix is the transpose); vr = vt.row(3)
+__device__ __forceinline__ void triangulate_vt3(const float* Pa, const float* Pb, const float* xs, const TriColumn& c,
+                                                float* vr) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float* P = r < 2 ? Pa : Pb;
+            c.At[(j * 4 + r) * 64] = orb_cv::add_weighted(P[8 + j], (double)xs[r], P[(r & 1) * 4 + j], -1.0);
+        }
+    hy_jacobi<4, 4, 0, true>(c.At, c.Vt, c.W);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) vr[k] = c.Vt[(12 + k) * 64];
 }

@@ -4,7 +4,8 @@
 // (src/LocalMapping.cc:227-393, 474-491; KeyFrame::ComputeSceneMedianDepth, src/KeyFrame.cc:659-689),
 // DESIGN.md §20; the CPU statement of the same reading is tests/native/local_mapping_model.cpp, which
 // shares no text with this file.  IEEE f32 / f64 operations, the reference build's three fused
-// multiply-adds per image written out, no libm call.
+// multiply-adds per image written out, no libm call.  The cv::Mat arithmetic is csrc/orb_cv_math.h's,
+// the triangulation's fill and SVD csrc/orb_jacobi_svd.h's.
 //
 //   lm_compute_f12   ComputeF12 as a __host__ __device__ function: orb_compute_f12 runs it on the host,
 //                    k_lm_triangulate on thread 0 where the caller asks for F12.
@@ -32,70 +33,26 @@ int fail(int code, const std::string& msg) { return orb_internal_set_error(code,
 constexpr int LM_MAX_CAP = 8192;
 constexpr int LM_MAX_PAIRS = 65535;
 constexpr int LM_THREADS = 256;  // 160 B of LDS per lane
-constexpr int LM_WAVE_BYTES = 32 * 64 * 4 + 4 * 64 * 8;  // At and Vt (4 x 4 floats each) and W (4 doubles) of 64 lanes
 
-struct LmM3 {
-    float m[9];
-};
-
-// gemm's 2 <= len <= 4 path, alpha = 1, no C
-__host__ __device__ inline LmM3 lm_mul3(const LmM3& a, const LmM3& b) {
-    LmM3 d;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) d.m[3 * i + j] = a.m[3 * i] * b.m[j] + a.m[3 * i + 1] * b.m[3 + j] + a.m[3 * i + 2] * b.m[6 + j];
-    return d;
-}
-
-// Mat::inv() of a 3 x 3 CV_32F: the closed form in double, zeros when det == 0
-__host__ __device__ inline LmM3 lm_inv3(const LmM3& S) {
-#define SF(y, x) S.m[(y)*3 + (x)]
-#define DD(a, b, c, d) ((double)(a) * (double)(b) - (double)(c) * (double)(d))
-    double d = (double)SF(0, 0) * DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) -
-               (double)SF(0, 1) * DD(SF(1, 0), SF(2, 2), SF(1, 2), SF(2, 0)) +
-               (double)SF(0, 2) * DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0));
-    LmM3 D;
-    if (d != 0.) {
-        d = 1. / d;
-        D.m[0] = (float)(DD(SF(1, 1), SF(2, 2), SF(1, 2), SF(2, 1)) * d);
-        D.m[1] = (float)(DD(SF(0, 2), SF(2, 1), SF(0, 1), SF(2, 2)) * d);
-        D.m[2] = (float)(DD(SF(0, 1), SF(1, 2), SF(0, 2), SF(1, 1)) * d);
-        D.m[3] = (float)(DD(SF(1, 2), SF(2, 0), SF(1, 0), SF(2, 2)) * d);
-        D.m[4] = (float)(DD(SF(0, 0), SF(2, 2), SF(0, 2), SF(2, 0)) * d);
-        D.m[5] = (float)(DD(SF(0, 2), SF(1, 0), SF(0, 0), SF(1, 2)) * d);
-        D.m[6] = (float)(DD(SF(1, 0), SF(2, 1), SF(1, 1), SF(2, 0)) * d);
-        D.m[7] = (float)(DD(SF(0, 1), SF(2, 0), SF(0, 0), SF(2, 1)) * d);
-        D.m[8] = (float)(DD(SF(0, 0), SF(1, 1), SF(0, 1), SF(1, 0)) * d);
-    } else {
-        for (int k = 0; k < 9; ++k) D.m[k] = 0.0f;
-    }
-#undef DD
-#undef SF
-    return D;
-}
+// cv::Mat arithmetic on 3-vectors and 3 x 3 matrices: csrc/orb_cv_math.h
+using orb_cv::dot3;
+using orb_cv::M3;
+using orb_cv::norm3;
 
 // LocalMapping::ComputeF12 (LocalMapping.cc:474-491).  R1w, R2w row-major 3 x 3, K1 / K2: fx fy cx cy.
 __host__ __device__ inline void lm_compute_f12(const float* R1w, const float* t1w, const float* R2w, const float* t2w,
                                                const float* K1, const float* K2, float* F12) {
     // R12 = R1w*R2w.t(): gemm with GEMM_2_T, the general path (one double accumulator, k ascending);
     // -R1w*R2w.t() is the same gemm with alpha = -1, evaluated to a matrix before the next product
-    LmM3 R12, N12;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s0 = 0;
-            for (int k = 0; k < 3; ++k) s0 += (double)R1w[i * 3 + k] * (double)R2w[j * 3 + k];
-            R12.m[i * 3 + j] = (float)(s0 * 1.0);
-            N12.m[i * 3 + j] = (float)(s0 * -1.0);
-        }
+    const M3 R1 = orb_cv::load3x3(R1w), R2 = orb_cv::load3x3(R2w);
+    const M3 R12 = orb_cv::gemm3<false, true>(R1, R2, 1.0), N12 = orb_cv::gemm3<false, true>(R1, R2, -1.0);
     // (..)*t2w+t1w: one gemm(N12, t2w, 1, t1w, 1), the short path
     float t12[3];
-    for (int i = 0; i < 3; ++i) {
-        const float t = N12.m[3 * i] * t2w[0] + N12.m[3 * i + 1] * t2w[1] + N12.m[3 * i + 2] * t2w[2];
-        t12[i] = (float)((double)t * 1.0 + (double)t1w[i] * 1.0);
-    }
-    const LmM3 t12x = {{0.0f, -t12[2], t12[1], t12[2], 0.0f, -t12[0], -t12[1], t12[0], 0.0f}};
-    const LmM3 K1t = {{K1[0], 0.0f, 0.0f, 0.0f, K1[1], 0.0f, K1[2], K1[3], 1.0f}};  // K1.t(), evaluated
-    const LmM3 K2m = {{K2[0], 0.0f, K2[2], 0.0f, K2[1], K2[3], 0.0f, 0.0f, 1.0f}};
-    const LmM3 F = lm_mul3(lm_mul3(lm_mul3(lm_inv3(K1t), t12x), R12), lm_inv3(K2m));
+    orb_cv::gemm3_add(N12.m, t2w, t1w, t12);
+    const M3 t12x = {{0.0f, -t12[2], t12[1], t12[2], 0.0f, -t12[0], -t12[1], t12[0], 0.0f}};
+    const M3 K1t = {{K1[0], 0.0f, 0.0f, 0.0f, K1[1], 0.0f, K1[2], K1[3], 1.0f}};  // K1.t(), evaluated
+    const M3 K2m = {{K2[0], 0.0f, K2[2], 0.0f, K2[1], K2[3], 0.0f, 0.0f, 1.0f}};
+    const M3 F = orb_cv::mul3(orb_cv::mul3(orb_cv::mul3(orb_cv::inv3(K1t), t12x), R12), orb_cv::inv3(K2m));
     for (int k = 0; k < 9; ++k) F12[k] = F.m[k];
 }
 
@@ -125,7 +82,7 @@ struct LmArgs {
     float* F12;                 // P x 9
 };
 
-// GetCameraCenter of keyframe f: the caller's, or -Rcw.t()*tcw as one gemm, GEMM_1_T, alpha = -1
+// GetCameraCenter of keyframe f: the caller's, or -Rcw.t()*tcw
 __device__ __forceinline__ void lm_center(const LmArgs& a, int f, float* O) {
     if (a.ow) {
 #pragma unroll
@@ -133,27 +90,7 @@ __device__ __forceinline__ void lm_center(const LmArgs& a, int f, float* O) {
         return;
     }
     const float* T = a.pose + (size_t)f * 12;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double s0 = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s0 += (double)T[k * 3 + i] * (double)T[9 + k];
-        O[i] = (float)(s0 * -1.0);
-    }
-}
-
-__device__ __forceinline__ double lm_norm3(const float* v) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s += (double)v[k] * (double)v[k];
-    return __builtin_sqrt(s);
-}
-
-__device__ __forceinline__ double lm_dot3(const float* x, const float* y) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s += (double)x[k] * (double)y[k];
-    return s;
+    orb_cv::camera_centre(T, T + 9, O);
 }
 
 __global__ void __launch_bounds__(LM_THREADS) k_lm_median(LmArgs a) {
@@ -169,7 +106,7 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_median(LmArgs a) {
         if (a.has_mp[(size_t)f * a.cap + i]) {
             // z = Rcw2.dot(x3Dw)+zcw: the dot and the sum in double, narrowed once
             const float* X = a.mp_pos + ((size_t)f * a.cap + i) * 3;
-            s_z[atomicAdd(&s_n, 1)] = (float)(lm_dot3(T + 6, X) + (double)T[11]);
+            s_z[atomicAdd(&s_n, 1)] = (float)(dot3(T + 6, X) + (double)T[11]);
         }
     __syncthreads();
     const int nz = s_n;
@@ -200,9 +137,8 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_median(LmArgs a) {
             float O1[3], O2[3], vb[3];
             lm_center(a, a.pair_a[j], O1);
             lm_center(a, f, O2);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) vb[k] = O2[k] - O1[k];
-            const float baseline = (float)lm_norm3(vb);
+            orb_cv::sub3(O2, O1, vb);
+            const float baseline = (float)norm3(vb);
             const float ratioBaselineDepth = baseline / ce;
             a.gate[j] = (double)ratioBaselineDepth < 0.01 ? 1 : 0;
         }
@@ -243,8 +179,8 @@ __device__ __forceinline__ void lm_ray(const LmCam& c, float x, float y, float* 
 // depth the caller has tested already.
 __device__ __forceinline__ bool lm_reproj_fails(const LmCam& c, const float* p3, float z, float kx, float ky,
                                                 float sigmaSquare) {
-    const float x = (float)(lm_dot3(c.R, p3) + (double)c.t[0]);
-    const float y = (float)(lm_dot3(c.R + 3, p3) + (double)c.t[1]);
+    const float x = (float)(dot3(c.R, p3) + (double)c.t[0]);
+    const float y = (float)(dot3(c.R + 3, p3) + (double)c.t[1]);
     const float invz = (float)(1.0 / (double)z);
     const float u = __builtin_fmaf(c.fx * x, invz, c.cx);
     const float v = __builtin_fmaf(c.fy * y, invz, c.cy);
@@ -257,52 +193,41 @@ __device__ __forceinline__ bool lm_reproj_fails(const LmCam& c, const float* p3,
 // One match of LocalMapping.cc:291-391 on the lane's LDS column.  Returns the status code; *cosp is
 // cosParallaxRays, pt the Euclidean point where the match got that far (zeros before).
 __device__ int lm_triangulate_one(const LmArgs& a, const LmCam& c1, const LmCam& c2, const orb_keypoint_t& kp1,
-                                  const orb_keypoint_t& kp2, float ratioFactor, float* At, float* Vt, double* W,
-                                  float* cosp, float* pt) {
+                                  const orb_keypoint_t& kp2, float ratioFactor, const TriColumn& col, float* cosp,
+                                  float* pt) {
     pt[0] = pt[1] = pt[2] = 0.0f;
     float xn1[3], xn2[3], ray1[3], ray2[3];
     lm_ray(c1, kp1.x, kp1.y, xn1, ray1);
     lm_ray(c2, kp2.x, kp2.y, xn2, ray2);
-    const float cosParallaxRays = (float)(lm_dot3(ray1, ray2) / (lm_norm3(ray1) * lm_norm3(ray2)));
+    const float cosParallaxRays = (float)(dot3(ray1, ray2) / (norm3(ray1) * norm3(ray2)));
     *cosp = cosParallaxRays;
     if (cosParallaxRays < 0.0f || (double)cosParallaxRays > 0.9998) return 2;
-    // A.row(r) = xn*Tcw.row(2) - Tcw.row(r & 1): addWeighted_<float, double>(a, xn, b, -1, 0)
+    // A.row(r) = xn*Tcw.row(2) - Tcw.row(r & 1) of the two [Rcw|tcw]
     const float xs[4] = {xn1[0], xn1[1], xn2[0], xn2[1]};
+    float T1[12], T2[12], vr[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const LmCam& c = r < 2 ? c1 : c2;
-            const float t2 = j < 3 ? c.R[6 + j] : c.t[2];
-            const float tr = j < 3 ? c.R[(r & 1) * 3 + j] : c.t[r & 1];
-            At[(j * 4 + r) * 64] = (float)((double)t2 * (double)xs[r] + (double)tr * -1.0 + 0.0);  // the work matrix is the transpose
+            T1[4 * i + j] = j < 3 ? c1.R[3 * i + j] : c1.t[i];
+            T2[4 * i + j] = j < 3 ? c2.R[3 * i + j] : c2.t[i];
         }
-    hy_jacobi<4, 4, 0, true>(At, Vt, W);
-    float vr[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) vr[k] = Vt[(12 + k) * 64];  // vt.row(3)
+    triangulate_vt3(T1, T2, xs, col, vr);
     if (vr[3] == 0.0f) return 3;
     float p3[3];
-    {  // rowRange(0,3)/x3D.at<float>(3): a MatExpr scale, x * (float)alpha + (float)0
-        const float al = (float)(1. / (double)vr[3]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p3[k] = vr[k] * al + 0.0f;
-    }
+    orb_cv::scale3(vr, 1. / (double)vr[3], p3);  // rowRange(0,3)/x3D.at<float>(3): a MatExpr scale
     pt[0] = p3[0], pt[1] = p3[1], pt[2] = p3[2];
-    const float z1 = (float)(lm_dot3(c1.R + 6, p3) + (double)c1.t[2]);
+    const float z1 = (float)(dot3(c1.R + 6, p3) + (double)c1.t[2]);
     if (z1 <= 0.0f) return 4;
-    const float z2 = (float)(lm_dot3(c2.R + 6, p3) + (double)c2.t[2]);
+    const float z2 = (float)(dot3(c2.R + 6, p3) + (double)c2.t[2]);
     if (z2 <= 0.0f) return 5;
     if (lm_reproj_fails(c1, p3, z1, kp1.x, kp1.y, a.s21[min(max(kp1.octave, 0), a.nl1 - 1)])) return 6;
     if (lm_reproj_fails(c2, p3, z2, kp2.x, kp2.y, a.s22[min(max(kp2.octave, 0), a.nl2 - 1)])) return 7;
     float normal1[3], normal2[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        normal1[k] = p3[k] - c1.O[k];
-        normal2[k] = p3[k] - c2.O[k];
-    }
-    const float dist1 = (float)lm_norm3(normal1);
-    const float dist2 = (float)lm_norm3(normal2);
+    orb_cv::sub3(p3, c1.O, normal1);
+    orb_cv::sub3(p3, c2.O, normal2);
+    const float dist1 = (float)norm3(normal1);
+    const float dist2 = (float)norm3(normal2);
     if (dist1 == 0.0f || dist2 == 0.0f) return 8;
     const float ratioDist = dist1 / dist2;
     const float ratioOctave = a.sf1[min(max(kp1.octave, 0), a.nl1 - 1)] / a.sf2[min(max(kp2.octave, 0), a.nl2 - 1)];
@@ -311,7 +236,7 @@ __device__ int lm_triangulate_one(const LmArgs& a, const LmCam& c1, const LmCam&
 }
 
 __global__ void __launch_bounds__(LM_THREADS) k_lm_triangulate(LmArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t smem[(LM_THREADS / 64) * LM_WAVE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[(LM_THREADS / 64) * TRI_WAVE_BYTES];
     __shared__ uint16_t s_ord[LM_MAX_CAP];  // idx1 of every match ordinal
     __shared__ int s_wtot[LM_THREADS / 64];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -360,9 +285,7 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_triangulate(LmArgs a) {
     }
     const LmCam c1 = lm_cam(a, f1, a.K1), c2 = lm_cam(a, f2, a.K2);
     const float ratioFactor = 1.5f * a.sf1[1];  // 1.5f*GetScaleFactor(), the level-1 entry
-    float* At = (float*)(smem + wave * LM_WAVE_BYTES) + lane;
-    float* Vt = At + 16 * 64;
-    double* W = (double*)(smem + wave * LM_WAVE_BYTES + 32 * 64 * 4) + lane;
+    const TriColumn col(smem + wave * TRI_WAVE_BYTES, lane);
     int nnew = 0;
     for (int o0 = 0; o0 < N; o0 += LM_THREADS) {
         const int o = o0 + tid;
@@ -371,7 +294,7 @@ __global__ void __launch_bounds__(LM_THREADS) k_lm_triangulate(LmArgs a) {
             i = s_ord[o];
             m = m12[i];
             float cs, pt[3];
-            st = lm_triangulate_one(a, c1, c2, k1[i], k2[m], ratioFactor, At, Vt, W, &cs, pt);
+            st = lm_triangulate_one(a, c1, c2, k1[i], k2[m], ratioFactor, col, &cs, pt);
             if (a.status) a.status[row + i] = (uint8_t)st;
             if (a.cosr) a.cosr[row + i] = cs;
             if (a.x3d) a.x3d[(row + i) * 3] = pt[0], a.x3d[(row + i) * 3 + 1] = pt[1], a.x3d[(row + i) * 3 + 2] = pt[2];

@@ -19,7 +19,8 @@
 //
 //   k_normal_depth one lane per map point: the unit vectors towards the observing keyframes'
 //                  centres summed in observation order, then the two distance bounds from the
-//                  reference keyframe (IEEE f32 / f64, nothing fuses).
+//                  reference keyframe (IEEE f32 / f64, nothing fuses; the cv::Mat
+//                  arithmetic is csrc/orb_cv_math.h's).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "../../include/orb_abi.h"
+#include "orb_cv_math.h"
 #include "orb_device.h"
 #include "orb_internal.h"
 
@@ -102,13 +104,6 @@ struct NdTables {
     int nlevels, max_obs;
 };
 
-__device__ __forceinline__ double nd_norm3(const float* v) {
-    double s = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s += (double)v[k] * (double)v[k];
-    return __builtin_sqrt(s);
-}
-
 __global__ void __launch_bounds__(64) k_normal_depth(int M, const int32_t* __restrict__ offsets,
                                                      const float* __restrict__ obsOw, const float* __restrict__ pos,
                                                      const float* __restrict__ refOw,
@@ -124,27 +119,22 @@ __global__ void __launch_bounds__(64) k_normal_depth(int M, const int32_t* __res
     const int n = min(max(offsets[m + 1] - r0, 0), t.max_obs);
     for (int r = r0; r < r0 + n; ++r) {
         float normali[3];
+        orb_cv::sub3(P, obsOw + (size_t)r * 3, normali);
+        // normal + normali/norm: one addWeighted(normali, 1./norm, normal, 1, 0)
+        const double alpha = 1. / orb_cv::norm3(normali);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) normali[k] = P[k] - obsOw[(size_t)r * 3 + k];
-        // normal + normali/norm: one addWeighted_<float, double>(normali, 1./norm, normal, 1, 0)
-        const double alpha = 1. / nd_norm3(normali);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) normal[k] = (float)((double)normali[k] * alpha + (double)normal[k] * 1.0 + 0.0);
+        for (int k = 0; k < 3; ++k) normal[k] = orb_cv::add_weighted(normali[k], alpha, normal[k], 1.0);
     }
     float PC[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) PC[k] = P[k] - refOw[(size_t)m * 3 + k];
-    const float dist = (float)nd_norm3(PC);
+    orb_cv::sub3(P, refOw + (size_t)m * 3, PC);
+    const float dist = (float)orb_cv::norm3(PC);
     const int level = min(max(refLevel[m], 0), t.nlevels - 1);
     const float scaleFactor = t.sf[1];  // GetScaleFactor(): the level-1 entry
     const float levelScaleFactor = t.sf[level];
     if (dmin) dmin[m] = (1.0f / scaleFactor) * dist / levelScaleFactor;
     if (dmax) dmax[m] = scaleFactor * dist * t.sf[t.nlevels - 1 - level];
-    if (normalOut) {  // normal/n: a MatExpr scale, x * (float)(1./n) + (float)0; n == 0 gives 0 * inf
-        const float a = (float)(1. / (double)n);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) normalOut[(size_t)m * 3 + k] = normal[k] * a + 0.0f;
-    }
+    // normal/n: a MatExpr scale; n == 0 gives 0 * inf
+    if (normalOut) orb_cv::scale3(normal, 1. / (double)n, normalOut + (size_t)m * 3);
 }
 
 }  // namespace

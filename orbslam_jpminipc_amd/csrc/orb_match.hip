@@ -26,8 +26,8 @@
 //                  Matchers without that dependency (Fuse, SearchBySim3) resolve in parallel.
 //
 // Arithmetic follows the reference bit for bit: cv::Mat algebra (gemm fast path, norm, dot)
-// in the double/float mix OpenCV 2.4 uses, the reference's own float expressions with the
-// FMA contraction g++ -O3 -march=native applies (explicit __builtin_fmaf; see
+// in the double/float mix OpenCV 2.4 uses (csrc/orb_cv_math.h), the reference's own float
+// expressions with the FMA contraction g++ -O3 -march=native applies (explicit __builtin_fmaf; see
 // scripts/contraction_check.sh), IEEE division/sqrt (-fhip-fp32-correctly-rounded-divide-sqrt).
 #include <hip/hip_runtime.h>
 
@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/orb_abi.h"
+#include "orb_cv_math.h"
 #include "orb_device.h"
 #include "orb_internal.h"
 
@@ -155,29 +156,11 @@ struct Job {
 
 __device__ __forceinline__ int qrow(const Job& J, int q) { return is_bow(J.mode) ? J.fv1Feat[q] : q; }
 
-// ---- OpenCV 2.4 cv::Mat algebra on 3-vectors (oracle/ocv_ops.h states the semantics) ----
-__device__ __forceinline__ void gemm3_add(const float* A, const float* x, const float* t, float* o) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float ti = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
-        o[i] = (float)((double)ti * 1.0 + (double)t[i] * 1.0);
-    }
-}
-__device__ __forceinline__ double norm3(const float* v) {
-    double s = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double e = v[i];
-        s += e * e;
-    }
-    return sqrt(s);
-}
-__device__ __forceinline__ double dot3(const float* a, const float* b) {
-    double r = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) r += (double)a[i] * (double)b[i];
-    return r;
-}
+// OpenCV 2.4 cv::Mat algebra on 3-vectors: csrc/orb_cv_math.h (oracle/ocv_ops.h states the semantics)
+using orb_cv::dot3;
+using orb_cv::gemm3_add;
+using orb_cv::norm3;
+using orb_cv::sub3;
 __device__ __forceinline__ int predict_level(const DView& T, float ratio) {  // lower_bound, clamped
     int n = 0;
     while (n < T.nlevels && T.sf[n] < ratio) ++n;
@@ -380,10 +363,7 @@ __global__ void __launch_bounds__(256) k_query_prep(Job J) {
                     p.aMax = oct + 1;
                 } else {
                     float PO[3];
-                    const float* P = J.qpos + 3 * q;
-                    PO[0] = P[0] - T.Ow[0];
-                    PO[1] = P[1] - T.Ow[1];
-                    PO[2] = P[2] - T.Ow[2];
+                    sub3(J.qpos + 3 * q, T.Ow, PO);
                     const float dist3D = (float)norm3(PO);
                     const float ratio = dist3D / J.qdmin[q];
                     const int pred = predict_level(T, ratio);
@@ -405,7 +385,8 @@ __global__ void __launch_bounds__(256) k_query_prep(Job J) {
                 const float x = X[0] * invz, y = X[1] * invz;
                 const float u = __builtin_fmaf(T.fx, x, T.cx), v = __builtin_fmaf(T.fy, y, T.cy);
                 if (!kf_in_image(T, u, v)) break;
-                float PO[3] = {P[0] - T.Ow[0], P[1] - T.Ow[1], P[2] - T.Ow[2]};
+                float PO[3];
+                sub3(P, T.Ow, PO);
                 const float dist3D = (float)norm3(PO);
                 const float minDistance = J.qdmin[q], maxDistance = J.qdmax[q];
                 if (dist3D < minDistance || dist3D > maxDistance) break;
@@ -2209,7 +2190,8 @@ __global__ void __launch_bounds__(256) k_is_in_frustum(DView T, const float* __r
         if (uu < (float)T.minX || uu > (float)T.maxX) break;
         if (vv < (float)T.minY || vv > (float)T.maxY) break;
         const float maxDistance = dmax[i], minDistance = dmin[i];
-        float PO[3] = {P[0] - T.Ow[0], P[1] - T.Ow[1], P[2] - T.Ow[2]};
+        float PO[3];
+        sub3(P, T.Ow, PO);
         const float dist = (float)norm3(PO);
         if (dist < minDistance || dist > maxDistance) break;
         const float vcos = (float)(dot3(PO, normal + 3 * i) / (double)dist);

@@ -21,7 +21,8 @@
 // csrc/orb_optimizer.hip; this unit holds the Sim3 state, its two edges and the schedule.
 //
 // Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
-// prepare step (the batch form's camera-frame points are the float row sums of §12 first).  Sums
+// prepare step (the batch form's camera-frame points are the float row sums of §12 first, gemm3_add of
+// csrc/orb_cv_math.h).  Sums
 // over edges are taken in a fixed order (thread-strided partial sums, e12 before e21 of a pair, an
 // xor butterfly across the wave, the four waves in order): a call gives the same bits on every run.
 // There is no floating-point atomic.
@@ -47,6 +48,7 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_cv_math.h"
 #include "orb_g2o_math.h"
 #include "orb_internal.h"
 
@@ -95,17 +97,6 @@ struct S3Args {
     int cap, S;
 };
 
-// cv::Mat R * X + t as §12 states it: a float row sum left to right, then the add in double
-__device__ __forceinline__ void gemm3_add(const float* T, const float* X, float* out) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float s = T[3 * i] * X[0];
-        s = s + T[3 * i + 1] * X[1];
-        s = s + T[3 * i + 2] * X[2];
-        out[i] = (float)((double)s + (double)T[9 + i]);
-    }
-}
-
 __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
     __shared__ int s_wtot[S3_WAVES];
     const int s = blockIdx.x, tid = threadIdx.x;
@@ -152,8 +143,11 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
                 w1 = a.w1[i], w2 = a.w2[i];
             } else {
                 const size_t k1 = (size_t)fa * cap + i, k2 = (size_t)fb * cap + m;
-                gemm3_add(a.pose + (size_t)fa * 12, a.mp_pos + 3 * k1, X1);
-                gemm3_add(a.pose + (size_t)fb * 12, a.mp_pos + 3 * k2, X2);
+                // cv::Mat Rcw * X + tcw as §12 states it (csrc/orb_cv_math.h)
+                const float* Ta = a.pose + (size_t)fa * 12;
+                const float* Tb = a.pose + (size_t)fb * 12;
+                orb_cv::gemm3_add(Ta, a.mp_pos + 3 * k1, Ta + 9, X1);
+                orb_cv::gemm3_add(Tb, a.mp_pos + 3 * k2, Tb + 9, X2);
                 const orb_keypoint_t& kp1 = a.kps[k1];
                 const orb_keypoint_t& kp2 = a.kps[k2];
                 o1[0] = kp1.x, o1[1] = kp1.y, o2[0] = kp2.x, o2[1] = kp2.y;

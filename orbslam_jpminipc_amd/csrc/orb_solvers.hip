@@ -21,8 +21,9 @@
 //         fx*x + cx                        ->  fmaf(fx, x, cx)
 // Sim3's cv::Mat arithmetic is OpenCV's binary and is not contracted: Rcw*X + tcw is a float row
 // sum taken left to right and then (float)((double)sum + (double)t); a - b is a float subtraction;
-// d.dot(d) is a double accumulation narrowed to float.  Its bound is the reference's
-// std::vector<size_t> entry: (size_t)(9.210 * sigma2), converted to float by the compare.
+// d.dot(d) is a double accumulation narrowed to float (these and computeT's are
+// csrc/orb_cv_math.h's).  Its bound is the reference's std::vector<size_t> entry:
+// (size_t)(9.210 * sigma2), converted to float by the compare.
 // The result of a consensus is an integer count and a bit mask, so nothing here depends on an
 // order of additions.
 //
@@ -60,6 +61,7 @@
 #include <string>
 
 #include "../../include/orb_abi.h"
+#include "orb_cv_math.h"
 #include "orb_epnp_math.h"
 #include "orb_internal.h"
 
@@ -114,18 +116,9 @@ struct ConsArgs {
     int cap, S, n_hyp, W;
 };
 
-// cv::Mat A(3x3) * x + t as OpenCV 2.4's gemm evaluates it: A row-major with `stride` floats per
-// row, t at A-relative `t` with `tstride`.
-__device__ __forceinline__ void gemm3_add(const float* A, int stride, const float* t, int tstride, float x0, float x1,
-                                          float x2, float* out) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float s = A[i * stride] * x0;
-        s = s + A[i * stride + 1] * x1;
-        s = s + A[i * stride + 2] * x2;
-        out[i] = (float)((double)s + (double)t[i * tstride]);
-    }
-}
+// cv::Mat arithmetic on 3-vectors and 3 x 3 matrices: csrc/orb_cv_math.h
+using orb_cv::gemm3_add;
+using orb_cv::gemm_out;
 
 // Project / FromCameraToImage (Sim3Solver.cc:392-396, 412-416)
 __device__ __forceinline__ void to_image(float X, float Y, float Z, const float* K, float* u, float* v) {
@@ -393,20 +386,6 @@ __device__ __forceinline__ float jac_get(const Jac4& J, int r, int c) {
     return __uint_as_float(jac_pick(p, 0, J.U[0]) | jac_pick(p, 1, J.U[1]) | jac_pick(p, 2, J.U[2]) |
                            jac_pick(p, 3, J.U[3]) | jac_pick(p, 4, J.U[4]) | jac_pick(p, 5, J.U[5]));
 }
-// lapack.cpp's own hypot
-__device__ __forceinline__ float jac_hypot(float a, float b) {
-    a = fabsf(a);
-    b = fabsf(b);
-    if (a > b) {
-        b /= a;
-        return a * sqrtf(1 + b * b);
-    }
-    if (b > 0) {
-        a /= b;
-        return b * sqrtf(1 + a * a);
-    }
-    return 0;
-}
 // indR[IDX] = the first largest |A[IDX][i]|, i > IDX; indC[IDX] = the first largest |A[i][IDX]|, i < IDX.
 // The loops of JacobiImpl_ are written out through templates so that every index is a constant
 // before the first scalar-replacement pass: a loop-indexed J.U[] would keep J in scratch memory.
@@ -457,8 +436,8 @@ __device__ __forceinline__ void jac_rot_at(Jac4& J, float c, float s) {
 template <int K, int L>
 __device__ __forceinline__ void jac_rotate(Jac4& J, float p) {
     const float y = (float)((double)(J.W[L] - J.W[K]) * 0.5);
-    float t = fabsf(y) + jac_hypot(p, y);
-    float s = jac_hypot(p, t);
+    float t = fabsf(y) + orb_cv::cv_hypot(p, y);  // lapack.cpp's own hypot, in float
+    float s = orb_cv::cv_hypot(p, t);
     const float c = t / s;
     s = p / s;
     t = (p / t) * p;
@@ -537,14 +516,6 @@ __device__ __forceinline__ void jac_eigen_row0(Jac4& J, float* q) {
     q[3] = sel4(m, J.V[3], J.V[7], J.V[11], J.V[15]);
 }
 
-// m = alpha * m assigned (convertTo -> cvtScale_<float, float, float>): scale and shift as floats
-__device__ __forceinline__ float cvt_scale(float v, double alpha) {
-    const float scale = (float)alpha, shift = (float)0.0;
-    return v * scale + shift;
-}
-__device__ __forceinline__ float gemm_out(float t, double alpha, float c, double beta) {
-    return (float)((double)t * alpha + (double)c * beta);
-}
 // Sim3Solver::centroid of a 3x3 (row-major, a correspondence per column)
 __device__ __forceinline__ void centroid3(const float* P, float* Pr, float* C) {
 #pragma unroll
@@ -552,7 +523,7 @@ __device__ __forceinline__ void centroid3(const float* P, float* Pr, float* C) {
         float a0 = P[3 * r], a1 = P[3 * r + 1];  // cv::reduce: (s0 + s2) + s1
         a0 = a0 + P[3 * r + 2];
         a0 = a0 + a1;
-        C[r] = cvt_scale(a0, 1. / (double)3);
+        C[r] = orb_cv::scale(a0, 1. / (double)3);
     }
 #pragma unroll
     for (int k = 0; k < 9; ++k) Pr[k] = P[k] - C[k / 3];
@@ -594,17 +565,8 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
         centroid3(P1, Pr1, O1);
         centroid3(P2, Pr2, O2);
         // M = Pr2*Pr1.t() (GEMM_2_T: GEMMSingleMul<float, double>)
-        float M[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s0 = 0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) s0 += (double)Pr2[3 * i + k] * (double)Pr1[3 * j + k];
-                s0 = (((s0 + 0.0) + 0.0) + 0.0) * 1.0;
-                M[3 * i + j] = (float)s0;
-            }
+        const orb_cv::M3 Mm = orb_cv::gemm3<false, true>(orb_cv::load3x3(Pr2), orb_cv::load3x3(Pr1), 1.0);
+        const float* M = Mm.m;
         Jac4 J;
         J.W[0] = M[0] + M[4] + M[8];    // N11
         J.U[0] = M[5] - M[7];           // N12
@@ -618,14 +580,9 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
         J.W[3] = -M[0] - M[4] + M[8];   // N44
         jac_eigen_row0(J, q);
         float vec[3] = {q[1], q[2], q[3]};
-        double nrm = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) nrm += (double)vec[k] * (double)vec[k];
-        nrm = sqrt(nrm);
+        const double nrm = orb_cv::norm3(vec);
         const double ang = atan2(nrm, (double)q[0]);
-        const double alpha = (2 * ang) * (1. / nrm);  // 2*ang*vec/norm(vec)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) vec[k] = cvt_scale(vec[k], alpha);
+        orb_cv::scale3(vec, (2 * ang) * (1. / nrm), vec);  // 2*ang*vec/norm(vec)
         {  // cvRodrigues2
             double rx = vec[0], ry = vec[1], rz = vec[2];
             const double theta = sqrt(rx * rx + ry * ry + rz * rz);
@@ -660,19 +617,15 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(ConsArgs a, HypArgs y) {
         for (int k = 0; k < 9; ++k) den += (double)(P3[k] * P3[k]);
         ms12i = (float)(nom / den);
         // mt12i = O1 - ms12i*mR12i*O2: one gemm, alpha = -ms12i, C = O1, beta = 1
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float t = R[3 * i] * O2[0] + R[3 * i + 1] * O2[1] + R[3 * i + 2] * O2[2];
-            t12[i] = gemm_out(t, -(double)ms12i, O1[i], 1.0);
-        }
+        gemm3_add(R, 3, O1, 1, O2[0], O2[1], O2[2], t12, -(double)ms12i, 1.0);
         // sR = ms12i*mR12i; sRinv = (1.0/ms12i)*mR12i.t(); tinv = -sRinv*mt12i
         const double inv_s = 1.0 / (double)ms12i;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                T12[4 * i + j] = cvt_scale(R[3 * i + j], (double)ms12i);
-                T21[4 * i + j] = cvt_scale(R[3 * j + i], inv_s);
+                T12[4 * i + j] = orb_cv::scale(R[3 * i + j], (double)ms12i);
+                T21[4 * i + j] = orb_cv::scale(R[3 * j + i], inv_s);
             }
             T12[4 * i + 3] = t12[i];
         }
