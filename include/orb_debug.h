@@ -5,7 +5,8 @@
  * ordinary frames rarely reach (k_fast's plane-scan fallback, the per-level pyramid kernels) and
  * check the libstdc++ nth_element replays in isolation.  None of them changes a result.  The
  * per-phase timing probes of the kernels (orb_debug_{ps,km,kr,ks,kf}_timing) exist only in
- * experiment builds (-DPS_TIMING=1 etc.), never in the product library.
+ * experiment builds (-DPS_TIMING=1 etc.), never in the product library; each is defined in its
+ * kernel's unit (ps, kf: csrc/orb_ilp.hip; kr, ks: csrc/orb_hip.hip; km: csrc/orb_sfi.hip).
  */
 #ifndef ORB_DEBUG_H
 #define ORB_DEBUG_H

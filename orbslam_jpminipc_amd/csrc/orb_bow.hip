@@ -53,9 +53,6 @@ __device__ __forceinline__ uint32_t rmin16(uint32_t v) {
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x128, 0xF, 0xF, false));
     return v;
 }
-#ifndef BOW_BATCH4
-#define BOW_BATCH4 1  // nodes of <= 16 candidates: four queries per step (speculated, exact); 0: one per step
-#endif
 
 __device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:230-236 / 799-805
     float rot = a1 - a2;
@@ -179,7 +176,7 @@ __global__ void __launch_bounds__(BOW_T) k_bow_pairs(BowBatch J) {
         if (b < 0) continue;
         const int q0 = OA[a], q1 = OA[a + 1], c0 = OB[b], nc = OB[b + 1] - c0;
         if (nc <= 0) continue;
-        if (BOW_BATCH4 && nc <= 16) {
+        if (nc <= 16) {
             // Four queries per step, lane 16g + c: query g of the step against candidate c (each
             // of the four 16-lane rows holds the node's candidates and their matched flags).  A
             // query's outcome is fixed by its best and second unmatched candidates and an

@@ -1029,15 +1029,6 @@ __global__ void __launch_bounds__(256) k_resolve(Job J) {
 // The loop is bounded by qn + 2 iterations (the induction's bound + the one that sees no
 // change); past it the kernel reports -1 matches and the call fails (cannot happen).
 #define RF_THREADS 1024
-#ifndef RF_DEBUG
-#define RF_DEBUG 0  // 1: iterations / rescans per call printed (experiment builds)
-#endif
-#ifndef RF_LONG_LISTS
-#define RF_LONG_LISTS 1  // 32-entry lists for the fixed-point resolver except SearchByProjection(local)
-#endif
-#ifndef RF_ALL_MODES
-#define RF_ALL_MODES 1  // 0: the fixed point for SearchByProjection(local) only
-#endif
 size_t resolve_fix_lds(const Job& J) { return (size_t)2 * std::max(J.T.n, 1) * 4 + (size_t)std::max(J.qn, 1) * 4 + 16; }
 template <int MODE>
 __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
@@ -1056,13 +1047,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
     for (int t = tid; t < Tn; t += RF_THREADS) s_tb[t] = J.taken0 && J.taken0[t] ? -1 : INT_MAX;
     constexpr int need = needs_second(MODE) ? 2 : 1;
     bool done = false;
-#if RF_DEBUG
-    int dbgIt = 0, dbgRes = 0;
-#endif
     for (int it = 0; it < J.qn + 2 && !done; ++it) {
-#if RF_DEBUG
-        ++dbgIt;
-#endif
         for (int t = tid; t < Tn; t += RF_THREADS) s_tn[t] = J.taken0 && J.taken0[t] ? -1 : INT_MAX;
         if (tid == 0) {
             s_nres = 0;
@@ -1101,9 +1086,6 @@ __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
                 atomicMin(&s_tn[x1 & 0xFFFFFFu], q);
         }
         __syncthreads();
-#if RF_DEBUG
-        dbgRes += s_nres;
-#endif
         for (int r = wave; r < s_nres; r += RF_THREADS / 64) {  // exact rescans, a wave each
             const int q = s_res[r];
             uint32_t b1, b2;
@@ -1189,10 +1171,6 @@ __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
     __syncthreads();
     if (tid == 0) {
         J.nOut[0] = done ? s_nacc : -1;
-#if RF_DEBUG
-        printf("k_resolve_fix mode %d qn %d Tn %d: %d iterations, %d rescans, %d accepted\n", MODE, J.qn, Tn, dbgIt,
-               dbgRes, s_nacc);
-#endif
     }
 }
 
@@ -1547,15 +1525,14 @@ int run_job(const Call& C, const Job& J0) {
     // the projection-family matchers: the fixed-point resolver where its state fits (it also
     // takes targets k_resolve's per-target LDS state cannot: 8 B per target instead of 13), fed
     // TOPK_FIX-entry candidate lists
-    const bool fixMode = J0.outByTarget && (J0.mode == M_LOCAL || (RF_ALL_MODES && (J0.mode == M_WINDOW || J0.mode == M_F2F ||
-                                                                                     J0.mode == M_MOTION || J0.mode == M_RELOC ||
-                                                                                     J0.mode == M_SIM3P)));
+    const bool fixMode = J0.outByTarget && (J0.mode == M_LOCAL || J0.mode == M_WINDOW || J0.mode == M_F2F ||
+                                            J0.mode == M_MOTION || J0.mode == M_RELOC || J0.mode == M_SIM3P);
     const bool useFix = fixMode && resolve_fix_lds(J0) <= 150 * 1024;
     Job J = J0;
     // (32 entries: no exact rescan left in the motion-model projection / WindowSearch of the
     // latency probe, 173 / 301 per call with 8; the local-map search has none with 8 and pays
     // ~4 us for the longer merge)
-    J.topS = useFix && RF_LONG_LISTS && J0.mode != M_LOCAL ? TOPK_FIX : TOPK;
+    J.topS = useFix && J0.mode != M_LOCAL ? TOPK_FIX : TOPK;
     if (J.qn > 0) {
         hipLaunchKernelGGL(k_query_prep, dim3((J.qn + 255) / 256), dim3(256), 0, s, J);
         if (J.topS == TOPK_FIX)

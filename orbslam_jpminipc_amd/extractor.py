@@ -10,7 +10,7 @@ arguments and defaults, same ``operator()`` semantics (``__call__`` here):
   N == 0 (``_descriptors.release()``, ORBextractor.cc:738-739);
 * the mask argument is accepted and ignored, as the reference's FAST ignores it.
 
-All arithmetic runs in the HIP kernels of csrc/orb_hip.hip; this module only marshals.
+All arithmetic runs in the HIP kernels of csrc/orb_hip.hip and csrc/orb_ilp.hip; this module only marshals.
 """
 from __future__ import annotations
 

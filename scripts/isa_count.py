@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Static instruction counts per kernel of a HIP source (device assembly for gfx950).
 
-Usage: isa_count.py [SRC] [-DFLAG=V ...] [KERNEL_SUBSTR ...]   (default SRC: csrc/orb_hip.hip, all kernels;
+Usage: isa_count.py [SRC] [-DFLAG=V ...] [KERNEL_SUBSTR ...]   (default SRC: csrc/orb_hip.hip, all kernels; k_fast and
+k_pyr_stream are in csrc/orb_ilp.hip -- ISA_EXTRA="-mllvm -amdgpu-sched-strategy=max-ilp" gives that unit's
+schedule -- and k_match_init in csrc/orb_sfi.hip;
 extra compiler options, e.g. -mllvm ones, in $ISA_EXTRA)
 Prints per kernel: VALU / SALU / LDS / VMEM / SMEM / MFMA counts, VGPRs, SGPRs, LDS bytes and
 the occupancy the compiler reports.  Static counts (each instruction once, loops not unrolled at

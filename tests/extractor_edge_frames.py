@@ -38,7 +38,7 @@ BG = 100
 EDGE = 16
 SCALE, NLEVELS = 1.2, 4
 TAPS = np.array([18, 34, 49, 55, 49, 34, 18], np.int64)
-K_FAST_TILE = 256  # detection columns per k_fast tile at level 0 (csrc/orb_hip.hip)
+K_FAST_TILE = 256  # detection columns per k_fast tile at level 0 (FT_TW_MAX, csrc/orb_extract.h)
 
 
 @dataclass

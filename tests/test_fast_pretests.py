@@ -1,5 +1,5 @@
-"""CPU proofs of the FAST pre-tests the kernels use before the exact strength (orb_hip.hip
-compass_half / compass8_half; reference cv::FAST behind ORBextractor.cc:607 and 613).
+"""CPU proofs of the FAST pre-tests the kernels use before the exact strength (compass_half in orb_extract.h,
+compass8_half in orb_hip.hip; reference cv::FAST behind ORBextractor.cc:607 and 613).
 
 * compass_half: per 16-bit lane, M = min(max(q0, q8), max(q4, q12)), m = max(min(q0, q8),
   min(q4, q12)); the pixel passes <=> t - max(M - v, v - m) < 0.  Restated here on i16 lanes
@@ -10,7 +10,7 @@ compass_half / compass8_half; reference cv::FAST behind ORBextractor.cc:607 and 
 """
 import numpy as np
 
-# circle offsets (dy, dx) in cv::FAST order, index 0 = (3, 0) (orb_hip.hip fast_strength_packed)
+# circle offsets (dy, dx) in cv::FAST order, index 0 = (3, 0) (orb_extract.h fast_strength_packed)
 CIRCLE = [(3, 0), (3, 1), (2, 2), (1, 3), (0, 3), (-1, 3), (-2, 2), (-3, 1),
           (-3, 0), (-3, -1), (-2, -2), (-1, -3), (0, -3), (1, -3), (2, -2), (3, -1)]
 

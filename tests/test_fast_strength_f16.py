@@ -1,4 +1,4 @@
-"""The FAST strength arithmetic of `fast_strength_packed` (orb_hip.hip): contrasts as exact f16
+"""The FAST strength arithmetic of `fast_strength_packed` (orb_extract.h): contrasts as exact f16
 denormals (a byte b loaded into a register is the binary16 bit pattern b = b * 2^-24), arcs of
 9 as three windows of 3 (the kernel's v_pk_minimum3_f16), the best arc by maximum, and the
 result read back as the int16 view of its bits.  Emulated here in numpy float16 (IEEE

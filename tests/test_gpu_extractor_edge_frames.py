@@ -105,8 +105,7 @@ def test_host_call_parity(name, score):
 @pytest.mark.parametrize("nf,th", GROUPS)
 def test_device_batch_parity(nf, th, B):
     """All frames in one device batch, repeated to fill it.  8, 64 and 256 frames: at and above
-    KR_SHORT_BATCH, below and above KS_SEP_BATCH (FAST(7) re-runs in k_rerun or in k_select) and
-    k_rerun's workgroup-count switch, and KR_STREAM_BATCH, where k_pyr_stream builds the pyramid."""
+    KR_SHORT_BATCH, below and above k_rerun's workgroup-count switch, and KR_STREAM_BATCH, where k_pyr_stream builds the pyramid."""
     import torch
 
     own = [n for n in NAMES if (E.frame(n).nf, E.frame(n).th) == (nf, th)]

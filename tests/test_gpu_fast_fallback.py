@@ -1,5 +1,5 @@
 """k_fast's whole-plane NMS fallback (taken when a wave finds more corners than its corner list
-holds, 256 by default; csrc/orb_hip.hip k_fast) is bit-exact with the oracle: the list capacity
+holds, 256 by default; csrc/orb_ilp.hip k_fast) is bit-exact with the oracle: the list capacity
 is lowered through orb_debug_set_fast_corner_list so that the fallback runs in every workgroup
 with a corner (cap 0) or in most of them (cap 8), on scene, low-texture and noise frames, and
 through the batched device path as well as the host entry point."""

@@ -3,7 +3,7 @@ deep as the query list, pairs exactly on every acceptance threshold, and the siz
 host BoW path.  Every result is compared element for element with the CPU oracle and with the
 expectation known by construction (count and mapping), so no test passes on two empty results.
 
-Which resolver a test reaches (csrc/orb_match.hip, csrc/orb_hip.hip):
+Which resolver a test reaches (csrc/orb_match.hip, csrc/orb_sfi.hip):
   test_fix_*            k_resolve_fix, chains of more than one and more than two 1024-thread
                         strides with short candidate lists, 200 links with truncated lists
   test_resolve_*        k_resolve: BoW on the generic path, SearchForTriangulation, and the grid

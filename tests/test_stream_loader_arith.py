@@ -1,4 +1,4 @@
-"""CPU check of k_pyr_stream's unaligned level-0 loads (load_unit16, orb_hip.hip).
+"""CPU check of k_pyr_stream's unaligned level-0 loads (load_unit16, orb_ilp.hip).
 
 A unit of 16 bytes at byte address p with nvalid valid bytes is rebuilt from the one or two
 16-B-aligned blocks holding it: dwords w[d .. d+4] of the 32-B pair (d = (p & 15) >> 2), four
