@@ -86,6 +86,16 @@ __device__ __forceinline__ void glibc_sincosf(float y, float* s_out, float* c_ou
     *c_out = (n & 1) ? S : C;
 }
 
+// (int) of a float the way the reference's x86 build converts it (cvttss2si): NaN and every value
+// outside int's range give INT_MIN.  C++ leaves these conversions undefined, and the GPU's own
+// conversion gives 0 for NaN and saturates, which would file a NaN keypoint in cell 0, send a NaN
+// box edge to cell 0 and an infinite one to the last cell (FP policy).  The one text
+// for the grid code of orb_match.hip and orb_sfi.hip.  One compare: |v| < 2^31 is false for NaN,
+// and the one in-range value it turns away, -2^31 itself, converts to INT_MIN anyway.
+__device__ __forceinline__ int cvt_x86(float v) {
+    return fabsf(v) < 2147483648.0f ? (int)v : (-2147483647 - 1);
+}
+
 // Minimum over each aligned group of 8 lanes (DPP: quad_perm xor 1, xor 2, row_half_mirror).
 __device__ __forceinline__ uint32_t min8(uint32_t v) {
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));

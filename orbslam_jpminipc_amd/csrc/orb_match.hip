@@ -169,13 +169,7 @@ __device__ __forceinline__ int predict_level(const DView& T, float ratio) {  // 
 __device__ __forceinline__ bool kf_in_image(const DView& T, float x, float y) {  // KeyFrame.cc:654-657
     return x >= (float)T.minX && x < (float)T.maxX && y >= (float)T.minY && y < (float)T.maxY;
 }
-// (int) of a float the way the reference's x86 build converts it (cvttss2si): NaN and every value
-// outside int's range give INT_MIN.  C++ leaves these conversions undefined, and the GPU's own
-// conversion gives 0 for NaN and saturates, which would file a NaN keypoint in cell 0, send a NaN
-// box edge to cell 0 and an infinite one to the last cell (FP policy).
-__device__ __forceinline__ int cvt_x86(float v) {
-    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MIN;
-}
+using orbdev::cvt_x86;  // (int) of a float as the reference's x86 build converts it (orb_device.h)
 struct CellRange {
     int minCX, maxCX, minCY, maxCY;
 };

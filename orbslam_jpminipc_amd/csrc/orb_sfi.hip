@@ -181,8 +181,8 @@ __device__ __forceinline__ bool match_pair(const MatchArgs& A, int p, int nmax, 
     // s_m12[i1] = 1 if F1 keypoint i1 is a query (octave 0), as scratch.
     for (int i = tid; i < n2; i += NT) {
         const orb_keypoint_t kp = K2[i];
-        const int px = (int)roundf((kp.x - mg.minX) * mg.invW);
-        const int py = (int)roundf((kp.y - mg.minY) * mg.invH);
+        const int px = cvt_x86(roundf((kp.x - mg.minX) * mg.invW));
+        const int py = cvt_x86(roundf((kp.y - mg.minY) * mg.invH));
         const bool ok = kp.octave == 0 && !(px < 0 || px >= 64 || py < 0 || py >= 48);
         s_key[i] = ok ? (((uint32_t)(px * 48 + py) << 16) | (uint32_t)i) : 0xFFFFFFFFu;
     }
@@ -358,10 +358,10 @@ __device__ __forceinline__ bool match_pair(const MatchArgs& A, int p, int nmax, 
         if (act) {
             qx = s_qx[q];
             qy = s_qy[q];
-            minCX = max(0, (int)floorf((qx - mg.minX - r) * mg.invW));
-            maxCX = min(63, (int)ceilf((qx - mg.minX + r) * mg.invW));
-            minCY = max(0, (int)floorf((qy - mg.minY - r) * mg.invH));
-            maxCY = min(47, (int)ceilf((qy - mg.minY + r) * mg.invH));
+            minCX = max(0, cvt_x86(floorf((qx - mg.minX - r) * mg.invW)));
+            maxCX = min(63, cvt_x86(ceilf((qx - mg.minX + r) * mg.invW)));
+            minCY = max(0, cvt_x86(floorf((qy - mg.minY - r) * mg.invH)));
+            maxCY = min(47, cvt_x86(ceilf((qy - mg.minY + r) * mg.invH)));
             if (early && q0 == 0) {
 #pragma unroll
                 for (int w = 0; w < 8; ++w) d1[w] = d1pre[w];
@@ -452,10 +452,10 @@ __device__ __forceinline__ bool match_pair(const MatchArgs& A, int p, int nmax, 
     auto rescan_best = [&](const int q0, auto&& live, uint32_t& gbOut, int& contribOut) {
         const int i1 = s_q2i[q0];
         const float qx = s_qx[q0], qy = s_qy[q0];
-        const int minCX = max(0, (int)floorf((qx - mg.minX - r) * mg.invW));
-        const int maxCX = min(63, (int)ceilf((qx - mg.minX + r) * mg.invW));
-        const int minCY = max(0, (int)floorf((qy - mg.minY - r) * mg.invH));
-        const int maxCY = min(47, (int)ceilf((qy - mg.minY + r) * mg.invH));
+        const int minCX = max(0, cvt_x86(floorf((qx - mg.minX - r) * mg.invW)));
+        const int maxCX = min(63, cvt_x86(ceilf((qx - mg.minX + r) * mg.invW)));
+        const int minCY = max(0, cvt_x86(floorf((qy - mg.minY - r) * mg.invH)));
+        const int maxCY = min(47, cvt_x86(ceilf((qy - mg.minY + r) * mg.invH)));
         uint32_t d1[8];
 #pragma unroll
         for (int w = 0; w < 2; ++w) {  // two 16-B loads (descriptor rows are 32-B aligned)

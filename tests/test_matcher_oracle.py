@@ -20,33 +20,50 @@ def hamming(a, b):
     return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
 
 
+def cvt_x86(v):
+    """(int) of a float as the reference's x86 build converts it (cvttss2si): NaN and every value
+    outside int's range give INT_MIN (FP policy)."""
+    v = np.float64(v)
+    return int(v) if -2147483648.0 <= v < 2147483648.0 else -(2**31)
+
+
+def c_round(v):
+    """std::round of a float: half away from zero."""
+    v = np.float64(v)
+    return np.copysign(np.floor(np.abs(v) + 0.5), v)
+
+
 class PyFrame:
-    def __init__(self, kps, desc, W, H):
+    def __init__(self, kps, desc, W, H, bounds=None):
         self.k, self.d = kps, desc
-        self.minX, self.maxX, self.minY, self.maxY = 0, W, 0, H
-        self.invW = F32(64) / F32(W)
-        self.invH = F32(48) / F32(H)
+        self.minX, self.maxX, self.minY, self.maxY = bounds or (0, W, 0, H)
+        self.invW = F32(64) / F32(self.maxX - self.minX)
+        self.invH = F32(48) / F32(self.maxY - self.minY)
         self.grid = {}
-        for i, kp in enumerate(kps):
-            # std::round (half away from zero) of a non-negative float32 product
-            px = int(np.floor(np.float64(F32(kp["x"] - F32(self.minX)) * self.invW) + 0.5))
-            py = int(np.floor(np.float64(F32(kp["y"] - F32(self.minY)) * self.invH) + 0.5))
-            if 0 <= px < 64 and 0 <= py < 48:
-                self.grid.setdefault((px, py), []).append(i)
+        with np.errstate(all="ignore"):
+            for i, kp in enumerate(kps):
+                px = cvt_x86(c_round(F32(kp["x"] - F32(self.minX)) * self.invW))
+                py = cvt_x86(c_round(F32(kp["y"] - F32(self.minY)) * self.invH))
+                if 0 <= px < 64 and 0 <= py < 48:
+                    self.grid.setdefault((px, py), []).append(i)
 
     def area(self, x, y, r, minL, maxL):
         x, y, r = F32(x), F32(y), F32(r)
         out = []
-        nminx = max(0, int(np.floor(F32(F32(x - F32(self.minX)) - r) * self.invW)))
+        with np.errstate(all="ignore"):
+            return self._area(x, y, r, minL, maxL, out)
+
+    def _area(self, x, y, r, minL, maxL, out):
+        nminx = max(0, cvt_x86(np.floor(F32(F32(x - F32(self.minX)) - r) * self.invW)))
         if nminx >= 64:
             return out
-        nmaxx = min(63, int(np.ceil(F32(F32(x - F32(self.minX)) + r) * self.invW)))
+        nmaxx = min(63, cvt_x86(np.ceil(F32(F32(x - F32(self.minX)) + r) * self.invW)))
         if nmaxx < 0:
             return out
-        nminy = max(0, int(np.floor(F32(F32(y - F32(self.minY)) - r) * self.invH)))
+        nminy = max(0, cvt_x86(np.floor(F32(F32(y - F32(self.minY)) - r) * self.invH)))
         if nminy >= 48:
             return out
-        nmaxy = min(47, int(np.ceil(F32(F32(y - F32(self.minY)) + r) * self.invH)))
+        nmaxy = min(47, cvt_x86(np.ceil(F32(F32(y - F32(self.minY)) + r) * self.invH)))
         if nmaxy < 0:
             return out
         check = not (minL == -1 and maxL == -1)
