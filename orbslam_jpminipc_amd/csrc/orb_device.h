@@ -8,20 +8,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orb_extract_geom.h"
+
 namespace orbdev {
 
-constexpr int EDGE = 16;           // EDGE_THRESHOLD, ORBextractor.cc:77
+// EDGE (EDGE_THRESHOLD) and reflect101 (BORDER_REFLECT_101): orb_extract_geom.h, shared with the host planner
 constexpr int HALF_PATCH = 15;     // HALF_PATCH_SIZE, ORBextractor.cc:76
-
-// cv::borderInterpolate(p, len, BORDER_REFLECT_101) (OpenCV 2.4).
-__host__ __device__ __forceinline__ int reflect101(int p, int len) {
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        p = p < 0 ? -p : 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
 
 // cv::fastAtan2 (OpenCV 2.4 mathfuncs.cpp): float, no contraction.
 __device__ __forceinline__ float fast_atan2(float y, float x) {

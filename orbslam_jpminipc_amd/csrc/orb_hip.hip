@@ -16,7 +16,9 @@
 // k_fast and k_pyr_stream (the whole pyramid of a frame in one pass, large batches) live in
 // orb_ilp.hip, which is compiled under its own scheduler flags, and are launched through its
 // orb_ilp_* functions; orb_extract.h holds what the two units share.  SearchForInitialization
-// (k_match_init) is orb_sfi.hip.
+// (k_match_init) is orb_sfi.hip.  What a frame size decides (level and cell geometry, resize
+// tables, k_fast's tiles, k_pyr_stream's schedule, every refusal) is the HIP-free planner
+// orb_extract_plan.h; the handle below allocates and uploads from its plan.
 //
 // Reference behaviour that lives in OpenCV 2.4 / libstdc++ / glibc is restated per
 // SURVEY.md Appendix A; DESIGN.md lists every arithmetic rule and where it is pinned.
@@ -38,6 +40,7 @@
 #include "orb_internal.h"
 #include "orb_device.h"
 #include "orb_extract.h"
+#include "orb_extract_plan.h"
 #include "pattern31.inc"
 
 #ifndef KR_TIMING  // 1: per-level, per-phase s_memrealtime sums of k_rerun's cell re-runs (experiments)
@@ -210,14 +213,8 @@ __device__ __forceinline__ void stage_tile16(uint4* __restrict__ dst, const uint
 // Every coefficient is in [0, 2050] with a0 + a1, b0 + b1 <= 2050 (checked on the host), so
 // no intermediate of the reference's saturating chain can saturate: H <= 255 * 2050 = 522750,
 // (H >> 4) * b < 2^27, the SSE2 sum <= 1023 and the scalar sum < 2^31; both end in [0, 255].
-// The SSE2 path's (h * b) >> 16 is then mulhi(h, b << 16).
-#define RZ_TW 256  // 64 lanes x 4 columns
-#ifndef RZ_TH
-#define RZ_TH 32
-#endif
-#ifndef RZ_THS
-#define RZ_THS 4  // tile rows for batches below KR_SHORT_BATCH (B=1 640x480: 0.074 -> 0.035 ms for levels 1-7)
-#endif
+// The SSE2 path's (h * b) >> 16 is then mulhi(h, b << 16).  (RZ_TW, RZ_TH, RZ_THS: orb_extract_plan.h,
+// whose planner builds the tile tables.)
 #ifndef KR_SHORT_BATCH
 #define KR_SHORT_BATCH 8
 #endif
@@ -350,8 +347,7 @@ __global__ void __launch_bounds__(256) k_pyr_resize(uint8_t* __restrict__ pyr, c
 // are staged in LDS too.  Per padded pixel the arithmetic is k_pyr_resize's: HResizeLinear
 // taps (tail columns S[sx] * 2048), then the SSE2 vertical body (((H >> 4) * b) >> 16 summed,
 // + 2 >> 2) on columns lx < xs, the scalar FixedPtCast (+ 2^21 >> 22) on the others.
-#define RT_THREADS 1024
-#define RT_LDS_MAX (150 * 1024)
+#define RT_THREADS 1024  // (its LDS bound RT_LDS_MAX: orb_extract_plan.h)
 __global__ void __launch_bounds__(RT_THREADS) k_pyr_resize_tail(uint8_t* __restrict__ pyr,
                                                                 const int* __restrict__ rtab, Geom g, int lf,
                                                                 int bufA, int bufB) {
@@ -443,12 +439,10 @@ __global__ void __launch_bounds__(RT_THREADS) k_pyr_resize_tail(uint8_t* __restr
     }
 }
 
-// k_pyr_stream (orb_ilp.hip): when the host uses it, and the LDS its plan aims for
+// k_pyr_stream (orb_ilp.hip): when the host uses it (the LDS its plan aims for, PS_LDS_TARGET:
+// orb_extract_plan.h)
 #ifndef KR_STREAM_BATCH  // smallest batch that uses k_pyr_stream (one workgroup per frame)
 #define KR_STREAM_BATCH 256
-#endif
-#ifndef PS_LDS_TARGET
-#define PS_LDS_TARGET (76 * 1024)  // two workgroups per CU
 #endif
 
 // cv::FAST's full pre-test (all eight even circle points): a 9-arc holds a point of every
@@ -497,17 +491,11 @@ __device__ __forceinline__ uint32_t compass8(uint32_t lf, uint32_t cc, uint32_t 
 // words) | rowc | In (the ROI staged from its 16-B aligned start with 16-B loads: the dword
 // staging before needed 128 VGPRs for its 20 loads in flight per thread, 4 waves per SIMD; 16-B
 // units need 50: re-runs 0.174 -> 0.123 ms per 512 KITTI frames, 2.61 -> 2.02 per 4096 720p),
-// rerun_lds() bytes.  Output: each survivor sets its bit in its row's mask
+// rerun_lds() bytes (orb_extract_plan.h, with RR_Q).  Output: each survivor sets its bit in its row's mask
 // and counts into its row; after the row prefix one thread per mask word writes that word's
 // survivors at the row's offset + the set bits of the row's earlier words (no per-row scan of
 // the cell, no list, no returning atomics in the NMS).
-#define RR_Q 320  // per-wave queue of compass survivors (< 64 carried + 4 x 64 new), + a trash slot
-inline size_t rerun_lds(int dw, int dh) {
-    const size_t dwp = (size_t)((dw + 3) & ~3);
-    const size_t inW = (size_t)((15 + dw + 6 + 15) & ~15), spBytes = (dwp * dh + 15) & ~(size_t)15;
-    const size_t bmBytes = 4 * (size_t)((dh * ((dw + 31) >> 5) + 3) & ~3);
-    return spBytes + bmBytes + 4 * (size_t)((dh + 3) & ~3) + inW * (dh + 6) + 16 + 4 * (4 + 4 * (RR_Q + 8));
-}
+
 // Stage `rows` x `units` 16-B units (global row pitch gsu units) into LDS (row pitch = units):
 // SB4 units per thread per batch, all loads of a batch in flight before any LDS write
 template <int NT, int SB4>
@@ -805,14 +793,7 @@ struct ScoreGreater {  // KeypointResponseGreater on the packed FAST score
 // retainBest's nth_element depends on; (3) nToRetain / redistribution (ORBextractor.cc:622-670);
 // (4) retainBest per cell, concatenation in cell order, retainBest to the level quota
 // (ORBextractor.cc:680-701) — exact libstdc++ nth_element replays.  Lists live in LDS when the
-// level's survivors fit (Geom::selCap), otherwise in the frame's scratch area `cand2`.
-// survivors per level held in LDS (beyond: the global-scratch path, same result), per frame
-// size: (W*H / 200) rounded down to 512 in [1024, 3072] -- 1536 at 640x480 (6 -> 10 work-groups
-// per CU: 0.177 -> 0.146 ms with 3072), 2048 at 1241x376 (0.499 -> 0.474), 3072 at 1280x720
-// (2048 there: 0.84 -> 1.14, most levels past LDS)
-inline int select_cap(int w, int h) {
-    return std::min(3072, std::max(1024, (int)(((long long)w * h / 200) & ~511ll)));
-}
+// level's survivors fit (Geom::selCap = select_cap(), orb_extract_plan.h), otherwise in the frame's scratch area `cand2`.
 // KeypointResponseGreater on HARRIS_SCORE elements: float response in the high word, the
 // packed FAST record (identity) in the low word.
 struct HarrisGreater {
@@ -1279,11 +1260,6 @@ __device__ __forceinline__ uint32_t blur_round(uint32_t T, bool tail) {
     return min((T + 0x7FFFu + bias) >> 16, 255u);
 }
 
-#ifndef OD_WAVES
-#define OD_WAVES 4  // keypoint slots (waves) per workgroup (8 / 2 measured slower: 0.521 / 0.474 vs 0.468 ms c3;
-                    // two slots per wave, lanes 0-31 / 32-63, 2 or 4 waves per workgroup: 0.531 / 0.567 vs
-                    // 0.428 ms c3, 1.018 / 1.093 vs 0.818 c4 -- half the waves per CU, longer chains)
-#endif
 __global__ void __launch_bounds__(64 * OD_WAVES) k_orient_desc(const uint8_t* __restrict__ pyr, Geom g,
                                                      const uint32_t* __restrict__ lvlOut,
                                                      const uint8_t* __restrict__ slotLvl,
@@ -1594,68 +1570,16 @@ __global__ void __launch_bounds__(256) k_debug_desc_image(const uint8_t* __restr
 // ======================================================================================
 // host side
 // ======================================================================================
-namespace {
+using orbplan::ExtractParams;
+using orbplan::ExtractPlan;
 
-inline int cvRoundH(double v) { return (int)lrint(v); }
-inline short satS16(int v) { return (short)std::min(std::max(v, -32768), 32767); }
-
-// OpenCV 2.4 getGaussianKernel(7, 2, CV_32F) -> convertTo(CV_32S, 256).
-void gaussian_taps7(int* k7) {
-    double scale2X = -0.5 / (2.0 * 2.0), sum = 0;
-    float cf[7];
-    for (int i = 0; i < 7; ++i) {
-        double x = i - 3.0;
-        cf[i] = (float)std::exp(scale2X * x * x);
-        sum += cf[i];
-    }
-    sum = 1. / sum;
-    for (int i = 0; i < 7; ++i) cf[i] = (float)(cf[i] * sum);
-    for (int i = 0; i < 7; ++i) k7[i] = cvRoundH(cf[i] * 256.0f);
-}
-
-}  // namespace
-
-struct orb_extractor {
-    int nfeatures = 0;
-    double scaleFactor = 1.2;  // double member, as in the reference (ORBextractor.h:62)
-    int nlevels = 0, scoreType = 1, fastTh = 20, device = 0, maxBatch = 1;
-    std::vector<float> mvScaleFactor, mvInvScaleFactor;
-    std::vector<int> nDesired;
-    int umax[16] = {};
-    int kpCap = 0;
-    hipStream_t stream = nullptr;      // the handle's own stream (host-buffer entry points)
-    hipStream_t lastStream = nullptr;  // stream of the last launch on this handle's workspace
-    bool lastValid = false;            // lastStream names a stream that ran a launch
-    hipEvent_t evOrder = nullptr;      // orders a launch after the previous one on another stream
-    int pyrBatch = 0;                  // frames whose pyramid phase 1 left in the workspace
-    // geometry of the current frame size
-    int W = 0, H = 0;
-    Geom g{};
-    int fastCl = FT_CL;  // orb_debug_set_fast_corner_list
-    std::vector<CellGeom> cells;
-    std::vector<int> rtab;
-    size_t listLds = 0;  // k_select: the survivor lists
-    size_t cellLds = 0;  // k_rerun: a FAST(7) re-run's LDS (largest cell)
-    size_t resizeLds[ORB_MAX_LEVELS] = {}, resizeLdsS[ORB_MAX_LEVELS] = {};
-    int resizeTail = 0;           // first level of k_pyr_resize_tail (nlevels: none)
-    int tailBufA = 0, tailBufB = 0;
-    size_t tailLds = 0;
-    // k_pyr_stream plan (build_stream_plan); streamOk false: per-level launches only
-    bool streamOk = false;
-    StreamGeom sgeom{};
-    size_t streamLds = 0;
-    int streamK0 = 0;
-    std::vector<StreamLevel> streamLv;  // host copy of d_slv (orb_debug_pyramid_plan_levels)
-    std::vector<int> streamCap;         // ring rows of levels 0 .. L-2
-    uint32_t* d_scol = nullptr;
-    uint4* d_srows = nullptr;
-    StreamLevel* d_slv = nullptr;
-    uint32_t* d_srounds = nullptr;
-    // device workspace
+// The handle's buffers of the current frame size.  Value-initialised: none.  A device buffer is
+// named here and where orb_extractor::alloc / upload allocates it, which registers it for
+// free_ws; the pinned host block is ensure_pinned's.
+struct ExtractWorkspace {
     uint8_t* d_pyr = nullptr;
     size_t pyrAlloc = 0;  // bytes of d_pyr (orb_debug_fill_pyramid)
     FastTile* d_tiles = nullptr;
-    int nTiles = 0;
     uint32_t* d_cand = nullptr;
     int* d_cellCount = nullptr;
     uint32_t* d_cand2 = nullptr;  // k_select scratch when a level's survivors exceed its LDS
@@ -1663,27 +1587,16 @@ struct orb_extractor {
     int* d_lvlCount = nullptr;
     int2* d_lvlInfo = nullptr;     // [frame][ORB_MAX_LEVELS] (first output slot, count): k_select's last WG
     int* d_selDone = nullptr;      // [frame] k_select workgroups done (self-resetting, zero between launches)
-    uint8_t* d_slotLvl = nullptr;  // keypoint slot -> level (kpCap bytes, padded to a dword)
-    uint64_t* d_candH = nullptr;  // HARRIS_SCORE: (response, record) scratch when a level exceeds LDS
-    float* d_lvlResp = nullptr;   // HARRIS_SCORE: response of every kept keypoint
-    float harrisScale4 = 0.f;
+    uint8_t* d_slotLvl = nullptr;  // keypoint slot -> level (ExtractPlan::slotLvl)
+    uint64_t* d_candH = nullptr;   // HARRIS_SCORE: (response, record) scratch when a level exceeds LDS
+    float* d_lvlResp = nullptr;    // HARRIS_SCORE: response of every kept keypoint
     int* d_rtab = nullptr;
     CellGeom* d_cells = nullptr;
-    // per-stage HIP-event timing (orb_profile_*): stage k brackets its kernel(s) on the launch stream
-    static constexpr int kStages = 5;
-    // phases run by orb_extract_batch_device (the other entry points always run both):
-    // bit 0 = pyramid (stages 0-1), bit 1 = detection, selection and descriptors (stages 2-4,
-    // reading the pyramid bit 0 left in the workspace)
-    unsigned phaseMask = 3u;
-    bool pyrLegacy = false;        // orb_debug_set_pyramid_path(1): per-level launches at every batch size
-    bool pyrStreamAlways = false;  // orb_debug_set_pyramid_path(2): k_pyr_stream at every batch size
-    bool prof = false;
-    unsigned profMask = 0;           // stages that record events (bit k = stage k)
-    std::vector<hipEvent_t> evPool;  // 2 per stage per launch, recycled after each read
-    std::vector<std::pair<int, int>> evPending;  // (stage, index of the start event)
-    double stageMs[kStages] = {};
-    long long stageLaunches[kStages] = {};
-    int evNext = 0;
+    // k_pyr_stream's tables (plan.streamOk)
+    uint32_t* d_scol = nullptr;
+    uint32_t* d_srows = nullptr;
+    StreamLevel* d_slv = nullptr;
+    uint32_t* d_srounds = nullptr;
     // staging for host-buffer entry points
     uint8_t* d_img = nullptr;
     uint8_t* d_imgColor = nullptr;  // orb_extract_color's interleaved frame
@@ -1700,6 +1613,36 @@ struct orb_extractor {
     // uploads and downloads are DMA from page-locked memory and nothing is allocated per call
     uint8_t* h_pin = nullptr;
     size_t pinImg = 0;
+};
+
+struct orb_extractor : ExtractWorkspace {
+    ExtractParams prm;  // the constructor's arithmetic (orb_extract_plan.h)
+    int device = 0, maxBatch = 1;
+    float harrisScale4 = 0.f;
+    hipStream_t stream = nullptr;      // the handle's own stream (host-buffer entry points)
+    hipStream_t lastStream = nullptr;  // stream of the last launch on this handle's workspace
+    bool lastValid = false;            // lastStream names a stream that ran a launch
+    hipEvent_t evOrder = nullptr;      // orders a launch after the previous one on another stream
+    int pyrBatch = 0;                  // frames whose pyramid phase 1 left in the workspace
+    // the current frame size's plan (plan.W = plan.H = 0: none, no workspace either)
+    ExtractPlan plan;
+    int fastCl = FT_CL;        // orb_debug_set_fast_corner_list
+    std::vector<void*> owned;  // every device buffer of the workspace, for free_ws
+    // per-stage HIP-event timing (orb_profile_*): stage k brackets its kernel(s) on the launch stream
+    static constexpr int kStages = 5;
+    // phases run by orb_extract_batch_device (the other entry points always run both):
+    // bit 0 = pyramid (stages 0-1), bit 1 = detection, selection and descriptors (stages 2-4,
+    // reading the pyramid bit 0 left in the workspace)
+    unsigned phaseMask = 3u;
+    bool pyrLegacy = false;        // orb_debug_set_pyramid_path(1): per-level launches at every batch size
+    bool pyrStreamAlways = false;  // orb_debug_set_pyramid_path(2): k_pyr_stream at every batch size
+    bool prof = false;
+    unsigned profMask = 0;           // stages that record events (bit k = stage k)
+    std::vector<hipEvent_t> evPool;  // 2 per stage per launch, recycled after each read
+    std::vector<std::pair<int, int>> evPending;  // (stage, index of the start event)
+    double stageMs[kStages] = {};
+    long long stageLaunches[kStages] = {};
+    int evNext = 0;
 
     void free_events() {
         for (auto e : evPool) hipEventDestroy(e);
@@ -1708,644 +1651,90 @@ struct orb_extractor {
         evNext = 0;
     }
 
+    // one hipMalloc per workspace buffer, registered for free_ws
+    template <class T>
+    int alloc(T*& p, size_t bytes) {
+        ORB_HIPCHK(hipMalloc(&p, bytes));
+        owned.push_back(p);
+        return ORB_OK;
+    }
+    // a buffer holding a table of the plan (one element at least, as an empty table has no size to ask for)
+    template <class T>
+    int upload(T*& p, const std::vector<T>& v) {
+        if (int r = alloc(p, std::max<size_t>(v.size(), 1) * sizeof(T))) return r;
+        if (!v.empty()) ORB_HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return ORB_OK;
+    }
+    void release(void* p) {
+        owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end());
+        (void)hipFree(p);
+    }
+
     void free_ws() {
-        hipFree(d_pyr);
-        hipFree(d_tiles);
-        hipFree(d_cand);
-        hipFree(d_cellCount);
-        hipFree(d_cand2);
-        hipFree(d_lvl);
-        hipFree(d_lvlCount);
-        hipFree(d_lvlInfo);
-        hipFree(d_selDone);
-        hipFree(d_slotLvl);
-        hipFree(d_candH);
-        hipFree(d_lvlResp);
-        hipFree(d_rtab);
-        hipFree(d_cells);
-        hipFree(d_img);
-        hipFree(d_imgColor);
-        hipFree(d_out);
-        hipFree(d_scol);
-        hipFree(d_srows);
-        hipFree(d_slv);
-        hipFree(d_srounds);
+        for (void* p : owned) (void)hipFree(p);
+        owned.clear();
         if (h_pin) (void)hipHostFree(h_pin);
-        d_scol = nullptr;
-        d_srows = nullptr;
-        d_slv = nullptr;
-        d_srounds = nullptr;
-        streamOk = false;
-        d_pyr = nullptr;
-        pyrAlloc = 0;
-        d_tiles = nullptr;
-        nTiles = 0;
-        d_cand = nullptr;
-        d_cellCount = nullptr;
-        d_cand2 = nullptr;
-        d_lvl = nullptr;
-        d_lvlCount = nullptr;
-        d_lvlInfo = nullptr;
-        d_selDone = nullptr;
-        d_slotLvl = nullptr;
-        d_candH = nullptr;
-        d_lvlResp = nullptr;
-        d_rtab = nullptr;
-        d_cells = nullptr;
-        d_img = nullptr;
-        d_imgColor = nullptr;
-        imgColorCap = 0;
-        d_out = nullptr;
-        d_kps = nullptr;
-        d_desc = nullptr;
-        d_counts = nullptr;
-        h_pin = nullptr;
-        pinImg = 0;
-        W = H = 0;
+        static_cast<ExtractWorkspace&>(*this) = ExtractWorkspace{};
+        plan = ExtractPlan{};
         pyrBatch = 0;
     }
 
-    // ORBextractor ctor arithmetic (ORBextractor.cc:462-510)
-    void init_params() {
-        mvScaleFactor.assign(nlevels, 1.f);
-        for (int i = 1; i < nlevels; ++i) mvScaleFactor[i] = (float)(mvScaleFactor[i - 1] * scaleFactor);
-        float invScaleFactor = (float)(1.0f / scaleFactor);
-        mvInvScaleFactor.assign(nlevels, 1.f);
-        for (int i = 1; i < nlevels; ++i) mvInvScaleFactor[i] = mvInvScaleFactor[i - 1] * invScaleFactor;
-        nDesired.assign(nlevels, 0);
-        float factor = (float)(1.0 / scaleFactor);
-        float nd = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
-        int sum = 0;
-        for (int l = 0; l < nlevels - 1; ++l) {
-            nDesired[l] = cvRoundH(nd);
-            sum += nDesired[l];
-            nd *= factor;
-        }
-        nDesired[nlevels - 1] = std::max(nfeatures - sum, 0);
-        kpCap = 0;
-        for (int n : nDesired) kpCap += n;
-        int vmax = (int)std::floor(15 * std::sqrt(2.f) / 2 + 1), vmin = (int)std::ceil(15 * std::sqrt(2.f) / 2);
-        for (int v = 0; v <= vmax; ++v) umax[v] = cvRoundH(std::sqrt(225.0 - v * v));
-        for (int v = 15, v0 = 0; v >= vmin; --v) {
-            while (umax[v0] == umax[v0 + 1]) ++v0;
-            umax[v] = v0;
-            ++v0;
-        }
-    }
-
-    // Per-frame-size geometry: level sizes, cell grids, resize tables, workspace.
+    // The workspace of one frame size: the old one dropped, the size planned (every refusal
+    // happens here, before anything is allocated), the buffers allocated and the plan's tables
+    // uploaded.  The plan is kept only when all of that succeeded.
     int build_geometry(int w0, int h0) {
         free_ws();
-        Geom G{};
-        G.L = nlevels;
-        G.fastTh = std::min(std::max(fastTh, 0), 255);
-        G.fastCl = fastCl;
-        G.scoreType = scoreType;
-        int k7[7];
-        gaussian_taps7(k7);
-        for (int i = 0; i < 4; ++i) G.taps[i] = k7[3 + i];
-        if (G.taps[0] != 55 || G.taps[1] != 49 || G.taps[2] != 34 || G.taps[3] != 18)
-            return orb_internal_set_error(ORB_EINVAL,
-                                          "Gaussian taps differ from the kernel's constants (c_rowB, GP_*)");
-        for (int v = 0; v < 16; ++v) G.umax[v] = umax[v];
-        G.umaxNib = 0;
-        for (int v = 0; v < 16; ++v) G.umaxNib |= (unsigned long long)umax[v] << (4 * v);
-        std::vector<CellGeom> cl;
-        cellLds = 0;
-        std::vector<int> rt;
-        long long pyrBytes = 0;
-        int cand = 0, kpBase = 0;
-        for (int l = 0; l < nlevels; ++l) {
-            LevelGeom& lg = G.lv[l];
-            float sc = mvInvScaleFactor[l];
-            lg.w = cvRoundH((float)w0 * sc);
-            lg.h = cvRoundH((float)h0 * sc);
-            if (lg.w < 1 || lg.h < 1 || lg.w >= 4096 || lg.h >= 4096)
-                return orb_internal_set_error(ORB_ENOTSUP, "level size out of the supported range [1, 4095]");
-            lg.pitch = (lg.w + 2 * orbdev::EDGE + 15) & ~15;
-            lg.ph = lg.h + 2 * orbdev::EDGE;
-            lg.fstride = (long long)lg.pitch * lg.ph;
-            lg.base = pyrBytes;
-            pyrBytes += lg.fstride * maxBatch;
-            lg.scale = mvScaleFactor[l];
-            lg.size = (float)(int)(31 * mvScaleFactor[l]);
-            lg.xsimd_blur = (lg.w / 4) * 4;
-            lg.nDesired = nDesired[l];
-            lg.kpBase = kpBase;
-            kpBase += nDesired[l];
-        }
-        // cell grid (ORBextractor.cc:527-597)
-        const float imageRatio = (float)G.lv[0].w / G.lv[0].h;
-        for (int l = 0; l < nlevels; ++l) {
-            LevelGeom& lg = G.lv[l];
-            const int nD = nDesired[l];
-            const int levelCols = (int)std::sqrt((float)nD / (5 * imageRatio));
-            const int levelRows = (int)(imageRatio * levelCols);
-            if (levelCols <= 0 || levelRows <= 0)
-                return orb_internal_set_error(ORB_ENOTSUP,
-                                              "level " + std::to_string(l) + " has an empty cell grid (the reference "
-                                              "divides by zero here)");
-            if (levelCols * levelRows > ORB_MAX_CELLS_PER_LEVEL)
-                return orb_internal_set_error(ORB_ENOTSUP, "more than 256 cells per level");
-            const int maxBX = lg.w - 16, maxBY = lg.h - 16;
-            const int Wd = maxBX - 16, Hd = maxBY - 16;
-            const int cellW = (int)std::ceil((float)Wd / levelCols);
-            const int cellH = (int)std::ceil((float)Hd / levelRows);
-            const int nCells = levelRows * levelCols;
-            lg.rows = levelRows;
-            lg.cols = levelCols;
-            lg.nfc = (int)std::ceil((float)nD / nCells);
-            lg.cellW = cellW;
-            lg.cellH = cellH;
-            // (a 1-px cell's reciprocal 2^32 does not fit: 2^32 - 1, which k_fast applies to n + 1)
-            lg.cellWm = cellW == 1 ? -1 : (int)(uint32_t)((0x100000000ull + cellW - 1) / (uint64_t)cellW);
-            lg.cellHm = cellH == 1 ? -1 : (int)(uint32_t)((0x100000000ull + cellH - 1) / (uint64_t)cellH);
-            lg.detX1 = std::max(maxBX, levelCols > 1 ? 16 + (levelCols - 1) * cellW : 0);
-            lg.detY1 = std::max(maxBY, levelRows > 1 ? 16 + (levelRows - 1) * cellH : 0);
-            // keypoints of non-last cells can sit past maxBorder (ORBextractor.cc:560-597); the
-            // descriptor image must hold every sample they reach (|offset| <= 18)
-            lg.ringX1 = std::max(lg.w + 3, lg.detX1 + 18);
-            lg.ringY1 = std::max(lg.h + 3, lg.detY1 + 18);
-            if (lg.ringX1 > lg.w + 12 || lg.ringY1 > lg.h + 12)
-                return orb_internal_set_error(ORB_ENOTSUP,
-                                              "cell grid too dense: rBRIEF samples leave the 16-px padding");
-            if (cellW <= 0 || cellH <= 0) return orb_internal_set_error(ORB_ENOTSUP, "empty cell size");
-            lg.cell0 = (int)cl.size();
-            std::vector<int> iniXCol(levelCols, 0);
-            float hY = cellH + 6;
-            for (int i = 0; i < levelRows; ++i) {
-                const float iniY = 16 + i * cellH - 3;
-                bool rowSkip = false;
-                if (i == levelRows - 1) {
-                    hY = maxBY + 3 - iniY;
-                    if (hY <= 0) rowSkip = true;
-                }
-                float hX = cellW + 6;
-                for (int j = 0; j < levelCols; ++j) {
-                    CellGeom c{};
-                    c.level = l;
-                    float iniX;
-                    if (rowSkip) {
-                        c.skipped = 1;
-                    } else {
-                        if (i == 0) {
-                            iniX = 16 + j * cellW - 3;
-                            iniXCol[j] = (int)iniX;
-                        } else {
-                            iniX = iniXCol[j];
-                        }
-                        if (j == levelCols - 1) {
-                            hX = maxBX + 3 - iniX;
-                            if (hX <= 0) c.skipped = 1;
-                        }
-                        if (!c.skipped) {
-                            c.x0 = (int)iniX;
-                            c.y0 = (int)iniY;
-                            c.hx = (int)(iniX + hX) - c.x0;
-                            c.hy = (int)(iniY + hY) - c.y0;
-                            if (c.x0 < 0 || c.y0 < 0 || c.x0 + c.hx > lg.w || c.y0 + c.hy > lg.h)
-                                return orb_internal_set_error(ORB_ENOTSUP,
-                                                              "cell ROI outside the level (the reference asserts)");
-                            int dw = c.hx - 6, dh = c.hy - 6;
-                            c.cap = (dw > 0 && dh > 0) ? ((dw + 1) / 2) * ((dh + 1) / 2) : 0;
-                            if (dw > 0 && dh > 0) cellLds = std::max(cellLds, rerun_lds(dw, dh));
-                        }
-                    }
-                    cl.push_back(c);
-                }
-            }
-            // uniform slot stride per level (k_fast computes a cell's slots arithmetically)
-            int capMax = 0;
-            for (size_t i = lg.cell0; i < cl.size(); ++i) capMax = std::max(capMax, cl[i].cap);
-            lg.candBase = cand;
-            lg.capMax = capMax;
-            for (size_t i = lg.cell0; i < cl.size(); ++i) cl[i].candOff = cand + (int)(i - lg.cell0) * capMax;
-            cand += (int)(cl.size() - lg.cell0) * capMax;
-        }
-        G.selCap = select_cap(w0, h0);
-        listLds = (size_t)(scoreType == ORB_HARRIS_SCORE ? 4 : 2) * G.selCap * 4;
-        if (std::max(cellLds, listLds) > 150 * 1024)
-            return orb_internal_set_error(ORB_ENOTSUP, "FAST cell larger than the LDS budget");
-        // resize tables, l >= 1
-        for (int l = 1; l < nlevels; ++l) {
-            LevelGeom& lg = G.lv[l];
-            const LevelGeom& ls = G.lv[l - 1];
-            const int sw = ls.w, sh = ls.h, dw = lg.w, dh = lg.h;
-            double inv_sx = (double)dw / sw, inv_sy = (double)dh / sh;
-            double scale_x = 1. / inv_sx, scale_y = 1. / inv_sy;
-            int isx = cvRoundH(scale_x), isy = cvRoundH(scale_y);
-            if (std::abs(scale_x - isx) < 2.220446049250313e-16 && std::abs(scale_y - isy) < 2.220446049250313e-16 &&
-                isx == 2 && isy == 2)
-                return orb_internal_set_error(ORB_ENOTSUP, "exact 2x level step (OpenCV switches to INTER_AREA)");
-            lg.rtab = (int)rt.size();
-            std::vector<int> xofs(dw), alpha(dw), yofs(dh), beta(dh);
-            int xmax = dw;
-            for (int dx = 0; dx < dw; ++dx) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)std::floor(fx);
-                fx -= sx;
-                if (sx < 0) fx = 0, sx = 0;
-                if (sx + 1 >= sw) {
-                    xmax = std::min(xmax, dx);
-                    if (sx >= sw - 1) fx = 0, sx = sw - 1;
-                }
-                xofs[dx] = sx;
-                short a0 = satS16(cvRoundH((1.f - fx) * 2048)), a1 = satS16(cvRoundH(fx * 2048));
-                alpha[dx] = (int)(uint16_t)a0 | ((int)(uint16_t)a1 << 16);
-            }
-            for (int dy = 0; dy < dh; ++dy) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = (int)std::floor(fy);
-                fy -= sy;
-                yofs[dy] = sy;
-                short b0 = satS16(cvRoundH((1.f - fy) * 2048)), b1 = satS16(cvRoundH(fy * 2048));
-                beta[dy] = (int)(uint16_t)b0 | ((int)(uint16_t)b1 << 16);
-            }
-            for (int dx = 0; dx < dw; ++dx) {  // k_pyr_resize's no-saturation premise
-                const int c0 = alpha[dx] & 0xFFFF, c1 = (alpha[dx] >> 16) & 0xFFFF;
-                if ((short)c0 < 0 || (short)c1 < 0 || c0 + c1 > 2050)
-                    return orb_internal_set_error(ORB_ENOTSUP, "resize coefficient outside [0, 2050]");
-            }
-            for (int dy = 0; dy < dh; ++dy) {
-                const int c0 = beta[dy] & 0xFFFF, c1 = (beta[dy] >> 16) & 0xFFFF;
-                if ((short)c0 < 0 || (short)c1 < 0 || c0 + c1 > 2050)
-                    return orb_internal_set_error(ORB_ENOTSUP, "resize coefficient outside [0, 2050]");
-            }
-            int xs = 0;
-            while (xs <= dw - 16) xs += 16;
-            while (xs < dw - 4) xs += 4;
-            lg.xs_resize = xs;
-            lg.xmax = xmax;
-            rt.insert(rt.end(), xofs.begin(), xofs.end());
-            rt.insert(rt.end(), alpha.begin(), alpha.end());
-            rt.insert(rt.end(), yofs.begin(), yofs.end());
-            rt.insert(rt.end(), beta.begin(), beta.end());
-            // source rectangle of every RZ_TW x TH tile of the padded level (k_pyr_resize), for
-            // the two tile heights
-            auto tiles = [&](int TH, int& off, size_t& ldsOut) {
-                const int tx = (lg.pitch + RZ_TW - 1) / RZ_TW, ty = (lg.ph + TH - 1) / TH;
-                off = (int)rt.size();
-                size_t lds = 0;
-                for (int y = 0; y < ty; ++y)
-                    for (int x = 0; x < tx; ++x) {
-                        int c0 = INT32_MAX, c1 = -1, r0 = INT32_MAX, r1 = -1;
-                        for (int px = x * RZ_TW; px < std::min((x + 1) * RZ_TW, lg.pitch); ++px) {
-                            const int lx = orbdev::reflect101(std::min(px, dw + 31) - 16, dw);
-                            const int sx = xofs[lx];
-                            const int sx1 = (lx < xmax && (alpha[lx] >> 16) != 0) ? sx + 1 : sx;
-                            c0 = std::min(c0, sx);
-                            c1 = std::max(c1, sx1);
-                        }
-                        for (int py = y * TH; py < std::min((y + 1) * TH, lg.ph); ++py) {
-                            const int ly = orbdev::reflect101(py - 16, dh);
-                            r0 = std::min(r0, std::min(std::max(yofs[ly], 0), sh - 1));
-                            r1 = std::max(r1, std::min(std::max(yofs[ly] + 1, 0), sh - 1));
-                        }
-                        const int cs = c0 & ~15, units = ((c1 - cs) >> 4) + 1, nr = r1 - r0 + 1;
-                        rt.push_back(cs);
-                        rt.push_back(units);
-                        rt.push_back(r0);
-                        rt.push_back(nr);
-                        lds = std::max(lds, (size_t)units * 16 * nr);
-                    }
-                ldsOut = lds;
-            };
-            tiles(RZ_TH, lg.rtile, resizeLds[l]);
-            tiles(RZ_THS, lg.rtileS, resizeLdsS[l]);
-            if (resizeLds[l] > 96 * 1024)
-                return orb_internal_set_error(ORB_ENOTSUP, "scale factor too large for the resize tile");
-        }
-        // the fused small-level tail: the first level from which every later level's source
-        // ROI (ping-pong A / B) plus the staged tables fit the CU's LDS
-        resizeTail = nlevels;
-        for (int l = 1; l + 1 < nlevels; ++l) {
-            auto roi = [&](int k) { return k + 1 < nlevels ? (size_t)G.lv[k].w * G.lv[k].h : (size_t)0; };
-            const size_t a = (roi(l) + 15) & ~(size_t)15, bsz = (roi(l + 1) + 15) & ~(size_t)15;
-            const size_t need = a + bsz + (size_t)8 * (G.lv[l].w + G.lv[l].h);
-            if (need <= (size_t)RT_LDS_MAX) {
-                resizeTail = l;
-                tailBufA = (int)a;
-                tailBufB = (int)bsz;
-                tailLds = need;
-                break;
-            }
-        }
-        G.nCells = (int)cl.size();
-        G.candPerFrame = cand;
-        G.kpCap = kpCap;
-        {  // k_orient_desc's grid is ((kpCap + slots - 1) / slots, B): bid / gridDim.x by multiply-high
-            const unsigned long long gx = (unsigned long long)(std::max(kpCap, 1) + OD_WAVES - 1) / OD_WAVES;
-            // and its per-slot offsets are 32-bit: descriptor bytes of the whole batch < 2^32
-            if ((unsigned long long)std::max(kpCap, 1) * (unsigned long long)maxBatch * 32ull >= (1ull << 32))
-                return orb_internal_set_error(ORB_ENOTSUP,
-                                              "max_batch x keypoint capacity too large (descriptor bytes >= 4 GiB)");
-            G.odDivMagic = (uint32_t)(((1ull << 32) + gx - 1) / gx);
-            if (gx * gx * (unsigned long long)maxBatch >= (1ull << 32))
-                return orb_internal_set_error(ORB_ENOTSUP, "keypoint grid too large for k_orient_desc's block decode");
-        }
-        // workspace
+        ExtractPlan P;
+        std::string err;
+        if (int r = orbplan::plan_extract(prm, w0, h0, maxBatch, fastCl, P, err)) return orb_internal_set_error(r, err);
+        const Geom& G = P.g;
+        const size_t cand = (size_t)std::max(G.candPerFrame, 1), kps = (size_t)std::max(prm.kpCap, 1);
         // + slack: k_orient_desc's 64-byte window rows and k_rerun's 16-B ROI units may over-read
         // the last row's pitch
-        ORB_HIPCHK(hipMalloc(&d_pyr, (size_t)pyrBytes + 256));
-        pyrAlloc = (size_t)pyrBytes + 256;
-        // k_fast tiles over each level's detection region: the width split evenly into
-        // ceil(width / 256) tiles of a multiple of 4 columns, as many rows as the LDS budgets
-        // (staged tile, strength plane) and the 16-bit queue codes allow
-        std::vector<FastTile> tl;
-        auto rcp = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); };
-        for (int l = 0; l < nlevels; ++l) {
-            const int detW = G.lv[l].detX1 - orbdev::EDGE;
-            const int nx = (detW + FT_TW_MAX - 1) / FT_TW_MAX;
-            int tw4 = std::max(2, ((detW + 3) / 4 + nx - 1) / nx);
-            tw4 = (tw4 + 1) & ~1;  // tiles of a multiple of 8 columns: every x0 = 0 mod 8
-            const int TW = 4 * tw4;
-            for (int x0 = orbdev::EDGE; x0 < G.lv[l].detX1; x0 += TW) {
-                // first staged byte at sx = 16 + (x0 mod 16) in {16, 24}: the compass groups' dword
-                // pairs (sx - 8 + 8 kp) 8-B aligned, and 16 bytes left of the tile for the left pair
-                const int sx = 16 + (x0 & 15);
-                const int sp = (sx + TW + 8 + 15) & ~15, spw = TW + 8;
-                const int thMax = std::min({FT_IN_BYTES / sp - 8, FT_S_BYTES / spw - 2, 126, 4095 / (tw4 + 2) - 2});
-                if (thMax < 1 || sp > 288) return orb_internal_set_error(ORB_EINVAL, "k_fast tile geometry");
-                for (int y0 = orbdev::EDGE; y0 < G.lv[l].detY1; y0 += thMax) {
-                    const int th = std::min(thMax, G.lv[l].detY1 - y0);
-                    tl.push_back(FastTile{l, x0, y0, tw4, th, sp, sx, rcp(tw4 + 2), rcp(tw4), rcp(sp >> 4)});
-                }
-            }
-        }
-        ORB_HIPCHK(hipMalloc(&d_tiles, tl.size() * sizeof(FastTile)));
-        ORB_HIPCHK(hipMemcpy(d_tiles, tl.data(), tl.size() * sizeof(FastTile), hipMemcpyHostToDevice));
-        nTiles = (int)tl.size();
-
-        ORB_HIPCHK(hipMalloc(&d_cand, (size_t)std::max(cand, 1) * maxBatch * 4));
-        ORB_HIPCHK(hipMalloc(&d_cellCount, (size_t)G.nCells * maxBatch * 4));
-        ORB_HIPCHK(hipMalloc(&d_cand2, (size_t)std::max(cand, 1) * maxBatch * 4));
-        ORB_HIPCHK(hipMalloc(&d_lvl, (size_t)std::max(kpCap, 1) * maxBatch * 4));
-        ORB_HIPCHK(hipMalloc(&d_lvlCount, (size_t)nlevels * maxBatch * 4));
-        ORB_HIPCHK(hipMalloc(&d_lvlInfo, (size_t)ORB_MAX_LEVELS * maxBatch * sizeof(int2)));
-        ORB_HIPCHK(hipMalloc(&d_selDone, (size_t)maxBatch * sizeof(int)));
+        pyrAlloc = (size_t)P.pyrBytes + 256;
+        if (int r = alloc(d_pyr, pyrAlloc)) return r;
+        if (int r = upload(d_tiles, P.tiles)) return r;
+        if (int r = alloc(d_cand, cand * maxBatch * 4)) return r;
+        if (int r = alloc(d_cellCount, (size_t)G.nCells * maxBatch * 4)) return r;
+        if (int r = alloc(d_cand2, cand * maxBatch * 4)) return r;
+        if (int r = alloc(d_lvl, kps * maxBatch * 4)) return r;
+        if (int r = alloc(d_lvlCount, (size_t)G.L * maxBatch * 4)) return r;
+        if (int r = alloc(d_lvlInfo, (size_t)ORB_MAX_LEVELS * maxBatch * sizeof(int2))) return r;
+        if (int r = alloc(d_selDone, (size_t)maxBatch * sizeof(int))) return r;
         ORB_HIPCHK(hipMemset(d_selDone, 0, (size_t)maxBatch * sizeof(int)));
-        {
-            std::vector<uint8_t> sl(((size_t)std::max(kpCap, 1) + 3) & ~(size_t)3, 0);
-            for (int l = 0; l < nlevels; ++l)
-                for (int k = 0; k < G.lv[l].nDesired; ++k) sl[(size_t)G.lv[l].kpBase + k] = (uint8_t)l;
-            ORB_HIPCHK(hipMalloc(&d_slotLvl, sl.size()));
-            ORB_HIPCHK(hipMemcpy(d_slotLvl, sl.data(), sl.size(), hipMemcpyHostToDevice));
+        if (int r = upload(d_slotLvl, P.slotLvl)) return r;
+        if (prm.scoreType == ORB_HARRIS_SCORE) {
+            if (int r = alloc(d_candH, cand * maxBatch * 8)) return r;
+            if (int r = alloc(d_lvlResp, kps * maxBatch * 4)) return r;
         }
-        if (scoreType == ORB_HARRIS_SCORE) {
-            ORB_HIPCHK(hipMalloc(&d_candH, (size_t)std::max(cand, 1) * maxBatch * 8));
-            ORB_HIPCHK(hipMalloc(&d_lvlResp, (size_t)std::max(kpCap, 1) * maxBatch * 4));
+        if (int r = upload(d_rtab, P.rtab)) return r;
+        if (int r = upload(d_cells, P.cells)) return r;
+        if (P.streamOk) {
+            if (int r = upload(d_scol, P.streamCol)) return r;
+            if (int r = upload(d_srows, P.streamRows)) return r;
+            if (int r = upload(d_slv, P.streamLv)) return r;
+            if (int r = upload(d_srounds, P.streamRounds)) return r;
         }
-        ORB_HIPCHK(hipMalloc(&d_rtab, std::max<size_t>(rt.size(), 1) * 4));
-        ORB_HIPCHK(hipMalloc(&d_cells, cl.size() * sizeof(CellGeom)));
-        if (!rt.empty()) ORB_HIPCHK(hipMemcpy(d_rtab, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));
-        ORB_HIPCHK(hipMemcpy(d_cells, cl.data(), cl.size() * sizeof(CellGeom), hipMemcpyHostToDevice));
-        if (int r = build_stream_plan(G, rt)) return r;
-        g = G;
-        cells = std::move(cl);
-        rtab = std::move(rt);
-        W = w0;
-        H = h0;
+        plan = std::move(P);
         return ORB_OK;
     }
 
-    // k_pyr_stream's plan: the round schedule (greedy: level l computes every row whose source
-    // rows of level l-1 are in its ring), the ring capacity of each level (max over rounds of
-    // newest row written - oldest row read + 1), ring slots, per-row and per-quad tables.  K0
-    // (level-0 rows per round) is the largest whose rings fit PS_LDS_TARGET.  Frames with a
-    // level under 17 px (multiple reflections) or rings that never fit keep the per-level path.
-    int build_stream_plan(const Geom& G, const std::vector<int>& rt) {
-        streamOk = false;
-        const int L = nlevels;
-        if (L < 2) return ORB_OK;
-        for (int l = 0; l < L; ++l)
-            if (G.lv[l].w < 17 || G.lv[l].h < 17) return ORB_OK;
-        const int u0 = (G.lv[0].w + 15) / 16;
-        std::vector<std::vector<int>> s0(L), s1(L);
-        for (int l = 1; l < L; ++l) {
-            const LevelGeom& lg = G.lv[l];
-            const int hs = G.lv[l - 1].h;
-            const int* yofs = rt.data() + lg.rtab + 2 * lg.w;
-            s0[l].resize(lg.h);
-            s1[l].resize(lg.h);
-            for (int dy = 0; dy < lg.h; ++dy) {
-                s0[l][dy] = std::min(std::max(yofs[dy], 0), hs - 1);
-                s1[l][dy] = std::min(std::max(yofs[dy] + 1, 0), hs - 1);
-            }
-        }
-        auto ringPitch = [&](int l) { return (G.lv[l].w + 15) & ~15; };
-        auto nqOf = [&](int l) { return l == 0 ? G.lv[0].pitch / 16 : G.lv[l].pitch / 4; };
-        // column words (LDS-resident): one u32 per padded column of levels >= 1
-        // sx | a1 << 12 | (a0 - 2047 + a1) << 24 | simd << 26 | live << 27
-        std::vector<uint32_t> cw;
-        std::vector<int> colQuad(L, 0);
-        for (int l = 1; l < L; ++l) {
-            const LevelGeom& lg = G.lv[l];
-            const int* xofs = rt.data() + lg.rtab;
-            const int* alpha = xofs + lg.w;
-            colQuad[l] = (int)(cw.size() / 4);
-            for (int px = 0; px < 4 * nqOf(l); ++px) {
-                const int lx = orbdev::reflect101(std::min(px, lg.w + 2 * orbdev::EDGE - 1) - orbdev::EDGE, lg.w);
-                const int sx = xofs[lx];
-                const int a0 = lx < lg.xmax ? (alpha[lx] & 0xFFFF) : 2048;
-                const int a1 = lx < lg.xmax ? ((alpha[lx] >> 16) & 0xFFFF) : 0;
-                const int d = a0 - 2047 + a1;
-                if (sx < 0 || sx > 0xFFF || a1 > 0xFFF || d < 0 || d > 3) return ORB_OK;  // not encodable
-                uint32_t c = (uint32_t)sx | ((uint32_t)a1 << 12) | ((uint32_t)d << 24);
-                if (lx < lg.xs_resize) c |= 1u << 26;
-                if (px < lg.w + 2 * orbdev::EDGE) c |= 1u << 27;
-                cw.push_back(c);
-            }
-        }
-        const size_t colBytes = (cw.size() * 4 + 15) & ~(size_t)15;
-        std::vector<uint32_t> rounds;
-        std::vector<int> cap;
-        std::vector<std::vector<int>> plan;  // per round: lo, cnt per level
-        int K0 = 0, maxEnt = 0;
-        size_t lds = 0;
-        for (int k0 : {32, 24, 16, 12, 8, 6, 4, 2}) {
-            if (k0 * u0 > PS_NPF * 64 * PS_LOADERS) continue;
-            std::vector<int> next(L, 0), cp(L, 0);
-            std::vector<std::vector<int>> pl;
-            int me = 0;
-            bool ok = true;
-            for (int n = 0;; ++n) {
-                bool done = true;
-                for (int l = 0; l < L; ++l) done = done && next[l] >= G.lv[l].h;
-                if (done) break;
-                if (n > 65536) {
-                    ok = false;
-                    break;
-                }
-                std::vector<int> lo(L), cnt(L);
-                lo[0] = next[0];
-                cnt[0] = std::min(k0, G.lv[0].h - next[0]);
-                const int avail0 = next[0] + cnt[0];
-                for (int l = 1; l < L; ++l) {
-                    const int srcAvail = l == 1 ? avail0 : next[l - 1];
-                    int d = next[l];
-                    while (d < G.lv[l].h && s1[l][d] < srcAvail) ++d;
-                    lo[l] = next[l];
-                    cnt[l] = d - next[l];
-                }
-                for (int l = 0; l + 1 < L; ++l) {
-                    // level 0: the loaders store round n+1's rows during round n
-                    const int newest = (l == 0 ? std::min(avail0 + k0, G.lv[0].h) : next[l] + cnt[l]) - 1;
-                    int oldest = INT32_MAX;
-                    if (l == 0 && cnt[0]) oldest = lo[0];
-                    if (cnt[l + 1]) oldest = std::min(oldest, s0[l + 1][lo[l + 1]]);
-                    if (oldest != INT32_MAX) cp[l] = std::max(cp[l], newest - oldest + 1);
-                }
-                std::vector<int> rec(2 * L);
-                int ent = 0;
-                for (int l = 0; l < L; ++l) {
-                    rec[2 * l] = lo[l];
-                    rec[2 * l + 1] = cnt[l];
-                    ent += cnt[l];
-                    next[l] += cnt[l];
-                }
-                me = std::max(me, ent);
-                pl.push_back(std::move(rec));
-            }
-            if (!ok || me > PS_NPF * 64 * PS_LOADERS) continue;
-            size_t bytes = 0;
-            bool capOk = true;
-            for (int l = 0; l + 1 < L; ++l) {
-                cp[l] = std::min(std::max(cp[l], 1), G.lv[l].h);
-                capOk = capOk && cp[l] <= 255;
-                bytes += (size_t)cp[l] * ringPitch(l);
-            }
-            const int stride8 = (me + 1) & ~1;
-            bytes += colBytes;
-            if (capOk && bytes <= PS_LDS_TARGET) {
-                K0 = k0;
-                plan = std::move(pl);
-                cap = std::move(cp);
-                maxEnt = stride8;
-                lds = bytes;
-                break;
-            }
-        }
-        if (!K0) return ORB_OK;
-        std::vector<StreamLevel> lv(L);
-        int ringOff = 0;
-        for (int l = 0; l < L; ++l) {
-            const LevelGeom& lg = G.lv[l];
-            StreamLevel& s = lv[l];
-            s.nq = nqOf(l);
-            s.nqm = (uint32_t)((0x100000000ull + s.nq - 1) / (uint64_t)s.nq);
-            s.ringPitch = ringPitch(l);
-            s.ringOff = l + 1 < L ? ringOff : 0;
-            if (l + 1 < L) ringOff += cap[l] * s.ringPitch;
-            s.w = lg.w;
-            s.h = lg.h;
-            s.pitch = lg.pitch;
-            s.base = lg.base;
-            s.fstride = lg.fstride;
-        }
-        // waves per level: one each, then greedily to the level with the most work per wave
-        // (level-0 units are copies: weighted 1/4), up to one wave per 64 column units
-        if (L > PS_THREADS / 64 - PS_LOADERS) return ORB_OK;
-        {
-            std::vector<int> nw(L, 1);
-            for (int left = PS_THREADS / 64 - PS_LOADERS - L; left > 0; --left) {
-                int best = -1;
-                double bw = 0;
-                for (int l = 0; l < L; ++l) {
-                    if (nw[l] * 64 >= lv[l].nq) continue;
-                    const double wk = (double)lv[l].nq * G.lv[l].h * (l == 0 ? 0.25 : 1.0) / nw[l];
-                    if (wk > bw) {
-                        bw = wk;
-                        best = l;
-                    }
-                }
-                if (best < 0) break;
-                ++nw[best];
-            }
-            int ws = PS_LOADERS;
-            for (int l = 0; l < L; ++l) {
-                lv[l].waveStart = ws;
-                lv[l].nWaves = nw[l];
-                ws += nw[l];
-            }
-        }
-        const int colOff = ringOff;  // multiple of 16
-        for (int l = 1; l < L; ++l) lv[l].colOff = colOff + 16 * colQuad[l];
-        lv[0].colOff = 0;
-        // rounds (L level words + the first entry) and the row entries in round order: per row
-        // {source row 0, source row 1 (LDS addresses), b0 << 12, b1 << 12, own ring row (LDS
-        //  address or ~0u), padded-row offset, top mirror offset, bottom mirror offset (~0u: none)}
-        std::vector<uint32_t> ent;
-        for (const auto& rec : plan) {
-            int ne = 0;
-            for (int l = 0; l < L; ++l) {
-                if (rec[2 * l] > 0xFFF || rec[2 * l + 1] > 0x3F || ne > 0x3FFF) return ORB_OK;
-                rounds.push_back((uint32_t)rec[2 * l] | ((uint32_t)rec[2 * l + 1] << 12) | ((uint32_t)ne << 18));
-                ne += rec[2 * l + 1];
-            }
-            rounds.push_back((uint32_t)(ent.size() / 8));
-            rounds.push_back((uint32_t)ne);
-            for (int l = 0; l < L; ++l)
-                for (int dy = rec[2 * l]; dy < rec[2 * l] + rec[2 * l + 1]; ++dy) {
-                    const LevelGeom& lg = G.lv[l];
-                    const uint32_t own =
-                        l + 1 < L ? (uint32_t)(lv[l].ringOff + (dy % cap[l]) * lv[l].ringPitch) : 0xFFFFFFFFu;
-                    const uint32_t main = (uint32_t)((dy + orbdev::EDGE) * lg.pitch);
-                    const uint32_t top = dy >= 1 && dy <= orbdev::EDGE ? (uint32_t)((orbdev::EDGE - dy) * lg.pitch) : 0xFFFFFFFFu;
-                    const uint32_t bot = dy >= lg.h - 17 && dy <= lg.h - 2 ? (uint32_t)((2 * lg.h + 14 - dy) * lg.pitch) : 0xFFFFFFFFu;
-                    if (l == 0) {
-                        ent.insert(ent.end(), {own, 0u, 0u, 0u, 0xFFFFFFFFu, main, top, bot});
-                    } else {
-                        const int cs = cap[l - 1];
-                        const uint32_t beta = (uint32_t)rt[lg.rtab + 2 * lg.w + lg.h + dy];
-                        const uint32_t a0 = (uint32_t)(lv[l - 1].ringOff + (s0[l][dy] % cs) * lv[l - 1].ringPitch);
-                        const uint32_t a1 = (uint32_t)(lv[l - 1].ringOff + (s1[l][dy] % cs) * lv[l - 1].ringPitch);
-                        ent.insert(ent.end(), {a0, a1, (beta & 0xFFFFu) << 12, (beta >> 16) << 12, own, main, top, bot});
-                    }
-                }
-        }
-        // the magic divisions are exact over every task index of every round
-        for (int l = 0; l < L; ++l) {
-            int maxCnt = 0;
-            for (const auto& rec : plan) maxCnt = std::max(maxCnt, rec[2 * l + 1]);
-            for (uint32_t i = 0; i < (uint32_t)(maxCnt * lv[l].nq); ++i)
-                if ((uint32_t)(((uint64_t)i * lv[l].nqm) >> 32) != i / (uint32_t)lv[l].nq) return ORB_OK;
-        }
-        StreamGeom sg{};
-        sg.L = L;
-        sg.nRounds = (int)plan.size();
-        sg.u0 = u0;
-        sg.u0m = (uint32_t)((0x100000000ull + u0 - 1) / (uint64_t)u0);
-        for (uint32_t i = 0; i < (uint32_t)(K0 * u0); ++i)
-            if ((uint32_t)(((uint64_t)i * sg.u0m) >> 32) != i / (uint32_t)u0) return ORB_OK;
-        sg.colWords = (int)cw.size();
-        sg.colOff = colOff;
-        sg.rowOff = colOff + (int)colBytes;
-        sg.rowStride = maxEnt;
-        sg.cap0 = cap[0];
-        ORB_HIPCHK(hipMalloc(&d_scol, std::max<size_t>(cw.size(), 1) * 4));
-        ORB_HIPCHK(hipMemcpy(d_scol, cw.data(), cw.size() * 4, hipMemcpyHostToDevice));
-        ORB_HIPCHK(hipMalloc(&d_srows, ent.size() * 4));
-        ORB_HIPCHK(hipMemcpy(d_srows, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
-        ORB_HIPCHK(hipMalloc(&d_slv, L * sizeof(StreamLevel)));
-        ORB_HIPCHK(hipMemcpy(d_slv, lv.data(), L * sizeof(StreamLevel), hipMemcpyHostToDevice));
-        ORB_HIPCHK(hipMalloc(&d_srounds, rounds.size() * 4));
-        ORB_HIPCHK(hipMemcpy(d_srounds, rounds.data(), rounds.size() * 4, hipMemcpyHostToDevice));
-        sgeom = sg;
-        streamLv = lv;
-        streamCap = cap;
-        streamLds = lds;
-        streamK0 = K0;
-        streamOk = true;
-        return ORB_OK;
+    // The workspace of frame size w x h: the current one, or a new one once every stream that
+    // may still use the current one has drained.
+    int ensure_geometry(int w, int h) {
+        if (w == plan.W && h == plan.H) return ORB_OK;
+        if (int r = drain()) return r;
+        return build_geometry(w, h);
     }
+
 
     int ensure_staging() {
         if (d_img) return ORB_OK;
-        ORB_HIPCHK(hipMalloc(&d_img, (size_t)W * H * maxBatch));
-        const size_t cap = (size_t)std::max(kpCap, 1);
+        if (int r = alloc(d_img, (size_t)plan.W * plan.H * maxBatch)) return r;
+        const size_t cap = (size_t)std::max(prm.kpCap, 1);
         countsPad = ((size_t)maxBatch * 4 + 255) & ~(size_t)255;
         const size_t kpsBytes = ((cap * maxBatch * sizeof(orb_keypoint_t)) + 255) & ~(size_t)255;
-        ORB_HIPCHK(hipMalloc(&d_out, countsPad + kpsBytes + cap * maxBatch * 32));
+        if (int r = alloc(d_out, countsPad + kpsBytes + cap * maxBatch * 32)) return r;
         d_counts = (int*)d_out;
         d_kps = (orb_keypoint_t*)(d_out + countsPad);
         d_desc = d_out + countsPad + kpsBytes;
@@ -2361,8 +1750,8 @@ struct orb_extractor {
             h_pin = nullptr;
             pinImg = 0;
         }
-        const size_t img = (std::max(frameBytes, (size_t)W * H * 4) + 255) & ~(size_t)255;
-        const size_t cap = (size_t)std::max(kpCap, 1);
+        const size_t img = (std::max(frameBytes, (size_t)plan.W * plan.H * 4) + 255) & ~(size_t)255;
+        const size_t cap = (size_t)std::max(prm.kpCap, 1);
         ORB_HIPCHK(hipHostMalloc((void**)&h_pin, img + countsPad + cap * (sizeof(orb_keypoint_t) + 32), 0));
         pinImg = img;
         return ORB_OK;
@@ -2382,7 +1771,7 @@ struct orb_extractor {
 
     // frame 0's count, keypoints and descriptors -> the caller's buffers (one stream sync)
     int download_frame0(orb_keypoint_t* kps_out, int kps_cap, uint8_t* desc_out, int* n_out) {
-        const size_t cap = (size_t)std::max(kpCap, 1);
+        const size_t cap = (size_t)std::max(prm.kpCap, 1);
         uint8_t* pk = h_pin + pinImg;
         uint8_t* pd = pk + countsPad + cap * sizeof(orb_keypoint_t);
         ORB_HIPCHK(hipMemcpyAsync(pk, d_out, countsPad + cap * sizeof(orb_keypoint_t), hipMemcpyDeviceToHost, stream));
@@ -2456,30 +1845,23 @@ struct orb_extractor {
         return ORB_OK;
     }
 
-    int launch(int B, const uint8_t* d_imgs, int stride, long long fpitch, orb_keypoint_t* kps, uint8_t* desc,
-               int* counts, hipStream_t st, int cn = 1, int rgb = 0, unsigned phases = 3u) {
-        if (!(phases & 1u) && B > pyrBatch)
-            return orb_internal_set_error(ORB_EINVAL,
-                                          "phase 2 without a phase-1 pyramid of this geometry for these frames");
-        if (int r = order_after_last(st)) return r;
-        if (prof && evNext > 4096) {  // bound the pool between reads
-            int r = profile_collect();
-            if (r) return r;
-        }
-        bool countsZeroed = false;  // k_pyr_stream zeroed k_fast's cell counters
-        if ((phases & 1u) && cn == 1 && streamOk && (B >= KR_STREAM_BATCH || pyrStreamAlways) && !pyrLegacy) {
+    // The pyramid phase (stages 0 and 1) of B frames.  Returns whether k_pyr_stream zeroed
+    // k_fast's cell counters on its way (`zeroCounts` asks it to).
+    bool launch_pyramid(int B, const uint8_t* d_imgs, int stride, long long fpitch, hipStream_t st, int cn, int rgb,
+                        bool zeroCounts) {
+        const Geom& g = plan.g;
+        pyrBatch = B;
+        if (cn == 1 && plan.streamOk && (B >= KR_STREAM_BATCH || pyrStreamAlways) && !pyrLegacy) {
             // the whole pyramid in one streaming pass per frame (stage 0; stage 1 is empty)
             stage_begin(0, st);
-            StreamGeom sg = sgeom;
+            StreamGeom sg = plan.sgeom;
             const uintptr_t al = (uintptr_t)d_imgs | (uintptr_t)stride | (uintptr_t)fpitch;
             sg.align = (al & 15u) == 0 ? 16 : (al & 3u) == 0 ? 4 : 1;
-            orb_ilp_pyr_stream(B, streamLds, st, d_imgs, stride, fpitch, d_pyr, (const uint32_t*)d_scol,
-                               (const uint4*)d_srows, (const StreamLevel*)d_slv, (const uint32_t*)d_srounds, sg,
-                               (phases & 2u) ? d_cellCount : (int*)nullptr, g.nCells);
-            countsZeroed = (phases & 2u) != 0;
+            orb_ilp_pyr_stream(B, plan.streamLds, st, d_imgs, stride, fpitch, d_pyr, d_scol, (const uint4*)d_srows, d_slv,
+                               d_srounds, sg, zeroCounts ? d_cellCount : (int*)nullptr, g.nCells);
             stage_end(0, st);
-            pyrBatch = B;
-        } else if (phases & 1u) {
+            return zeroCounts;
+        }
         stage_begin(0, st);
         {
             const LevelGeom& lg = g.lv[0];
@@ -2495,32 +1877,47 @@ struct orb_extractor {
         stage_begin(1, st);
         // a few frames: one multi-workgroup launch per level (the tail kernel's one workgroup
         // per frame walks its levels serially, the latency floor of a single frame)
-        const int tail = B < KR_TAIL_BATCH ? nlevels : resizeTail;
+        const int tail = B < KR_TAIL_BATCH ? g.L : plan.resizeTail;
         for (int l = 1; l < tail; ++l) {
             const LevelGeom& lg = g.lv[l];
             if (B < KR_SHORT_BATCH) {
                 dim3 grid((lg.pitch + RZ_TW - 1) / RZ_TW, (lg.ph + RZ_THS - 1) / RZ_THS, B);
-                hipLaunchKernelGGL(k_pyr_resize<RZ_THS>, grid, dim3(256), resizeLdsS[l], st, d_pyr, d_rtab, g.lv[l],
-                                   g.lv[l - 1]);
+                hipLaunchKernelGGL(k_pyr_resize<RZ_THS>, grid, dim3(256), plan.resizeLdsS[l], st, d_pyr, d_rtab,
+                                   g.lv[l], g.lv[l - 1]);
             } else {
                 dim3 grid((lg.pitch + RZ_TW - 1) / RZ_TW, (lg.ph + RZ_TH - 1) / RZ_TH, B);
-                hipLaunchKernelGGL(k_pyr_resize<RZ_TH>, grid, dim3(256), resizeLds[l], st, d_pyr, d_rtab, g.lv[l],
+                hipLaunchKernelGGL(k_pyr_resize<RZ_TH>, grid, dim3(256), plan.resizeLds[l], st, d_pyr, d_rtab, g.lv[l],
                                    g.lv[l - 1]);
             }
         }
-        if (tail < nlevels)
-            hipLaunchKernelGGL(k_pyr_resize_tail, dim3(B), dim3(RT_THREADS), tailLds, st, d_pyr, d_rtab, g, resizeTail,
-                               tailBufA, tailBufB);
+        if (tail < g.L)
+            hipLaunchKernelGGL(k_pyr_resize_tail, dim3(B), dim3(RT_THREADS), plan.tailLds, st, d_pyr, d_rtab, g,
+                               plan.resizeTail, plan.tailBufA, plan.tailBufB);
         stage_end(1, st);
-        pyrBatch = B;
+        return false;
+    }
+
+    int launch(int B, const uint8_t* d_imgs, int stride, long long fpitch, orb_keypoint_t* kps, uint8_t* desc,
+               int* counts, hipStream_t st, int cn = 1, int rgb = 0, unsigned phases = 3u) {
+        if (!(phases & 1u) && B > pyrBatch)
+            return orb_internal_set_error(ORB_EINVAL,
+                                          "phase 2 without a phase-1 pyramid of this geometry for these frames");
+        if (int r = order_after_last(st)) return r;
+        if (prof && evNext > 4096) {  // bound the pool between reads
+            int r = profile_collect();
+            if (r) return r;
         }
+        const Geom& g = plan.g;
+        const size_t cellLds = plan.cellLds, listLds = plan.listLds;
+        bool countsZeroed = false;  // k_pyr_stream zeroed k_fast's cell counters
+        if (phases & 1u) countsZeroed = launch_pyramid(B, d_imgs, stride, fpitch, st, cn, rgb, (phases & 2u) != 0);
         if (!(phases & 2u)) {
             ORB_HIPCHK(hipGetLastError());
             return ORB_OK;
         }
         stage_begin(2, st);
         if (!countsZeroed) ORB_HIPCHK(hipMemsetAsync(d_cellCount, 0, (size_t)g.nCells * B * 4, st));
-        orb_ilp_fast(nTiles, B, st, d_pyr, g, d_tiles, d_cand, d_cellCount);
+        orb_ilp_fast((int)plan.tiles.size(), B, st, d_pyr, g, d_tiles, d_cand, d_cellCount);
         stage_end(2, st);
         stage_begin(3, st);
         // FAST(7) re-runs: spread over NWG workgroups per level (k_rerun), ahead of k_select's one
@@ -2529,12 +1926,12 @@ struct orb_extractor {
         // 0.497 vs 0.696; 1280x720 0.864 vs 1.421.  (cellLds > 0: the first cell of every level
         // has a detection area, build_geometry.)
         {
-            const int NWG = std::min(32, std::max(KR_NWG_MIN, 512 / (B * nlevels)));
-            hipLaunchKernelGGL(k_rerun, dim3(B * NWG, nlevels), dim3(256), cellLds, st, d_pyr, d_cand, d_cellCount, g,
+            const int NWG = std::min(32, std::max(KR_NWG_MIN, 512 / (B * prm.nlevels)));
+            hipLaunchKernelGGL(k_rerun, dim3(B * NWG, prm.nlevels), dim3(256), cellLds, st, d_pyr, d_cand, d_cellCount, g,
                                d_cells, NWG);
         }
-        const dim3 sg(B, nlevels);
-        if (scoreType == ORB_HARRIS_SCORE)
+        const dim3 sg(B, prm.nlevels);
+        if (prm.scoreType == ORB_HARRIS_SCORE)
             hipLaunchKernelGGL((k_select<true, false>), sg, dim3(256), listLds, st, d_pyr, d_cand, d_cand2, d_cellCount,
                                g, d_cells, d_lvl, d_lvlCount, d_candH, d_lvlResp, harrisScale4, d_selDone, d_lvlInfo,
                                counts);
@@ -2552,7 +1949,7 @@ struct orb_extractor {
         }
         stage_end(3, st);
         stage_begin(4, st);
-        dim3 gd((std::max(kpCap, 1) + OD_WAVES - 1) / OD_WAVES, B);
+        dim3 gd((std::max(prm.kpCap, 1) + OD_WAVES - 1) / OD_WAVES, B);
         hipLaunchKernelGGL(k_orient_desc, gd, dim3(64 * OD_WAVES), 0, st, d_pyr, g, d_lvl, d_slotLvl, d_lvlInfo, kps,
                            desc, (const float*)d_lvlResp);
         stage_end(4, st);
@@ -2561,7 +1958,7 @@ struct orb_extractor {
     }
 };
 
-static int upload_pattern(int device) {
+static int upload_pattern(int device, const int* um) {  // um: ExtractParams::umax
     static bool uploaded[64] = {};
     static std::mutex mu;
     std::lock_guard<std::mutex> lock(mu);
@@ -2572,14 +1969,6 @@ static int upload_pattern(int device) {
             for (int c = 0; c < 2; ++c) pf[2 * (64 * q + l) + c] = (float)kOrbPattern31[2 * (8 * l + q) + c];
     ORB_HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_patternf), pf, sizeof(pf)));
     {  // IC disc masks per alignment (umax of ORBextractor.cc:495-510, HALF_PATCH_SIZE 15)
-        int um[16];
-        const int vmax = (int)std::floor(15 * std::sqrt(2.f) / 2 + 1), vmin = (int)std::ceil(15 * std::sqrt(2.f) / 2);
-        for (int v = 0; v <= vmax; ++v) um[v] = (int)lrint(std::sqrt(225.0 - v * v));
-        for (int v = 15, v0 = 0; v >= vmin; --v) {
-            while (um[v0] == um[v0 + 1]) ++v0;
-            um[v] = v0;
-            ++v0;
-        }
         uint32_t off[320], c10[4 * 320] = {}, c01[4 * 320] = {};
         for (int n = 0; n < 320; ++n) off[n] = (uint32_t)(OD_WP * (n / 9) + 4 * (n % 9));
         for (int sh = 0; sh < 4; ++sh)
@@ -2638,7 +2027,8 @@ int orb_extractor_create(int nfeatures, float scale_factor, int nlevels, int sco
     ORB_HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return orb_internal_set_error(ORB_EINVAL, "device ordinal out of range");
     ORB_HIPCHK(hipSetDevice(device));
-    int st = upload_pattern(device);
+    ExtractParams prm = orbplan::extract_params(nfeatures, scale_factor, nlevels, score_type, fast_th);
+    int st = upload_pattern(device, prm.umax);
     if (st) return st;
     // k_select<true> (HARRIS_SCORE) stages (response, record) pairs: up to 96 KB of LDS
     hipFuncSetAttribute((const void*)k_select<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
@@ -2647,11 +2037,7 @@ int orb_extractor_create(int nfeatures, float scale_factor, int nlevels, int sco
     hipFuncSetAttribute((const void*)k_pyr_resize_tail, hipFuncAttributeMaxDynamicSharedMemorySize, RT_LDS_MAX);
     orb_ilp_init();
     orb_extractor* h = new orb_extractor();
-    h->nfeatures = nfeatures;
-    h->scaleFactor = scale_factor;
-    h->nlevels = nlevels;
-    h->scoreType = score_type;
-    h->fastTh = fast_th;
+    h->prm = std::move(prm);
     {  // HarrisResponses' scale (ORBextractor.cc:89-91), blockSize 7, in the reference's float steps
         float scale = (1 << 2) * 7 * 255.0f;
         scale = 1.0f / scale;
@@ -2659,7 +2045,6 @@ int orb_extractor_create(int nfeatures, float scale_factor, int nlevels, int sco
     }
     h->device = device;
     h->maxBatch = max_batch;
-    h->init_params();
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evOrder, hipEventDisableTiming);
     if (e != hipSuccess) {
@@ -2683,17 +2068,17 @@ int orb_extractor_destroy(orb_extractor_t* h) {
     return ORB_OK;
 }
 
-int orb_get_levels(const orb_extractor_t* h) { return h ? h->nlevels : ORB_EINVAL; }
+int orb_get_levels(const orb_extractor_t* h) { return h ? h->prm.nlevels : ORB_EINVAL; }
 
-float orb_get_scale_factor(const orb_extractor_t* h) { return h ? (float)h->scaleFactor : 0.f; }
+float orb_get_scale_factor(const orb_extractor_t* h) { return h ? (float)h->prm.scaleFactor : 0.f; }
 
-int orb_get_max_keypoints(const orb_extractor_t* h) { return h ? h->kpCap : ORB_EINVAL; }
+int orb_get_max_keypoints(const orb_extractor_t* h) { return h ? h->prm.kpCap : ORB_EINVAL; }
 
 int orb_get_level_info(const orb_extractor_t* h, int* fpl, float* sf) {
     if (!h) return ORB_EINVAL;
-    for (int l = 0; l < h->nlevels; ++l) {
-        if (fpl) fpl[l] = h->nDesired[l];
-        if (sf) sf[l] = h->mvScaleFactor[l];
+    for (int l = 0; l < h->prm.nlevels; ++l) {
+        if (fpl) fpl[l] = h->prm.nDesired[l];
+        if (sf) sf[l] = h->prm.mvScaleFactor[l];
     }
     return ORB_OK;
 }
@@ -2708,12 +2093,7 @@ int orb_extract_batch_device(orb_extractor_t* h, int B, const uint8_t* d_imgs, i
         return orb_internal_set_error(ORB_EINVAL, "bad image geometry");
     ORB_HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the null stream, as everywhere in HIP
-    if (w != h->W || hgt != h->H) {
-        // the workspace is re-allocated: drain every stream that may still be using it
-        if (int r = h->drain()) return r;
-        int r = h->build_geometry(w, hgt);
-        if (r) return r;
-    }
+    if (int r = h->ensure_geometry(w, hgt)) return r;
     return h->launch(B, d_imgs, stride, frame_pitch, d_kps, d_desc, d_counts, st, 1, 0, h->phaseMask);
 }
 
@@ -2725,11 +2105,7 @@ int orb_extract_batch(orb_extractor_t* h, int B, const uint8_t* imgs, int w, int
     if (w <= 0 || hgt <= 0 || stride < w || frame_pitch < (int64_t)stride * hgt)
         return orb_internal_set_error(ORB_EINVAL, "bad image geometry");
     ORB_HIPCHK(hipSetDevice(h->device));
-    if (w != h->W || hgt != h->H) {
-        if (int r = h->drain()) return r;
-        int st = h->build_geometry(w, hgt);
-        if (st) return st;
-    }
+    if (int r = h->ensure_geometry(w, hgt)) return r;
     // the copies below overwrite the staging a launch on another stream may still read
     if (int r = h->order_after_last(h->stream)) return r;
     int st = h->ensure_staging();
@@ -2744,9 +2120,9 @@ int orb_extract_batch(orb_extractor_t* h, int B, const uint8_t* imgs, int w, int
     st = h->launch(B, h->d_img, w, (long long)w * hgt, h->d_kps, h->d_desc, h->d_counts, h->stream);
     if (st) return st;
     ORB_HIPCHK(hipMemcpyAsync(n_out, h->d_counts, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-    ORB_HIPCHK(hipMemcpyAsync(kps_out, h->d_kps, (size_t)B * h->kpCap * sizeof(orb_keypoint_t), hipMemcpyDeviceToHost,
+    ORB_HIPCHK(hipMemcpyAsync(kps_out, h->d_kps, (size_t)B * h->prm.kpCap * sizeof(orb_keypoint_t), hipMemcpyDeviceToHost,
                            h->stream));
-    ORB_HIPCHK(hipMemcpyAsync(desc_out, h->d_desc, (size_t)B * h->kpCap * 32, hipMemcpyDeviceToHost, h->stream));
+    ORB_HIPCHK(hipMemcpyAsync(desc_out, h->d_desc, (size_t)B * h->prm.kpCap * 32, hipMemcpyDeviceToHost, h->stream));
     ORB_HIPCHK(hipStreamSynchronize(h->stream));
     return ORB_OK;
 }
@@ -2761,10 +2137,7 @@ int orb_extract(orb_extractor_t* h, const uint8_t* img, int w, int hgt, int stri
     if (!img || !kps_out || !desc_out) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
     if (stride < w) return orb_internal_set_error(ORB_EINVAL, "bad image geometry");
     ORB_HIPCHK(hipSetDevice(h->device));
-    if (w != h->W || hgt != h->H) {
-        if (int r = h->drain()) return r;
-        if (int r = h->build_geometry(w, hgt)) return r;
-    }
+    if (int r = h->ensure_geometry(w, hgt)) return r;
     // the upload overwrites the staging a launch on another stream may still read
     if (int r = h->order_after_last(h->stream)) return r;
     if (int r = h->ensure_staging()) return r;
@@ -2787,11 +2160,7 @@ int orb_extract_batch_device_color(orb_extractor_t* h, int B, const uint8_t* d_i
         return orb_internal_set_error(ORB_EINVAL, "bad image geometry");
     ORB_HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    if (w != h->W || hgt != h->H) {
-        if (int r = h->drain()) return r;
-        int r = h->build_geometry(w, hgt);
-        if (r) return r;
-    }
+    if (int r = h->ensure_geometry(w, hgt)) return r;
     return h->launch(B, d_imgs, stride, frame_pitch, d_kps, d_desc, d_counts, st, channels, rgb);
 }
 
@@ -2806,21 +2175,17 @@ int orb_extract_color(orb_extractor_t* h, const uint8_t* img, int w, int hgt, in
     if (channels != 3 && channels != 4) return orb_internal_set_error(ORB_EINVAL, "channels must be 3 or 4");
     if (stride < w * channels) return orb_internal_set_error(ORB_EINVAL, "bad image geometry");
     ORB_HIPCHK(hipSetDevice(h->device));
-    if (w != h->W || hgt != h->H) {
-        if (int r = h->drain()) return r;
-        int r = h->build_geometry(w, hgt);
-        if (r) return r;
-    }
+    if (int r = h->ensure_geometry(w, hgt)) return r;
     if (int r = h->order_after_last(h->stream)) return r;
     int st = h->ensure_staging();
     if (st) return st;
     const size_t row = (size_t)w * channels;
     if (row * hgt > h->imgColorCap) {  // handle-owned, grow-only (the stream is ordered after every user)
         ORB_HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_imgColor);
+        h->release(h->d_imgColor);
         h->d_imgColor = nullptr;
         h->imgColorCap = 0;
-        ORB_HIPCHK(hipMalloc(&h->d_imgColor, row * hgt));
+        if (int r = h->alloc(h->d_imgColor, row * hgt)) return r;
         h->imgColorCap = row * hgt;
     }
     if (int r = h->upload_frame(h->d_imgColor, img, row, hgt, (size_t)stride)) return r;
@@ -2884,27 +2249,27 @@ int orb_debug_set_pyramid_path(orb_extractor_t* h, int mode) {
 int orb_debug_set_fast_corner_list(orb_extractor_t* h, int cap) {
     if (!h || cap < 0 || cap > FT_CL) return orb_internal_set_error(ORB_EINVAL, "cap must be in [0, 256]");
     h->fastCl = cap;
-    h->g.fastCl = cap;
+    h->plan.g.fastCl = cap;
     return ORB_OK;
 }
 
 int orb_debug_pyramid_plan(const orb_extractor_t* h, int* rows_per_round, int* rounds, int* lds_bytes) {
     if (!h) return orb_internal_set_error(ORB_EINVAL, "bad handle");
-    if (!h->streamOk) return 0;
-    if (rows_per_round) *rows_per_round = h->streamK0;
-    if (rounds) *rounds = h->sgeom.nRounds;
-    if (lds_bytes) *lds_bytes = (int)h->streamLds;
+    if (!h->plan.streamOk) return 0;
+    if (rows_per_round) *rows_per_round = h->plan.streamK0;
+    if (rounds) *rounds = h->plan.sgeom.nRounds;
+    if (lds_bytes) *lds_bytes = (int)h->plan.streamLds;
     return 1;
 }
 
 int orb_debug_pyramid_plan_levels(const orb_extractor_t* h, int* nq, int* n_waves, int* ring_rows, int cap) {
     if (!h || cap < 0) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
-    if (!h->streamOk) return 0;
-    const int L = (int)h->streamLv.size();
+    if (!h->plan.streamOk) return 0;
+    const int L = (int)h->plan.streamLv.size();
     for (int l = 0; l < L && l < cap; ++l) {
-        if (nq) nq[l] = h->streamLv[l].nq;
-        if (n_waves) n_waves[l] = h->streamLv[l].nWaves;
-        if (ring_rows) ring_rows[l] = l + 1 < L ? h->streamCap[l] : 0;
+        if (nq) nq[l] = h->plan.streamLv[l].nq;
+        if (n_waves) n_waves[l] = h->plan.streamLv[l].nWaves;
+        if (ring_rows) ring_rows[l] = l + 1 < L ? h->plan.streamCap[l] : 0;
     }
     return L;
 }
@@ -3002,8 +2367,8 @@ int orb_debug_nth_element_wave_u32(uint32_t* a, int n, int nth, int device) {
 // Download a padded pyramid level of frame `b` (after the last batch) into `out`
 // ((w+32) x (h+32) bytes, tightly packed).  Synchronises the handle's stream.
 int orb_debug_level_image(orb_extractor_t* h, int b, int l, uint8_t* out, int* w, int* hgt) {
-    if (!h || l < 0 || l >= h->nlevels || !h->d_pyr) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
-    const LevelGeom& lg = h->g.lv[l];
+    if (!h || l < 0 || l >= h->prm.nlevels || !h->d_pyr) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
+    const LevelGeom& lg = h->plan.g.lv[l];
     if (w) *w = lg.w;
     if (hgt) *hgt = lg.h;
     if (!out) return ORB_OK;
@@ -3017,9 +2382,9 @@ int orb_debug_level_image(orb_extractor_t* h, int b, int l, uint8_t* out, int* w
 // The bytes of the same level's rows between the padded image and the row pitch: (h+32) rows of
 // pitch - (w+32) bytes (the return value, 0 .. 15), tightly packed.  Every builder writes zeros there.
 int orb_debug_level_row_slack(orb_extractor_t* h, int b, int l, uint8_t* out) {
-    if (!h || b < 0 || b >= h->maxBatch || l < 0 || l >= h->nlevels || !h->d_pyr)
+    if (!h || b < 0 || b >= h->maxBatch || l < 0 || l >= h->prm.nlevels || !h->d_pyr)
         return orb_internal_set_error(ORB_EINVAL, "bad arguments");
-    const LevelGeom& lg = h->g.lv[l];
+    const LevelGeom& lg = h->plan.g.lv[l];
     const int slack = lg.pitch - (lg.w + 32);
     if (!out || slack == 0) return slack;
     ORB_HIPCHK(hipSetDevice(h->device));
@@ -3032,8 +2397,8 @@ int orb_debug_level_row_slack(orb_extractor_t* h, int b, int l, uint8_t* out) {
 // Descriptor image of level l, frame b (blurred ROI + raw padding), padded layout, computed by
 // k_debug_desc_image with k_orient_desc's rounding (the product never materialises it).
 int orb_debug_blur_image(orb_extractor_t* h, int b, int l, uint8_t* out) {
-    if (!h || l < 0 || l >= h->nlevels || !h->d_pyr || !out) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
-    const LevelGeom& lg = h->g.lv[l];
+    if (!h || l < 0 || l >= h->prm.nlevels || !h->d_pyr || !out) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
+    const LevelGeom& lg = h->plan.g.lv[l];
     ORB_HIPCHK(hipSetDevice(h->device));
     ORB_HIPCHK(hipDeviceSynchronize());
     const size_t n = (size_t)(lg.w + 32) * (lg.h + 32);
@@ -3070,13 +2435,13 @@ int orb_debug_ks_timing(unsigned long long* out) {
 #endif
 // Per-cell FAST counts (after fallback) of frame `b`, level `l`, row-major cells.
 int orb_debug_cell_counts(orb_extractor_t* h, int b, int l, int* counts, int cap) {
-    if (!h || l < 0 || l >= h->nlevels || !h->d_cellCount) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
-    const LevelGeom& lg = h->g.lv[l];
+    if (!h || l < 0 || l >= h->prm.nlevels || !h->d_cellCount) return orb_internal_set_error(ORB_EINVAL, "bad arguments");
+    const LevelGeom& lg = h->plan.g.lv[l];
     int n = lg.rows * lg.cols;
     if (n > cap) return ORB_ERANGE;
     ORB_HIPCHK(hipSetDevice(h->device));
     ORB_HIPCHK(hipDeviceSynchronize());
-    ORB_HIPCHK(hipMemcpy(counts, h->d_cellCount + (long long)b * h->g.nCells + lg.cell0, (size_t)n * 4,
+    ORB_HIPCHK(hipMemcpy(counts, h->d_cellCount + (long long)b * h->plan.g.nCells + lg.cell0, (size_t)n * 4,
                       hipMemcpyDeviceToHost));
     return n;
 }

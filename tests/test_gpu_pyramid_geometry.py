@@ -4,12 +4,16 @@ of tests/pyramid_cases.py, which reach every geometry-dependent branch (tests/te
 proves that on the CPU).  Every build runs on a poisoned workspace (tests/pyramid_build.py), only
 the pyramid phase is run, and every padded level of the checked frames must equal the oracle's
 byte for byte, with zeros in the row slack."""
+import ctypes
+import pathlib
+
 import numpy as np
 import pytest
 
 import orbslam_jpminipc_amd as orb
 import pyramid_build as pb
 import pyramid_cases as pc
+import test_extract_plan_host as plan_host
 from oracle_lib import Oracle
 from orbslam_jpminipc_amd import _native
 
@@ -118,6 +122,51 @@ def test_plans_match_the_table():
         k0s.add(k0)
     assert len(k0s) >= 5, sorted(k0s)
     assert hoisted and per_round, (len(hoisted), len(per_round))
+
+
+@pytest.mark.parametrize("W,H,nf,nl", [(64, 57, 300, 4), (320, 240, 500, 8), (1000, 150, 400, 6)])
+def test_handle_plan_agrees_with_the_host_planner(W, H, nf, nl):
+    """The library's planner (built with the device compiler) and tests/native/extract_plan_host.cpp's
+    (the host compiler) answer alike: what orb_debug_pyramid_plan, orb_debug_pyramid_plan_levels,
+    orb_get_level_info and orb_get_max_keypoints report of a handle is the host planner's plan.
+    1000 x 150 with six levels has levels that decode their columns per round."""
+    import torch
+
+    host = ctypes.CDLL(str(pathlib.Path(__file__).resolve().parents[1] / "build" / "libextract_plan_host.so"))
+    q = plan_host.query(host, plan_host.plan_case(W, H, nf, 1.2, nl))
+    ext = orb.ORBextractor(nf, 1.2, nl, orb.FAST_SCORE, 20, device=0, max_batch=1)
+    ext.set_phases(1)
+    ext.extract_batch_device(torch.from_numpy(np.random.default_rng(W).integers(0, 256, (1, H, W), dtype=np.uint8)).cuda())
+    assert q["code"] == 0 and q["stream"] == 1
+    assert pb.plan(ext) == (q["stream"], q["k0"], q["rounds"], q["lds"])
+    assert pb.plan_levels(ext) == q["levels"] and len(q["levels"]) == nl
+    assert ext.mnFeaturesPerLevel.tolist() == q["features_per_level"] and ext.max_keypoints == q["max_keypoints"]
+    assert ext.mvScaleFactor.tobytes() == np.asarray(q["scale"], np.float32).tobytes()
+    if (W, H) == (1000, 150):
+        assert any(nq > 64 * nw for nq, nw, _ in q["levels"][1:])
+
+
+def test_a_refused_size_leaves_the_earlier_one_intact():
+    """96 x 57, then 5000 x 100 (refused: a level wider than 4095), then 96 x 57 again on the same
+    handle: the refusal drops the workspace, the third call rebuilds it and gives the first call's bytes."""
+    import torch
+
+    case = pc.HEIGHT_SWEEP[0]
+    assert (case.W, case.H, case.nf, case.sf, case.nl) == (96, 57, 300, 1.2, 4)
+    ext = _extractor(case, 2)
+    d = torch.from_numpy(pc.frames(case, 2).copy()).cuda()
+
+    def run():
+        kps, desc, counts = (t.cpu().numpy() for t in ext.extract_batch_device(d))
+        return [(int(counts[b]), kps[b, :counts[b]].tobytes(), desc[b, :counts[b]].tobytes()) for b in range(2)]
+
+    first = run()
+    assert sum(n for n, _, _ in first) > 0
+    with pytest.raises(orb.OrbError) as e:
+        ext.extract_batch_device(torch.zeros((2, 100, 5000), dtype=torch.uint8, device="cuda"))
+    assert e.value.code == _native.ORB_ENOTSUP and "level size out of the supported range" in str(e.value)
+    assert pb.plan(ext)[0] == 0  # no geometry, so no plan either
+    assert run() == first
 
 
 def test_input_alignment_and_partial_units():
