@@ -36,10 +36,13 @@
 #include "../../include/orb_abi.h"
 #include "orb_device.h"
 #include "orb_internal.h"
+#include "orb_rot_hist.h"
 
 namespace {
 
-constexpr int TH_LOW = 50, HISTO = 30;  // ORBmatcher.cc:40-42
+constexpr int TH_LOW = 50;  // ORBmatcher.cc:40
+using orb_rot::HISTO_LENGTH;
+using orb_rot::rot_bin;  // rotHist's bin (ORBmatcher.cc:230-236 / 799-805) and the three maxima: orb_rot_hist.h
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int BOW_WAVES = 16;  // waves per pair: the common nodes are dealt round-robin to them
 constexpr int BOW_T = 64 * BOW_WAVES;
@@ -52,14 +55,6 @@ __device__ __forceinline__ uint32_t rmin16(uint32_t v) {
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x124, 0xF, 0xF, false));
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x128, 0xF, 0xF, false));
     return v;
-}
-
-__device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:230-236 / 799-805
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / HISTO));
-    if (bin == HISTO) bin = 0;
-    return bin;
 }
 
 __device__ __forceinline__ int ham(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
@@ -98,7 +93,7 @@ __host__ __device__ inline size_t bow_stage_bytes(int cap) {
 template <bool STAGE>
 __global__ void __launch_bounds__(BOW_T) k_bow_pairs(BowBatch J) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ int s_hist[HISTO];
+    __shared__ int s_hist[HISTO_LENGTH];
     __shared__ int s_ind[3];
     __shared__ int s_acc, s_rem;
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -166,7 +161,7 @@ __global__ void __launch_bounds__(BOW_T) k_bow_pairs(BowBatch J) {
         }
         s_mb[a] = (lo < nodesB && NBs[lo] == id) ? lo : -1;
     }
-    if (tid < HISTO) s_hist[tid] = 0;
+    if (tid < HISTO_LENGTH) s_hist[tid] = 0;
     if (tid == 0) s_acc = 0, s_rem = 0;
     __syncthreads();
 
@@ -347,27 +342,7 @@ __global__ void __launch_bounds__(BOW_T) k_bow_pairs(BowBatch J) {
                 atomicAdd(&s_hist[J.kfkf ? rot_bin(KA[i].angle, KB[v].angle) : rot_bin(KA[v].angle, KB[i].angle)], 1);
         }
         __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (ORBmatcher.cc:1748-1789)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) {
-                    max3 = max2, max2 = max1, max1 = sz;
-                    ind3 = ind2, ind2 = ind1, ind1 = i;
-                } else if (sz > max2) {
-                    max3 = max2, max2 = sz;
-                    ind3 = ind2, ind2 = i;
-                } else if (sz > max3) {
-                    max3 = sz, ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1, ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            s_ind[0] = ind1, s_ind[1] = ind2, s_ind[2] = ind3;
-        }
+        if (tid == 0) orb_rot::three_maxima(s_hist, s_ind);  // ComputeThreeMaxima (ORBmatcher.cc:1748-1789)
         __syncthreads();
         int rem = 0;
         for (int i = tid; i < nOut; i += BOW_T) {

@@ -181,6 +181,14 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+// The device side of a host call's completion flag (orb_internal.h, OrbDoneFlag), by one thread after
+// the workgroup's output stores are complete (s_waitcnt vmcnt(0), barrier): the writes made visible
+// to the host (system-scope release fence), then the sequence stored into the pinned flag.  The
+// kernel's last act: nothing of the call is written after it.
+__device__ __forceinline__ void publish_done(int* flag, int seq) {
+    __threadfence_system();
+    __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 // The value of lane ^ 1.
 __device__ __forceinline__ int lane_xor1(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false); }
 

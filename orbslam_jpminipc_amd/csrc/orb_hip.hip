@@ -18,7 +18,8 @@
 // orb_ilp_* functions; orb_extract.h holds what the two units share.  SearchForInitialization
 // (k_match_init) is orb_sfi.hip.  What a frame size decides (level and cell geometry, resize
 // tables, k_fast's tiles, k_pyr_stream's schedule, every refusal) is the HIP-free planner
-// orb_extract_plan.h; the handle below allocates and uploads from its plan.
+// orb_extract_plan.h; the handle below allocates and uploads from its plan.  The thread's last
+// error (orb_last_error, orb_internal_set_error) is orb_runtime.hip.
 //
 // Reference behaviour that lives in OpenCV 2.4 / libstdc++ / glibc is restated per
 // SURVEY.md Appendix A; DESIGN.md lists every arithmetic rule and where it is pinned.
@@ -63,16 +64,6 @@ __device__ unsigned long long g_kstime[ORB_MAX_LEVELS][8];
 #endif
 // Only switches that keep the output exact (sizes, register targets, timing probes) exist in
 // this translation unit; ablations that change the output are not part of the product source.
-
-// ======================================================================================
-// error plumbing
-// ======================================================================================
-static thread_local std::string g_last_error = "";
-
-int orb_internal_set_error(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
 
 // ======================================================================================
 // kernels
@@ -2010,8 +2001,6 @@ static int upload_pattern(int device, const int* um) {  // um: ExtractParams::um
 // C ABI
 // ======================================================================================
 extern "C" {
-
-const char* orb_last_error(void) { return g_last_error.c_str(); }
 
 const char* orb_version(void) { return "orb_hip gfx950 " __DATE__; }
 

@@ -1,5 +1,6 @@
 // orb_internal.h — host-side plumbing shared by the translation units of liborb_hip.so
-// (not part of the C ABI).
+// (not part of the C ABI).  What is only declared here (the last error, the per-thread contexts,
+// the completion flag) is defined in orb_runtime.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -54,6 +55,25 @@ struct OrbHostCtx {
     int reserve(size_t dev_bytes, size_t host_bytes);
 };
 __attribute__((visibility("hidden"))) OrbHostCtx* orb_internal_thread_ctx(int device);
+
+// The completion flag of a host call whose last kernel publishes it (orb_device.h, publish_done): an
+// int in the context's pinned staging that the host spins on instead of synchronising the stream
+// (~1 us after the kernel's write, where a synchronisation takes several).  One sequence per thread
+// for every user (a thread's calls are one after another, on one staging), never 0, so a flag left
+// by an earlier call, at this offset or another, is never taken for this call's.  The caller
+// synchronises its stream when wait() gives false (an error, or a kernel past the bound); the staging
+// is reused only after the flag or that synchronisation.
+class __attribute__((visibility("hidden"))) OrbDoneFlag {
+    volatile int* flag_ = nullptr;
+    int seq_ = 0;
+
+public:
+    // The thread's sequence advanced (wrapping to 1), the flag at `at` cleared; the sequence to give the kernel.
+    int arm(void* at);
+    // Spins (acquire loads) until the flag holds the sequence: true; false after 2 ms, the clock read
+    // every 1024 spins.
+    bool wait() const;
+};
 
 // One synchronous host-buffer call on the calling thread's context of `device` (< 0: the current one):
 // the planned arena reserved (device: all of it; pinned staging: in + out, the scratch is not

@@ -22,8 +22,13 @@
 //                  vpMatched[idx], vbMatched2[idx]) replay the queries in order on one wave:
 //                  best / second = the first untaken entries of the query's top-8; if the
 //                  top-8 runs out the wave rescans the full window against the live taken
-//                  flags (exact).  Then the rotation histogram / ComputeThreeMaxima filter.
+//                  flags (exact).  Then the rotation histogram / ComputeThreeMaxima filter
+//                  (csrc/orb_rot_hist.h, shared with orb_bow.hip and orb_sfi.hip).
 //                  Matchers without that dependency (Fuse, SearchBySim3) resolve in parallel.
+//
+// The host side below is the matchers' own: the arena of a call, its transport (k_stage_copy in,
+// k_stage_out and the completion flag out) and the drivers.  The per-thread context it runs on
+// and the flag's host side are orb_runtime.hip (declared in orb_internal.h).
 //
 // Arithmetic follows the reference bit for bit: cv::Mat algebra (gemm fast path, norm, dot)
 // in the double/float mix OpenCV 2.4 uses (csrc/orb_cv_math.h), the reference's own float
@@ -33,10 +38,8 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <climits>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -44,16 +47,19 @@
 #include "orb_cv_math.h"
 #include "orb_device.h"
 #include "orb_internal.h"
+#include "orb_rot_hist.h"
 
 using orbdev::hamming256;
 using orbdev::min8;
+using orb_rot::HISTO_LENGTH;
+using orb_rot::rot_bin;  // the rotation filter's bin and three maxima: orb_rot_hist.h
 
 namespace {
 
 constexpr int GRID_COLS = 64, GRID_ROWS = 48, NCELLS = GRID_COLS * GRID_ROWS;  // Frame.h:35-36
 constexpr int TOPK = 8;
 constexpr int TOPK_FIX = 32;  // the fixed-point resolver's lists (fewer exact rescans)
-constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO = 30;  // ORBmatcher.cc:40-42
+constexpr int TH_HIGH = 100, TH_LOW = 50;  // ORBmatcher.cc:40-41
 constexpr int MAX_TARGET = 16384;                       // keypoints per target frame (LDS state)
 static_assert(NCELLS == 3 * 1024 && MAX_TARGET <= 65536, "k_grid_build: 3 cells per thread, u16 item indices");
 
@@ -83,6 +89,20 @@ __host__ __device__ constexpr bool is_exclusive(int m) {
 // best and second best (ratio test) vs best only
 __host__ __device__ constexpr bool needs_second(int m) {
     return m == M_LOCAL || m == M_WINDOW || m == M_F2F || m == M_BOW_KFF || m == M_BOW_KFKF;
+}
+// the matchers with a rotation-consistency check (mbCheckOrientation, e.g. ORBmatcher.cc:491-512)
+__host__ __device__ constexpr bool has_rot_check(int m) {
+    return m == M_WINDOW || m == M_MOTION || m == M_RELOC || m == M_BOW_KFF || m == M_BOW_KFKF || m == M_TRIANG;
+}
+// One list per resolver, X(mode) for every mode it is instantiated for.  k_resolve_fix: the
+// projection-family matchers whose only loop-carried state is the taken targets (each reports by
+// target: out[target] = query); k_resolve: every matcher.
+#define FIX_MODES(X) X(M_LOCAL) X(M_WINDOW) X(M_F2F) X(M_MOTION) X(M_RELOC) X(M_SIM3P)
+#define RESOLVE_MODES(X) FIX_MODES(X) X(M_FUSE) X(M_FUSE_SCW) X(M_SIM3) X(M_BOW_KFF) X(M_BOW_KFKF) X(M_TRIANG)
+__host__ __device__ constexpr bool is_fix_mode(int m) {
+#define OR_MODE(M) || m == M
+    return false FIX_MODES(OR_MODE);
+#undef OR_MODE
 }
 
 // Target frame on the device.
@@ -183,13 +203,6 @@ __device__ __forceinline__ bool cell_range(const DView& T, float u, float v, flo
     if (c.minCY >= GRID_ROWS) return false;
     c.maxCY = min(GRID_ROWS - 1, cvt_x86(ceilf((v - (float)T.minY + r) * T.invH)));
     return c.maxCY >= 0;
-}
-__device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:668-675
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / HISTO));
-    if (bin == HISTO) bin = 0;
-    return bin;
 }
 __device__ __forceinline__ void load_desc(const uint32_t* p, uint32_t (&d)[8]) {
     const uint4 a = *(const uint4*)p, b = *(const uint4*)(p + 4);
@@ -708,7 +721,7 @@ __device__ __forceinline__ bool accept_rule(const Job& J, int bestDist, int best
 template <int MODE>
 __global__ void __launch_bounds__(256) k_resolve(Job J) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ int s_hist[HISTO + 2];
+    __shared__ int s_hist[HISTO_LENGTH + 2];
     __shared__ int s_ind[3];
     __shared__ int s_nacc;
     // the sequential pass's inputs, RES_CHUNK queries per buffer (double-buffered)
@@ -727,8 +740,7 @@ __global__ void __launch_bounds__(256) k_resolve(Job J) {
     for (int i = tid; i < Tn; i += 256) s_taken[i] = J.taken0 ? J.taken0[i] : 0;
     if (tid == 0) s_nacc = 0;
     __syncthreads();
-    const bool rotMode = J.checkOri && (m == M_WINDOW || m == M_MOTION || m == M_RELOC || m == M_BOW_KFF ||
-                                        m == M_BOW_KFKF || m == M_TRIANG);
+    const bool rotMode = J.checkOri && has_rot_check(m);
     if (!is_exclusive(m)) {
         // Fuse / SearchBySim3: best distance per query, no cross-query state
         int acc = 0;
@@ -949,7 +961,7 @@ __global__ void __launch_bounds__(256) k_resolve(Job J) {
     int removed = 0;
     if (rotMode && is_exclusive(m)) {  // rotation consistency (e.g. ORBmatcher.cc:491-512)
         const int nacc = s_nacc;
-        if (tid < HISTO) s_hist[tid] = 0;
+        if (tid < HISTO_LENGTH) s_hist[tid] = 0;
         __syncthreads();
         for (int i = tid; i < nacc; i += 256) {
             const int slot = s_acc[i] >> 5, v = s_accp[i];
@@ -959,37 +971,7 @@ __global__ void __launch_bounds__(256) k_resolve(Job J) {
             atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (1748-1789)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) {
-                    max3 = max2;
-                    max2 = max1;
-                    max1 = sz;
-                    ind3 = ind2;
-                    ind2 = ind1;
-                    ind1 = i;
-                } else if (sz > max2) {
-                    max3 = max2;
-                    max2 = sz;
-                    ind3 = ind2;
-                    ind2 = i;
-                } else if (sz > max3) {
-                    max3 = sz;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1;
-                ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            s_ind[0] = ind1;
-            s_ind[1] = ind2;
-            s_ind[2] = ind3;
-        }
+        if (tid == 0) orb_rot::three_maxima(s_hist, s_ind);  // ComputeThreeMaxima (1748-1789)
         __syncthreads();
         for (int i = tid; i < nacc; i += 256) {
             const int b = s_acc[i] & 31;
@@ -1026,11 +1008,7 @@ __global__ void __launch_bounds__(256) k_resolve(Job J) {
 size_t resolve_fix_lds(const Job& J) { return (size_t)2 * std::max(J.T.n, 1) * 4 + (size_t)std::max(J.qn, 1) * 4 + 16; }
 template <int MODE>
 __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
-    // the projection-family matchers whose only loop-carried state is the taken targets (each
-    // reports by target: out[target] = query)
-    static_assert(MODE == M_LOCAL || MODE == M_WINDOW || MODE == M_F2F || MODE == M_MOTION || MODE == M_RELOC ||
-                      MODE == M_SIM3P,
-                  "fixed-point resolver mode");
+    static_assert(is_fix_mode(MODE), "fixed-point resolver mode");
     extern __shared__ __attribute__((aligned(16))) int rsm[];
     __shared__ int s_changed, s_nres, s_nacc;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1104,49 +1082,19 @@ __global__ void __launch_bounds__(RF_THREADS) k_resolve_fix(Job J) {
     }
     // the rotation consistency check of the matchers that have one (e.g. ORBmatcher.cc:491-512):
     // the histogram counts every final acceptance, order-free
-    __shared__ int s_hist[HISTO + 2];
+    __shared__ int s_hist[HISTO_LENGTH + 2];
     __shared__ int s_ind[3];
-    const bool rotMode = J.checkOri && (MODE == M_WINDOW || MODE == M_MOTION || MODE == M_RELOC);
+    const bool rotMode = J.checkOri && has_rot_check(MODE);
     if (tid == 0) s_nacc = 0;
     if (rotMode) {
-        if (tid < HISTO) s_hist[tid] = 0;
+        if (tid < HISTO_LENGTH) s_hist[tid] = 0;
         __syncthreads();
         for (int t = tid; t < Tn; t += RF_THREADS) {
             const int v = s_tb[t];
             if (v >= 0 && v != INT_MAX) atomicAdd(&s_hist[rot_bin(J.qkps[qrow(J, v)].angle, J.T.kps[t].angle)], 1);
         }
         __syncthreads();
-        if (tid == 0) {  // ComputeThreeMaxima (1748-1789)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < HISTO; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) {
-                    max3 = max2;
-                    max2 = max1;
-                    max1 = sz;
-                    ind3 = ind2;
-                    ind2 = ind1;
-                    ind1 = i;
-                } else if (sz > max2) {
-                    max3 = max2;
-                    max2 = sz;
-                    ind3 = ind2;
-                    ind2 = i;
-                } else if (sz > max3) {
-                    max3 = sz;
-                    ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) {
-                ind2 = -1;
-                ind3 = -1;
-            } else if (max3 < 0.1f * (float)max1) {
-                ind3 = -1;
-            }
-            s_ind[0] = ind1;
-            s_ind[1] = ind2;
-            s_ind[2] = ind3;
-        }
+        if (tid == 0) orb_rot::three_maxima(s_hist, s_ind);  // ComputeThreeMaxima (1748-1789)
     }
     __syncthreads();
     int acc = 0;
@@ -1191,77 +1139,6 @@ __global__ void k_sim3_agree(const int* __restrict__ m1, int n1, const int* __re
 // =========================================================================================
 int fail(int code, const std::string& msg) { return orb_internal_set_error(code, msg); }
 
-}  // namespace
-
-// ---- per-thread host contexts (orb_internal.h) -------------------------------------------
-int OrbHostCtx::reserve(size_t dev_bytes, size_t host_bytes) {
-    if (!stream) {
-        hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return orb_internal_set_error(ORB_EDEVICE, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    }
-    if (dev_bytes > cap) {
-        const size_t want = std::max(dev_bytes, cap * 2);
-        if (buf) (void)hipFree(buf);
-        buf = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&buf, want);
-        if (e != hipSuccess) return orb_internal_set_error(ORB_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-        cap = want;
-    }
-    if (host_bytes > pcap) {
-        const size_t want = std::max(host_bytes, pcap * 2);
-        if (pinned) (void)hipHostFree(pinned);
-        pinned = nullptr;
-        pcap = 0;
-        hipError_t e = hipHostMalloc((void**)&pinned, want, hipHostMallocDefault);
-        if (e != hipSuccess) return orb_internal_set_error(ORB_EDEVICE, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        pcap = want;
-    }
-    return ORB_OK;
-}
-
-namespace {
-// Contexts are never destroyed (no HIP teardown at exit); a thread's contexts go back to the
-// pool when it exits.
-struct CtxPool {
-    std::mutex mu;
-    std::vector<OrbHostCtx*> free[64];
-};
-CtxPool& ctx_pool() {
-    static CtxPool* p = new CtxPool();
-    return *p;
-}
-struct ThreadCtxs {
-    OrbHostCtx* c[64] = {};
-    ~ThreadCtxs() {
-        CtxPool& P = ctx_pool();
-        std::lock_guard<std::mutex> lk(P.mu);
-        for (int d = 0; d < 64; ++d)
-            if (c[d]) P.free[d].push_back(c[d]);
-    }
-};
-thread_local ThreadCtxs t_ctxs;
-}  // namespace
-
-OrbHostCtx* orb_internal_thread_ctx(int device) {
-    if (device < 0 || device >= 64) return nullptr;
-    OrbHostCtx*& c = t_ctxs.c[device];
-    if (!c) {
-        CtxPool& P = ctx_pool();
-        std::lock_guard<std::mutex> lk(P.mu);
-        if (!P.free[device].empty()) {
-            c = P.free[device].back();
-            P.free[device].pop_back();
-        } else {
-            c = new OrbHostCtx();
-            c->device = device;
-        }
-    }
-    return c;
-}
-
-namespace {
-// Bump allocator over one device buffer; `stage` copies a host array into it.
 // The staged inputs of a call, copied into the arena by a kernel reading the pinned staging
 // (mapped host memory) directly: in-stream with the call's kernels, so no copy-engine hand-off
 // (the SDMA copy of ~100 KB took 8.5 us plus ~8 us until the first kernel started, rocprofv3
@@ -1284,28 +1161,28 @@ __global__ void __launch_bounds__(256) k_stage_out(uint8_t* __restrict__ dst, co
     if ((int)threadIdx.x < (bytes & 15)) dst[(n16 << 4) + threadIdx.x] = src[(n16 << 4) + threadIdx.x];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence_system();
-        __hip_atomic_store(flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (threadIdx.x == 0) orbdev::publish_done(flag, seq);
 }
 #define STAGE_OUT_MAX (256u << 10)  // larger results take a D2H copy + stream synchronisation
 
+// Bump allocator over one device buffer (the 256-byte chain of orb_staging.h's OrbLayout); `stage`
+// copies a host array into it.
 struct Arena {
-    std::vector<std::pair<size_t, std::pair<const void*, size_t>>> uploads;
-    size_t size = 0;
-    size_t take(size_t bytes) {
-        const size_t off = size;
-        size += (bytes + 255) & ~(size_t)255;
-        return off;
-    }
-    size_t stage(const void* host, size_t bytes) {
+    struct Upload {
+        size_t off;
+        const void* host;
+        size_t bytes;
+    };
+    std::vector<Upload> uploads;
+    OrbLayout L{};  // offsets only: no base
+    size_t take(size_t bytes) { return L.add(bytes); }
+    size_t stage(const void* host, size_t bytes) {  // (an empty array still gets a region)
         const size_t off = take(bytes ? bytes : 1);
-        if (host && bytes) uploads.push_back({off, {host, bytes}});
+        put(off, host, bytes);
         return off;
     }
     void put(size_t off, const void* host, size_t bytes) {  // into a region from take()
-        if (host && bytes) uploads.push_back({off, {host, bytes}});
+        if (host && bytes) uploads.push_back({off, host, bytes});
     }
 };
 
@@ -1337,19 +1214,23 @@ struct Call {
         ctx = orb_internal_thread_ctx(device);
         return ORB_OK;
     }
-    // allocate (grow) the arena and upload every staged array in one H2D copy
-    std::vector<std::pair<void*, std::pair<size_t, size_t>>> pending;  // (host, (off, bytes)) downloads
+    struct Download {
+        void* host;
+        size_t off, bytes;
+    };
+    std::vector<Download> pending;
     bool inflight = false;  // work queued on ctx->stream since the last sync()
     size_t flagOff = 0;  // the completion flag's offset in the staging (past the arena's)
+    // allocate (grow) the arena and upload every staged array in one H2D copy
     int commit() {
-        flagOff = (A.size + 255) & ~(size_t)255;
-        if (int st = ctx->reserve(A.size, flagOff + 256)) return st;
+        flagOff = A.L.end;
+        if (int st = ctx->reserve(A.L.end, flagOff + 256)) return st;
         inflight = true;
         base = ctx->buf;
         size_t hi = 0;
         for (auto& u : A.uploads) {
-            std::memcpy(ctx->pinned + u.first, u.second.first, u.second.second);
-            hi = std::max(hi, u.first + u.second.second);
+            std::memcpy(ctx->pinned + u.off, u.host, u.bytes);
+            hi = std::max(hi, u.off + u.bytes);
         }
         if (hi && hi <= STAGE_KERNEL_MAX) {
             const size_t n16 = hi >> 4;
@@ -1369,33 +1250,24 @@ struct Call {
     // nothing) and then fills the callers' buffers
     int download(void* host, size_t off, size_t bytes) {
         inflight = true;
-        if (bytes) pending.push_back({host, {off, bytes}});
+        if (bytes) pending.push_back({host, off, bytes});
         return ORB_OK;
     }
     int sync() {
         bool seen = false;
         if (!pending.empty()) {
-            size_t lo = pending[0].second.first, hi = lo;
+            size_t lo = pending[0].off, hi = lo;
             for (auto& d : pending) {
-                lo = std::min(lo, d.second.first);
-                hi = std::max(hi, d.second.first + d.second.second);
+                lo = std::min(lo, d.off);
+                hi = std::max(hi, d.off + d.bytes);
             }
             if (hi - lo <= STAGE_OUT_MAX) {
-                static thread_local int seq = 0;
-                seq = seq == 0x7fffffff ? 1 : seq + 1;
-                volatile int* flag = (volatile int*)(ctx->pinned + flagOff);
-                *flag = 0;
+                OrbDoneFlag done;
+                const int seq = done.arm(ctx->pinned + flagOff);
                 hipLaunchKernelGGL(k_stage_out, dim3(1), dim3(256), 0, ctx->stream, ctx->pinned + lo, base + lo,
                                    (int)(hi - lo), (int*)(ctx->pinned + flagOff), seq);
                 ORB_HIPCHK(hipGetLastError());
-                const auto t0 = std::chrono::steady_clock::now();
-                for (int spin = 0;; ++spin) {
-                    if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) {
-                        seen = true;
-                        break;
-                    }
-                    if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-                }
+                seen = done.wait();
             } else {
                 ORB_HIPCHK(hipMemcpyAsync(ctx->pinned + lo, base + lo, hi - lo, hipMemcpyDeviceToHost, ctx->stream));
             }
@@ -1404,7 +1276,7 @@ struct Call {
         // no results, an error, a call past the bound -- the stream is synchronised)
         if (!seen) ORB_HIPCHK(hipStreamSynchronize(ctx->stream));
         inflight = false;
-        for (auto& d : pending) std::memcpy(d.first, ctx->pinned + d.second.first, d.second.second);
+        for (auto& d : pending) std::memcpy(d.host, ctx->pinned + d.off, d.bytes);
         pending.clear();
         return ORB_OK;
     }
@@ -1519,9 +1391,7 @@ int run_job(const Call& C, const Job& J0) {
     // the projection-family matchers: the fixed-point resolver where its state fits (it also
     // takes targets k_resolve's per-target LDS state cannot: 8 B per target instead of 13), fed
     // TOPK_FIX-entry candidate lists
-    const bool fixMode = J0.outByTarget && (J0.mode == M_LOCAL || J0.mode == M_WINDOW || J0.mode == M_F2F ||
-                                            J0.mode == M_MOTION || J0.mode == M_RELOC || J0.mode == M_SIM3P);
-    const bool useFix = fixMode && resolve_fix_lds(J0) <= 150 * 1024;
+    const bool useFix = J0.outByTarget && is_fix_mode(J0.mode) && resolve_fix_lds(J0) <= 150 * 1024;
     Job J = J0;
     // (32 entries: no exact rescan left in the motion-model projection / WindowSearch of the
     // latency probe, 173 / 301 per call with 8; the local-map search has none with 8 and pays
@@ -1537,13 +1407,8 @@ int run_job(const Call& C, const Job& J0) {
     if (useFix) {
         static std::atomic<bool> fix_attr[64] = {};
         if (!fix_attr[C.device].load()) {
-#define SET_FIX_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve_fix<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
-            SET_FIX_LDS(M_LOCAL);
-            SET_FIX_LDS(M_WINDOW);
-            SET_FIX_LDS(M_F2F);
-            SET_FIX_LDS(M_MOTION);
-            SET_FIX_LDS(M_RELOC);
-            SET_FIX_LDS(M_SIM3P);
+#define SET_FIX_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve_fix<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            FIX_MODES(SET_FIX_LDS)
 #undef SET_FIX_LDS
             fix_attr[C.device] = true;
         }
@@ -1551,12 +1416,7 @@ int run_job(const Call& C, const Job& J0) {
         switch (J.mode) {
 #define LAUNCH_FIX(M) \
     case M: hipLaunchKernelGGL(k_resolve_fix<M>, dim3(1), dim3(RF_THREADS), fl, s, J); break;
-            LAUNCH_FIX(M_LOCAL)
-            LAUNCH_FIX(M_WINDOW)
-            LAUNCH_FIX(M_F2F)
-            LAUNCH_FIX(M_MOTION)
-            LAUNCH_FIX(M_RELOC)
-            LAUNCH_FIX(M_SIM3P)
+            FIX_MODES(LAUNCH_FIX)
 #undef LAUNCH_FIX
             default:
                 return fail(ORB_EINVAL, "matcher mode without a fixed-point resolver");
@@ -1569,37 +1429,15 @@ int run_job(const Call& C, const Job& J0) {
     if (st) return st;
     static std::atomic<bool> attr_set[64] = {};
     if (!attr_set[C.device].load()) {
-#define SET_RESOLVE_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
-        SET_RESOLVE_LDS(M_LOCAL);
-        SET_RESOLVE_LDS(M_WINDOW);
-        SET_RESOLVE_LDS(M_F2F);
-        SET_RESOLVE_LDS(M_MOTION);
-        SET_RESOLVE_LDS(M_RELOC);
-        SET_RESOLVE_LDS(M_SIM3P);
-        SET_RESOLVE_LDS(M_FUSE);
-        SET_RESOLVE_LDS(M_FUSE_SCW);
-        SET_RESOLVE_LDS(M_SIM3);
-        SET_RESOLVE_LDS(M_BOW_KFF);
-        SET_RESOLVE_LDS(M_BOW_KFKF);
-        SET_RESOLVE_LDS(M_TRIANG);
+#define SET_RESOLVE_LDS(M) ORB_HIPCHK(hipFuncSetAttribute((const void*)k_resolve<M>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        RESOLVE_MODES(SET_RESOLVE_LDS)
 #undef SET_RESOLVE_LDS
         attr_set[C.device] = true;
     }
     switch (J.mode) {
 #define LAUNCH_RESOLVE(M) \
     case M: hipLaunchKernelGGL(k_resolve<M>, dim3(1), dim3(256), lds, s, J); break;
-        LAUNCH_RESOLVE(M_LOCAL)
-        LAUNCH_RESOLVE(M_WINDOW)
-        LAUNCH_RESOLVE(M_F2F)
-        LAUNCH_RESOLVE(M_MOTION)
-        LAUNCH_RESOLVE(M_RELOC)
-        LAUNCH_RESOLVE(M_SIM3P)
-        LAUNCH_RESOLVE(M_FUSE)
-        LAUNCH_RESOLVE(M_FUSE_SCW)
-        LAUNCH_RESOLVE(M_SIM3)
-        LAUNCH_RESOLVE(M_BOW_KFF)
-        LAUNCH_RESOLVE(M_BOW_KFKF)
-        LAUNCH_RESOLVE(M_TRIANG)
+        RESOLVE_MODES(LAUNCH_RESOLVE)
 #undef LAUNCH_RESOLVE
         default:
             return fail(ORB_EINVAL, "matcher mode without a resolver");
@@ -1717,11 +1555,9 @@ int bow_match(int mode, const orb_frame_view_t* V1, const uint8_t* flag1, orb_fe
     if ((st = C.begin())) return st;
     DeviceGuard dg(device);
     Arena& A = C.A;
-    const size_t o1k = A.stage(V1->kps, (size_t)V1->n * sizeof(orb_keypoint_t));
-    const size_t o1d = A.stage(V1->desc, (size_t)V1->n * 32);
+    const ViewOffs v1 = plan_view(A, V1, false);
     const size_t o1f = A.stage(flag1, (size_t)V1->n);
-    const size_t o2k = A.stage(V2->kps, (size_t)V2->n * sizeof(orb_keypoint_t));
-    const size_t o2d = A.stage(V2->desc, (size_t)V2->n * 32);
+    const ViewOffs v2 = plan_view(A, V2, false);
     const size_t o2f = flag2 ? A.stage(flag2, (size_t)V2->n) : 0;
     const size_t on1 = A.stage(fv1.nodes, (size_t)fv1.n_nodes * 4);
     const size_t oo1 = A.stage(fv1.offsets, (size_t)(fv1.n_nodes + 1) * 4);
@@ -1732,15 +1568,15 @@ int bow_match(int mode, const orb_frame_view_t* V1, const uint8_t* flag1, orb_fe
     const JobOffs jo = plan_job(A, qn, outN);
     if ((st = C.commit())) return st;
     Job J = base_job(mode);
-    J.T.kps = C.at<orb_keypoint_t>(o2k);
-    J.T.desc = C.at<uint32_t>(o2d);
+    J.T.kps = C.at<orb_keypoint_t>(v2.kps);
+    J.T.desc = C.at<uint32_t>(v2.desc);
     J.T.n = V2->n;
     J.T.nlevels = V2->nlevels;
     std::memcpy(J.T.sigma2, V2->level_sigma2, sizeof(J.T.sigma2));
     std::memcpy(J.T.sf, V2->scale_factors, sizeof(J.T.sf));
     J.T.items = C.at<int>(of2);
-    J.qkps = C.at<orb_keypoint_t>(o1k);
-    J.qdesc = C.at<uint32_t>(o1d);
+    J.qkps = C.at<orb_keypoint_t>(v1.kps);
+    J.qdesc = C.at<uint32_t>(v1.desc);
     J.qflag = C.at<uint8_t>(o1f);
     J.tflag = flag2 ? C.at<uint8_t>(o2f) : nullptr;
     J.fv1Nodes = C.at<uint32_t>(on1);
@@ -1915,10 +1751,6 @@ int orb_features_in_area(const orb_frame_view_t* view, int keyframe, int q, cons
     if ((st = C.download(out_indices, oOut, (size_t)tot * 4)) || (st = C.sync())) return st;
     return ORB_OK;
 }
-
-int orb_frame_is_in_frustum(const orb_frame_view_t* F, orb_map_points_t mps, float viewing_cos_limit,
-                            uint8_t* in_view, float* proj_x, float* proj_y, int32_t* level, float* view_cos,
-                            int device);
 
 int orb_search_by_bow_kf_f(const orb_frame_view_t* KF, const uint8_t* kf_usable, orb_feature_vector_t kf_fv,
                            const orb_frame_view_t* F, orb_feature_vector_t f_fv, float nnratio, int check_ori,

@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -19,6 +18,7 @@
 #include "../../include/orb_abi.h"
 #include "orb_internal.h"
 #include "orb_device.h"
+#include "orb_rot_hist.h"
 
 using namespace orbdev;
 
@@ -99,13 +99,8 @@ struct MatchArgs {
     int fixOff;   // LDS byte offset of the fixed-point phase 2's arrays (16-wave launches), 0: sequential
 };
 
-// ORBmatcher.cc:664-670: the rotation's histogram bin (HISTO_LENGTH 30, factor 1/30)
-__device__ __forceinline__ int rot_bin30(float rot) {
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / 30));
-    if (bin == 30) bin = 0;
-    return bin;
-}
+using orb_rot::HISTO_LENGTH;
+using orb_rot::rot_bin;  // ORBmatcher.cc:664-670: the rotation's histogram bin (orb_rot_hist.h)
 
 // Byte size of one global scratch slot of the large-capacity body (nmax slots / queries).
 __host__ __device__ inline size_t match_big_slot_bytes(int cap, int nmax) {
@@ -713,15 +708,16 @@ __device__ __forceinline__ bool match_pair(const MatchArgs& A, int p, int nmax, 
             const int i = BIG ? t : s_q2i[t];
             const int sl = s_bslot[i];
             if (sl < 0) continue;
-            atomicAdd(&s_hist[rot_bin30((BIG ? K1[i].angle : s_qa[t]) - s_a2[sl])], 1);
+            atomicAdd(&s_hist[rot_bin(BIG ? K1[i].angle : s_qa[t], s_a2[sl])], 1);
         }
         __syncthreads();
         if (wave == 0) {
-            // ComputeThreeMaxima (ORBmatcher.cc:1748-1789) on one wave: its strict-> insertion scan
+            // ComputeThreeMaxima (ORBmatcher.cc:1748-1789) on one wave.  The rule is
+            // orb_rot::three_maxima (orb_rot_hist.h); this restates it: its strict-> insertion scan
             // keeps the three largest non-zero counts, ties in bin order, so the bins are the
             // three largest keys (count << 8 | 255 - bin) by wave-max reductions (tid 0 scanning
             // the 30 bins took ~1 us per pair)
-            const int v = lane < 30 ? s_hist[lane] : 0;
+            const int v = lane < HISTO_LENGTH ? s_hist[lane] : 0;
             const uint32_t key = v > 0 ? ((uint32_t)v << 8) | (uint32_t)(255 - lane) : 0u;
             const uint32_t k1 = ~wave_min_u32(~key);
             const uint32_t k2 = ~wave_min_u32(~(key == k1 ? 0u : key));
@@ -747,7 +743,7 @@ __device__ __forceinline__ bool match_pair(const MatchArgs& A, int p, int nmax, 
             const int i = BIG ? t : s_q2i[t];
             const int sl = s_bslot[i];
             if (sl < 0) continue;
-            const int bn = rot_bin30((BIG ? K1[i].angle : s_qa[t]) - s_a2[sl]);
+            const int bn = rot_bin(BIG ? K1[i].angle : s_qa[t], s_a2[sl]);
             if (bn != i1x && bn != i2x && bn != i3x) s_m12[i] = -1;
         }
         __syncthreads();
@@ -810,10 +806,7 @@ __global__ void __launch_bounds__(NT) k_match_init(MatchArgs A, uint8_t* __restr
                    // workgroup's writes made visible to the host (system-scope release), then the flag
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence_system();
-            __hip_atomic_store(A.done, A.doneSeq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (threadIdx.x == 0) publish_done(A.done, A.doneSeq);
     }
 }
 
@@ -1000,23 +993,11 @@ int orb_search_for_initialization(const orb_keypoint_t* kps1, const uint8_t* des
     // synchronisation takes several) and synchronises the stream only when the flag does not
     // come (an error, or a kernel beyond the bound) -- the staging is then reused by the next call
     // only after the flag: the kernel writes nothing after it
-    static thread_local int seq = 0;
-    seq = seq == 0x7fffffff ? 1 : seq + 1;
-    volatile int* flag = (volatile int*)(hs + oF);
-    *flag = 0;
+    OrbDoneFlag done;
+    const int seq = done.arm(hs + oF);
     int st = sfi_launch((const orb_keypoint_t*)(hs + oK), hs + oD, dc, cap, 1, dc + 2, dc + 3, bounds, nnratio, check_ori,
                         window, (float*)(hs + oP), dm, dm + cap, s, (int*)(hs + oF), seq);
-    bool seen = false;
-    if (st == ORB_OK) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int spin = 0;; ++spin) {
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) {
-                seen = true;
-                break;
-            }
-            if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
-    }
+    const bool seen = st == ORB_OK && done.wait();
     const hipError_t e = seen ? hipSuccess : hipStreamSynchronize(s);
     if (st) return st;
     if (e != hipSuccess) return orb_internal_set_error(ORB_EDEVICE, std::string("match: ") + hipGetErrorString(e));

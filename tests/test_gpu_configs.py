@@ -319,3 +319,60 @@ def test_match_batch_reduced_capacity_fallback():
         prev = np.ascontiguousarray(np.stack([k1["x"], k1["y"]], 1).astype(np.float32))
         no, m12o = search_for_initialization(k1, d1, k2, d2, 640, 480, prev, 0.9, True, 100)
         assert nm[p] == no and np.array_equal(m12[p, : cnt[b]], m12o), p
+
+
+def test_flag_users_from_three_threads():
+    """The two users of the completion flag from three host threads at once, about 200 keypoints a
+    frame: one thread runs SearchForInitialization only, one WindowSearch only, and one alternates
+    SearchForInitialization with SearchByProjection (local), so that its sequence counter and staging
+    serve both; each repeated, each bit-exact against the oracle."""
+    import scenes as S
+    from orbslam_jpminipc_amd.views import View
+
+    rng = np.random.default_rng(78)
+    F2 = S.view(rng, 220, clusters=6, spread=20)
+    idx = rng.integers(0, F2.n, 200)
+    k1 = F2.kps[idx].copy()
+    k1["x"] = np.clip(k1["x"] + rng.normal(0, 4, len(idx)), 0, S.W - 1)
+    k1["y"] = np.clip(k1["y"] + rng.normal(0, 4, len(idx)), 0, S.H - 1)
+    F1 = View(k1, S.perturb(rng, F2.desc[idx], 80), (0, S.W, 0, S.H))
+    mps, _ = S.map_points_on(rng, F2, 200)
+    O = OracleMatcher(0.9, True)
+    iv, px, py, lv, vc = O.isInFrustum(F2, mps, 0.5)
+    local = (F2, None, iv, px, py, lv, vc, mps.desc, 3.0)
+    Fa, Fb = orb.Frame(F1.kps, F1.desc, S.W, S.H), orb.Frame(F2.kps, F2.desc, S.W, S.H)
+    prev0 = np.ascontiguousarray(np.stack([F1.kps["x"], F1.kps["y"]], 1).astype(np.float32))
+    pe = prev0.copy()
+    expect = {"sfi": search_for_initialization(F1.kps, F1.desc, F2.kps, F2.desc, S.W, S.H, pe, 0.9, True, 100),
+              "window": O.WindowSearch(F1, None, F2, 100), "local": O.SearchByProjection_Local(*local)}
+    assert all(e[0] > 0 for e in expect.values())
+
+    def sfi(M):
+        p, m12 = prev0.copy(), []
+        n = M.SearchForInitialization(Fa, Fb, p, m12, 100)
+        assert p.tobytes() == pe.tobytes()
+        return n, np.array(m12, np.int32)
+
+    calls = {"sfi": sfi, "window": lambda M: M.WindowSearch(F1, None, F2, 100),
+             "local": lambda M: M.SearchByProjection_Local(*local)}
+    errors = []
+    start = threading.Barrier(3)
+
+    def run(names, M):
+        try:
+            start.wait()
+            for i in range(20):
+                name = names[i % len(names)]
+                got = calls[name](M)
+                ne, oe = expect[name]
+                assert got[0] == ne and np.array_equal(got[1], oe), (names, name, i)
+        except Exception as e:  # reported by the main thread
+            errors.append((names, repr(e)))
+
+    ts = [threading.Thread(target=run, args=(n, orb.ORBmatcher(0.9, True)))
+          for n in (("sfi",), ("window",), ("sfi", "local"))]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+    assert not errors, errors

@@ -382,3 +382,85 @@ def test_empty_inputs():
     mps = MapPointSet(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32),
                       np.zeros(0, np.float32), np.zeros((0, 32), np.uint8))
     assert same(g.Fuse(F, mps, None), o.Fuse(F, mps, None)) == 0
+
+
+def test_flag_users_interleaved_on_one_thread():
+    """SearchForInitialization (k_match_init's flag) between SearchByProjection (local) and WindowSearch
+    (k_stage_out's flag) on one thread: the two share the thread's sequence counter and its pinned
+    staging.  Per round the frames go small, large (the staging regrows and the flag's offset moves),
+    small again, then an empty query side; three rounds, every result the oracle's."""
+    from oracle_lib import search_for_initialization
+
+    rng = np.random.default_rng(1234)
+    g, o = both(0.9, True)
+    E = View(np.zeros(0, orb.KEYPOINT_DTYPE), np.zeros((0, 32), np.uint8), (0, S.W, 0, S.H))
+    scenes = []
+    for n in (40, 3000, 41, 0):
+        F2 = S.view(rng, max(n, 40), clusters=6, spread=20)
+        if n:
+            idx = rng.integers(0, F2.n, n)
+            k1 = F2.kps[idx].copy()
+            k1["x"] = np.clip(k1["x"] + rng.normal(0, 4, n), 0, S.W - 1)
+            k1["y"] = np.clip(k1["y"] + rng.normal(0, 4, n), 0, S.H - 1)
+            k1["angle"] = (k1["angle"] + rng.choice([0, 0, 0, 90, 200], n)) % 360
+            F1 = View(k1, S.perturb(rng, F2.desc[idx], 80), (0, S.W, 0, S.H))
+            mps, _ = S.map_points_on(rng, F2, n)
+            iv, px, py, lv, vc = o.isInFrustum(F2, mps, 0.5)
+            local = (F2, None, iv, px, py, lv, vc, mps.desc, 3.0)
+        else:
+            F1 = E
+            z = np.zeros(0, np.float32)
+            local = (F2, None, np.zeros(0, np.uint8), z, z, np.zeros(0, np.int32), z, np.zeros((0, 32), np.uint8), 3.0)
+        prev = np.ascontiguousarray(np.stack([F1.kps["x"], F1.kps["y"]], 1).astype(np.float32)).reshape(-1, 2)
+        p = prev.copy()
+        want = {"sfi": search_for_initialization(F1.kps, F1.desc, F2.kps, F2.desc, S.W, S.H, p, 0.9, True, 100),
+                "prev": p, "local": o.SearchByProjection_Local(*local), "window": o.WindowSearch(F1, None, F2, 100)}
+        scenes.append((F1, F2, prev, local, want))
+    assert scenes[1][4]["sfi"][0] > 0 and scenes[1][4]["local"][0] > 0 and scenes[1][4]["window"][0] > 0
+
+    def sfi(F1, F2, prev, want):
+        p, m12 = prev.copy(), []
+        n = g.SearchForInitialization(orb.Frame(F1.kps, F1.desc, S.W, S.H), orb.Frame(F2.kps, F2.desc, S.W, S.H), p, m12, 100)
+        same((n, np.array(m12, np.int32)), want["sfi"])
+        assert p.tobytes() == want["prev"].tobytes()
+
+    for _ in range(3):
+        for F1, F2, prev, local, want in scenes:
+            sfi(F1, F2, prev, want)
+            same(g.SearchByProjection_Local(*local), want["local"])
+            sfi(F1, F2, prev, want)
+            same(g.WindowSearch(F1, None, F2, 100), want["window"])
+
+
+# ComputeThreeMaxima's two edges that a random scene does not reach (csrc/orb_rot_hist.h), per kernel that
+# calls it: four bins of equal count, where bin order decides which three stay, and a second maximum
+# exactly at 0.1f * (float)max1, which stays.  tests/test_gpu_sfi_gates.py has both for k_match_init.
+ROT_CASES = {"four equal bins": ([(9, 4), (3, 4), (11, 4), (6, 4)], 12), "max2 at equality": ([(7, 10), (2, 1)], 11)}
+
+
+@pytest.mark.parametrize("case", sorted(ROT_CASES))
+@pytest.mark.parametrize("kernel", ["k_resolve_fix", "k_bow_pairs", "k_resolve"])
+def test_rotation_filter_edges(kernel, case):
+    """One keypoint pair per histogram entry: 40 px apart (a window of 10 holds the counterpart alone, and
+    each pair has a vocabulary node of its own), equal descriptors, the angles 30 b apart, so every pair is
+    accepted and votes for one bin.  WindowSearch resolves through k_resolve_fix, SearchByBoW (KF, KF) through
+    k_bow_pairs, and through k_resolve once a feature is listed under a second node."""
+    counts, kept = ROT_CASES[case]
+    bins = [b for b, n in counts for _ in range(n)]
+    rng = np.random.default_rng(5)
+    k2 = np.zeros(len(bins), orb.KEYPOINT_DTYPE)
+    k2["x"], k2["y"] = 40 + 40 * (np.arange(len(bins)) % 12), 40 + 40 * (np.arange(len(bins)) // 12)
+    k2["size"], k2["response"], k2["class_id"] = 31, 50, -1
+    k1 = k2.copy()
+    k1["angle"] = 30 * np.array(bins, np.float32)
+    d = S.descriptors(rng, len(bins))
+    F1, F2 = View(k1, d, (0, S.W, 0, S.H)), View(k2, d.copy(), (0, S.W, 0, S.H))
+    g, o = both(0.9, True)
+    if kernel == "k_resolve_fix":
+        n = same(g.WindowSearch(F1, None, F2, 10), o.WindowSearch(F1, None, F2, 10))
+    else:
+        nodes = {i + 1: [i] for i in range(len(bins))}
+        fv2 = S.FeatureVector.from_dict(nodes)
+        fv1 = S.FeatureVector.from_dict({**nodes, 10**6: [0]} if kernel == "k_resolve" else nodes)
+        n = same(g.SearchByBoW_KF_KF(F1, None, fv1, F2, None, fv2), o.SearchByBoW_KF_KF(F1, None, fv1, F2, None, fv2))
+    assert n == kept  # (without the filter every pair stays: len(bins))
