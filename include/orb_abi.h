@@ -1191,6 +1191,69 @@ int orb_local_bundle_adjustment_batch_device(int S, const int32_t* d_kf_off, con
                                              uint8_t* d_edge_erased, uint8_t* d_pt_bad, orb_local_ba_info_t* d_info,
                                              void* stream);
 
+/* Optimizer::OptimizeEssentialGraph (Optimizer.cc:1470-1719, csrc/orb_essgraph.hip): the
+ * pose graph of lines 1498-1659 as flat arrays, optimize(n_iterations), the SE3 recovery and the point
+ * correction.  The map stays with the caller, who also does the topological filtering of the edges.
+ *   keyframes  n_kf (<= ORB_EG_MAX_KF) in the caller's order, bad ones left out: kf_pose n_kf x 12
+ *              floats (Rcw row-major, tcw), entering as Sim3(R, t, 1.0); kf_corrected n_kf x 8 doubles
+ *              (q x y z w, t, s: CorrectedSim3[pKF], taken bit for bit) where kf_has_corrected[i];
+ *              kf_noncorrected / kf_has_noncorrected likewise (NonCorrectedSim3); either pair may be
+ *              NULL (no entry); kf_fixed n_kf u8 (pLoopKF; any number)
+ *   edges      n_edge in the order the reference adds them: edge_i (vertex 0), edge_j (vertex 1),
+ *              edge_kind u8: 0 a loop connection of lines 1539-1567 (Sji = vScw[j] * vScw[i]^-1), 1 an
+ *              edge of lines 1570-1659 (each factor from the non-corrected table where that keyframe
+ *              has an entry).  A pair may come more than once, in either direction.
+ *   points     n_pt: pt_pos n_pt x 3, pt_ref n_pt (the keyframe index of nIDr, -1: a keyframe without
+ *              a vertex, the point comes back as it is), pt_skip n_pt u8 (NULL: none; a skipped
+ *              point's output is not written)
+ * Outputs, each may be NULL: kf_sim3_out n_kf x 8 doubles; kf_pose_out n_kf x 12 ([R | t (1 / s)]
+ * narrowed) and kf_pose_out_f64; pt_pos_out n_pt x 3 and pt_pos_out_f64; info.
+ * ORB_EINVAL: no fixed vertex among those an edge touches, a self-edge, an index out of range, a kind
+ * other than 0 or 1, a non-finite pose or Sim3 value, a scale <= 0.  ORB_ENOTSUP, nothing written and
+ * no scratch of that size requested: more than ORB_EG_MAX_KF keyframes, or a factor profile above
+ * ORB_EG_MAX_PROFILE_BYTES.  n_edge == 0 or no free vertex with an edge: ORB_OK, the inputs after the
+ * round trip, the points corrected through it.  One graph per call, host buffers, synchronous; the
+ * reference has neither a stop flag nor a batch here, and neither has this. */
+#define ORB_EG_MAX_KF 65536
+#define ORB_EG_MAX_PROFILE_BYTES (256ull << 20)
+#define ORB_EG_MAX_TRIALS 200
+typedef struct {
+    int32_t status;
+    int32_t n_active;         /* vertices that an edge touches                                    */
+    int32_t n_free;           /* ... of which not fixed: the block rows of the system             */
+    int32_t n_edges;
+    int64_t profile_bytes;    /* the factor's block profile                                       */
+    int32_t iterations;       /* Levenberg iterations run                                         */
+    int32_t trials;           /* trial steps in all                                               */
+    int32_t refused;          /* trials whose system was not positive definite                    */
+    int32_t reserved;
+    double lambda;            /* lambda at the end (-1: nothing ran)                              */
+    double chi2_before;
+    double chi2_after;
+    double trial_rho[ORB_EG_MAX_TRIALS];   /* the first ORB_EG_MAX_TRIALS trials                  */
+    double trial_chi2[ORB_EG_MAX_TRIALS];
+    uint8_t trial_accepted[ORB_EG_MAX_TRIALS];
+} orb_essential_graph_info_t;
+int orb_optimize_essential_graph(int n_kf, const float* kf_pose, const double* kf_corrected,
+                                 const uint8_t* kf_has_corrected, const double* kf_noncorrected,
+                                 const uint8_t* kf_has_noncorrected, const uint8_t* kf_fixed, int n_edge,
+                                 const int32_t* edge_i, const int32_t* edge_j, const uint8_t* edge_kind, int n_pt,
+                                 const float* pt_pos, const int32_t* pt_ref, const uint8_t* pt_skip, int n_iterations,
+                                 double* kf_sim3_out, float* kf_pose_out, double* kf_pose_out_f64, float* pt_pos_out,
+                                 double* pt_pos_out_f64, orb_essential_graph_info_t* info, int device);
+/* Host arithmetic, no device: Sim3(R, t, 1.0) of a keyframe's Tcw (12 floats) as 8 doubles, with the bits
+ * of the device's conversion, and [R | t (1 / s)] of a Sim3 as orb_optimize_essential_graph writes it
+ * (LoopClosing::CorrectLoop lines 498-506 need both); pose / pose_f64 may be NULL. */
+void orb_sim3_from_pose(const float* Tcw, double* sim3);
+void orb_sim3_to_pose(const double* sim3, float* pose, double* pose_f64);
+/* The point pass on its own (LoopClosing::CorrectLoop lines 466-495): out = to[pair]^-1.map(from[pair].map(P))
+ * with P widened, pair = pt_pair[p] in [0, n_pair); pt_pair[p] == -1 returns the point as it is (bit for
+ * bit in the float output).  sim3_from / sim3_to: n_pair x 8 doubles.  ORB_EINVAL: a pair index out of
+ * range, a non-finite Sim3 value or a scale <= 0.  Host buffers, synchronous. */
+int orb_sim3_correct_points(int n_pt, const float* pt_pos, const int32_t* pt_pair, int n_pair,
+                            const double* sim3_from, const double* sim3_to, float* pt_pos_out,
+                            double* pt_pos_out_f64, int device);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

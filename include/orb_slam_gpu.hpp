@@ -30,6 +30,7 @@
 #define ORB_SLAM_GPU_HPP
 
 #include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -868,8 +869,24 @@ private:
 };
 
 // ORB_SLAM::Optimizer::PoseOptimization(Frame*) (Optimizer.cc:154-285) and Optimizer::OptimizeSim3
-// (Optimizer.cc:1721-1917) and Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536) over PODs; global
-// bundle adjustment and the essential graph stay with the reference's g2o.
+// (Optimizer.cc:1721-1917), Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536) and
+// Optimizer::OptimizeEssentialGraph (Optimizer.cc:1470-1719) over PODs; global bundle adjustment stays with
+// the reference's g2o.
+
+// g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), 1.0) of a keyframe's Tcw (Rcw row-major,
+// tcw) as eight doubles (q x y z w, t, s): host arithmetic with the bits of the device's conversion.
+inline std::array<double, 8> Sim3FromPose(const float Tcw[12]) {
+    std::array<double, 8> S;
+    orb_sim3_from_pose(Tcw, S.data());
+    return S;
+}
+// [R | t (1 / s)] narrowed, what KeyFrame::SetPose receives (Optimizer.cc:1676-1684, LoopClosing.cc:498-506)
+inline std::array<float, 12> PoseFromSim3(const double S[8]) {
+    std::array<float, 12> T;
+    orb_sim3_to_pose(S, T.data(), nullptr);
+    return T;
+}
+
 class Optimizer {
 public:
     // F.keysUn = pFrame->mvKeysUn (N of them), invLevelSigma2 = mvInvLevelSigma2, fx..cy the
@@ -974,6 +991,47 @@ public:
                                               G.edgeObs.data(), G.edgeInvSigma2.data(), R.kfPose.data(), nullptr,
                                               R.ptPos.data(), nullptr, R.edgeErased.data(), R.ptBad.data(), &R.info,
                                               device));
+    }
+
+    // The graph of ORB_SLAM::Optimizer::OptimizeEssentialGraph (Optimizer.cc:1498-1659) as the caller's
+    // flattening loop fills it, and what lines 1666-1718 read back.
+    struct EssentialGraph {
+        std::vector<float> kfPose;            // 12 per keyframe of vpKFs that is not bad (Rcw row-major, tcw)
+        std::vector<uint8_t> kfFixed;         // pKF == pLoopKF
+        std::vector<double> kfCorrected;      // 8 per keyframe (q x y z w, t, s): CorrectedSim3[pKF] where ...
+        std::vector<uint8_t> kfHasCorrected;  // ... CorrectedSim3.count(pKF); both empty: no entry at all
+        std::vector<double> kfNonCorrected;   // NonCorrectedSim3 likewise
+        std::vector<uint8_t> kfHasNonCorrected;
+        std::vector<int32_t> edgeI, edgeJ;    // vertex 0 and vertex 1, indices into the keyframe arrays
+        std::vector<uint8_t> edgeKind;        // 0: lines 1539-1567, 1: lines 1570-1659
+        std::vector<float> ptPos;             // GetWorldPos() of vpMPs
+        std::vector<int32_t> ptRef;           // the index of nIDr's keyframe, -1 where it has no vertex
+        std::vector<uint8_t> ptSkip;          // pMP->isBad(); empty: none
+    };
+    struct EssentialGraphResult {
+        std::vector<double> kfSim3;           // the optimised estimates
+        std::vector<float> kfPose, ptPos;     // what SetPose / SetWorldPos receive (a skipped point: its input)
+        orb_essential_graph_info_t info;
+    };
+    static void OptimizeEssentialGraph(const EssentialGraph& G, EssentialGraphResult& R, int nIterations = 20,
+                                       int device = 0) {
+        const size_t nk = G.kfFixed.size(), ne = G.edgeI.size(), np = G.ptRef.size();
+        auto table_ok = [nk](const std::vector<double>& t, const std::vector<uint8_t>& f) {
+            return (t.empty() && f.empty()) || (t.size() == nk * 8 && f.size() == nk);
+        };
+        if (G.kfPose.size() != nk * 12 || G.edgeJ.size() != ne || G.edgeKind.size() != ne || G.ptPos.size() != np * 3 ||
+            !table_ok(G.kfCorrected, G.kfHasCorrected) || !table_ok(G.kfNonCorrected, G.kfHasNonCorrected) ||
+            (!G.ptSkip.empty() && G.ptSkip.size() != np))
+            throw std::invalid_argument("OptimizeEssentialGraph: array sizes disagree");
+        R.kfSim3.assign(nk * 8, 0.0), R.kfPose.assign(nk * 12, 0.0f), R.ptPos = G.ptPos;
+        orb_check(orb_optimize_essential_graph(
+            (int)nk, G.kfPose.data(), G.kfHasCorrected.empty() ? nullptr : G.kfCorrected.data(),
+            G.kfHasCorrected.empty() ? nullptr : G.kfHasCorrected.data(),
+            G.kfHasNonCorrected.empty() ? nullptr : G.kfNonCorrected.data(),
+            G.kfHasNonCorrected.empty() ? nullptr : G.kfHasNonCorrected.data(), G.kfFixed.data(), (int)ne, G.edgeI.data(),
+            G.edgeJ.data(), G.edgeKind.data(), (int)np, G.ptPos.data(), G.ptRef.data(),
+            G.ptSkip.empty() ? nullptr : G.ptSkip.data(), nIterations, R.kfSim3.data(), R.kfPose.data(), nullptr,
+            R.ptPos.data(), nullptr, &R.info, device));
     }
 };
 

@@ -245,6 +245,10 @@ HIP_SIGNATURES = {
                                             _vp, _vp, _vp, _vp, _vp, _vp]),
     "orb_local_bundle_adjustment": (_i, [_i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 7 + [_i]),
     "orb_local_bundle_adjustment_batch_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i] + [_vp] * 17),
+    "orb_optimize_essential_graph": (_i, [_i] + [_vp] * 6 + [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i] + [_vp] * 6 + [_i]),
+    "orb_sim3_from_pose": (None, [_vp, _vp]),
+    "orb_sim3_to_pose": (None, [_vp, _vp, _vp]),
+    "orb_sim3_correct_points": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),

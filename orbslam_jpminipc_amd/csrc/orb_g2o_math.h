@@ -1,6 +1,6 @@
 // orb_g2o_math.h — the double-precision restatement of g2o and Eigen that the GPU optimizers share
 // (orb_optimizer.hip: PoseOptimization; orb_sim3opt.hip: OptimizeSim3, §14;
-// orb_localba.hip: LocalBundleAdjustment, §21).
+// orb_localba.hip: LocalBundleAdjustment, §21; orb_essgraph.hip: OptimizeEssentialGraph, §22).
 //
 // One definition each of the quaternion / rotation helpers, the Huber kernel, Eigen's dense LDLT
 // solve, the Levenberg bookkeeping of optimization_algorithm_levenberg.cpp, the workgroup sum and
@@ -265,6 +265,175 @@ ORB_G2O_FN static inline bool lm_stop(int qmax, double rho, double ini, double c
     return bad_steps >= 3;
 }
 
+// ---- g2o::Sim3 (types/sim3/sim3.h:41-292) ---------------------------------------------------------
+// The state of a VertexSim3Expmap (OptimizeSim3, §14; OptimizeEssentialGraph, §22): a quaternion
+// that is never normalised, a translation and a scale.  As eight doubles it is q (x y z w), t, s.
+struct Sim3 {
+    double q[4];  // x y z w
+    double t[3];
+    double s;
+};
+
+ORB_G2O_FN static inline __attribute__((always_inline)) void sim3_map(const Sim3& S, const double* X,
+                                                                      double* o) {  // s * (r * xyz) + t
+    double r[3];
+    rotate(S.q, X, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = S.s * r[k] + S.t[k];
+}
+
+ORB_G2O_FN static inline Sim3 sim3_inverse(const Sim3& S) {  // sim3.h:233-236
+    Sim3 I;
+    I.q[0] = -S.q[0], I.q[1] = -S.q[1], I.q[2] = -S.q[2], I.q[3] = S.q[3];
+    const double f = -1. / S.s;
+    const double v[3] = {f * S.t[0], f * S.t[1], f * S.t[2]};
+    rotate(I.q, v, I.t);
+    I.s = 1. / S.s;
+    return I;
+}
+
+ORB_G2O_FN static inline Sim3 sim3_mul(const Sim3& A, const Sim3& B) {  // Sim3::operator* (sim3.h:266-272)
+    Sim3 r;
+    quat_mul(A.q, B.q, r.q);
+    double rt[3];
+    rotate(A.q, B.t, rt);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.t[k] = A.s * rt[k] + A.t[k];
+    r.s = A.s * B.s;
+    return r;
+}
+
+// Sim3(Matrix3d R, t, 1.0) of a keyframe's Tcw = [Rcw row-major | tcw] (Optimizer.cc:1515-1517): the
+// floats widened, the quaternion of the widened R, not normalised
+ORB_G2O_FN static inline Sim3 sim3_from_pose(const float* Tcw) {
+    Sim3 S;
+    double R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (double)Tcw[k];
+    quat_from_matrix(R, S.q);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) S.t[k] = (double)Tcw[9 + k];
+    S.s = 1.0;
+    return S;
+}
+
+// [R | t * (1 / s)] of a Sim3, twelve doubles (Optimizer.cc:1676-1682; LoopClosing.cc:498-506)
+ORB_G2O_FN static inline void sim3_to_pose(const Sim3& S, double* M) {
+    matrix_from_quat(S.q, M);
+    const double is = 1. / S.s;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) M[9 + k] = S.t[k] * is;
+}
+
+// x = W^-1 t as Eigen's Matrix3d::lu().solve(): PartialPivLU, the pivot of a column the largest
+// |entry| on or below the diagonal (the first of equals), rows exchanged, then the unit-lower and the
+// upper substitution.  Eigen is not in the reference tree, so the order inside it is not pinned
+// ("unpinned").  The exchanges are selects: no index depends on the data.
+ORB_G2O_FN static inline void lu3_solve(const double* W, const double* t, double* x) {
+    double a00 = W[0], a01 = W[1], a02 = W[2], a10 = W[3], a11 = W[4], a12 = W[5], a20 = W[6], a21 = W[7], a22 = W[8];
+    double b0 = t[0], b1 = t[1], b2 = t[2];
+    {  // column 0
+        const double m1 = fabs(a00) < fabs(a10) ? fabs(a10) : fabs(a00);
+        const bool p2 = fabs(a20) > m1;
+        const bool p1 = !p2 && fabs(a10) > fabs(a00);
+        cswap(p1, a00, a10), cswap(p1, a01, a11), cswap(p1, a02, a12), cswap(p1, b0, b1);
+        cswap(p2, a00, a20), cswap(p2, a01, a21), cswap(p2, a02, a22), cswap(p2, b0, b2);
+    }
+    a10 /= a00, a20 /= a00;
+    a11 -= a10 * a01, a12 -= a10 * a02;
+    a21 -= a20 * a01, a22 -= a20 * a02;
+    {  // column 1
+        const bool p2 = fabs(a21) > fabs(a11);
+        cswap(p2, a10, a20), cswap(p2, a11, a21), cswap(p2, a12, a22), cswap(p2, b1, b2);
+    }
+    a21 /= a11;
+    a22 -= a21 * a12;
+    b1 -= a10 * b0;
+    b2 -= a20 * b0;
+    b2 -= a21 * b1;
+    x[2] = b2 / a22;
+    x[1] = (b1 - a12 * x[2]) / a11;
+    x[0] = ((b0 - a01 * x[1]) - a02 * x[2]) / a00;
+}
+
+// Functions marked ORB_G2O_LIBM_FN are one source for the host and the device too, but call log /
+// acos / sin / cos: the two libraries round those differently, so their bits are not pinned across
+// the two, only their values (tests/native/essential_graph_host.cpp).
+#define ORB_G2O_LIBM_FN ORB_G2O_FN
+
+// Which of log()'s four branches an evaluation took, and how far it sat from the two tests
+// (|sigma| against eps, d against 1 - eps): what the scene generators' margins are read from.
+struct Sim3LogTrace {
+    double sigma, d;
+    int branch;  // bit 0: |sigma| >= eps, bit 1: d <= 1 - eps
+};
+
+// Sim3::log() (sim3.h:148-230): (omega, upsilon, sigma)
+ORB_G2O_LIBM_FN static inline void sim3_log(const Sim3& S, double* res, Sim3LogTrace* trace = nullptr) {
+    const double sigma = log(S.s);
+    double R[9];
+    matrix_from_quat(S.q, R);
+    const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
+    const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};  // deltaR (se3_ops.hpp:40-47)
+    const double eps = 0.00001;
+    double omega[3], A, B, C;
+    const bool near = d > 1 - eps;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (near) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) omega[k] = 0.5 * dR[k];
+            A = 1. / 2.;
+            B = 1. / 6.;
+        } else {
+            const double theta = acos(d);
+            const double theta2 = theta * theta;
+            const double f = theta / (2 * sqrt(1 - d * d));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) omega[k] = f * dR[k];
+            A = (1 - cos(theta)) / (theta2);
+            B = (theta - sin(theta)) / (theta2 * theta);
+        }
+    } else {
+        C = (S.s - 1) / sigma;
+        if (near) {
+            const double sigma2 = sigma * sigma;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) omega[k] = 0.5 * dR[k];
+            A = ((sigma - 1) * S.s + 1) / (sigma2);
+            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
+        } else {
+            const double theta = acos(d);
+            const double f = theta / (2 * sqrt(1 - d * d));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) omega[k] = f * dR[k];
+            const double theta2 = theta * theta;
+            const double a = S.s * sin(theta);
+            const double b = S.s * cos(theta);
+            const double c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+        }
+    }
+    if (trace) trace->sigma = sigma, trace->d = d, trace->branch = (fabs(sigma) < eps ? 0 : 1) | (near ? 0 : 2);
+    // W = A * Omega + B * Omega * Omega + C * I: (B * Omega) * Omega, each entry a row sum left to right
+    const double O[9] = {0, -omega[2], omega[1], omega[2], 0, -omega[0], -omega[1], omega[0], 0};
+    double W[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = (B * O[3 * i]) * O[j];
+            s += (B * O[3 * i + 1]) * O[3 + j];
+            s += (B * O[3 * i + 2]) * O[6 + j];
+            W[3 * i + j] = (A * O[3 * i + j] + s) + C * (i == j ? 1.0 : 0.0);
+        }
+    lu3_solve(W, S.t, res + 3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) res[k] = omega[k];
+    res[6] = sigma;
+}
+
 #ifdef __HIPCC__
 
 // One trial's verdict: accepted (true) scales lambda by 1 - (2 rho - 1)^3 clamped to [1/3, 2/3] and
@@ -349,6 +518,63 @@ __device__ Pose exp_update(const double* x, const Pose& T) {
     normalize_rotation(r);
     return r;
 }
+
+// Sim3(update) (sim3.h:70-142); update = (omega, upsilon, sigma)
+__device__ static inline Sim3 sim3_exp(const double* u) {
+    const double* om = u;
+    const double* up = u + 3;
+    const double sigma = u[6];
+    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+    Sim3 E;
+    E.s = exp(sigma);
+    double O[9], O2[9], R[9];
+    hat_sq(om, O, O2);
+    const double eps = 0.00001;
+    double A, B, C;
+    const bool small_theta = theta < eps;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (small_theta) {
+            A = 1. / 2.;
+            B = 1. / 6.;
+        } else {
+            const double theta2 = theta * theta;
+            A = (1 - cos(theta)) / (theta2);
+            B = (theta - sin(theta)) / (theta2 * theta);
+        }
+    } else {
+        C = (E.s - 1) / sigma;
+        if (small_theta) {
+            const double sigma2 = sigma * sigma;
+            A = ((sigma - 1) * E.s + 1) / sigma2;
+            B = ((0.5 * sigma2 - sigma + 1) * E.s) / (sigma2 * sigma);
+        } else {
+            const double a = E.s * sin(theta);
+            const double b = E.s * cos(theta);
+            const double theta2 = theta * theta;
+            const double sigma2 = sigma * sigma;
+            const double c = theta2 + sigma2;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
+        }
+    }
+    rodrigues(O, O2, theta, R);
+    quat_from_matrix(R, E.q);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // t = (A * Omega + B * Omega2 + C * I) * upsilon
+        double W[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) W[j] = (A * O[3 * i + j] + B * O2[3 * i + j]) + C * (i == j ? 1.0 : 0.0);
+        double s = W[0] * up[0];
+        s += W[1] * up[1];
+        s += W[2] * up[2];
+        E.t[i] = s;
+    }
+    return E;
+}
+
+// VertexSim3Expmap::oplusImpl: Sim3(update) * T
+__device__ static inline Sim3 sim3_oplus(const double* u, const Sim3& T) { return sim3_mul(sim3_exp(u), T); }
 
 constexpr int G2O_WAVES = 4;  // both optimizers run 256-thread workgroups
 

@@ -17,8 +17,9 @@
 //   Levenberg       optimization_algorithm_levenberg.cpp:61-189, dense solver linear_solver_dense.h:104-112
 //   schedule        Optimizer.cc:1857-1916
 // The quaternion and rotation helpers, the Huber kernel, ldlt<7>, the Levenberg bookkeeping, the
-// workgroup sum and the compaction step are those of csrc/orb_g2o_math.h, shared with
-// csrc/orb_optimizer.hip; this unit holds the Sim3 state, its two edges and the schedule.
+// workgroup sum, the compaction step and the Sim3 state with its map, inverse, product and exponential are
+// those of csrc/orb_g2o_math.h, shared with the other optimizer units; this unit holds the two edges and
+// the schedule.
 //
 // Arithmetic: all f64, the TU built -ffp-contract=off; inputs are widened from f32 once, in the
 // prepare step (the batch form's camera-frame points are the float row sums of §12 first, gemm3_add of
@@ -165,90 +166,8 @@ __global__ void __launch_bounds__(S3_THREADS) k_s3_prepare(S3Args a) {
     if (tid == 0) a.n[s] = base;
 }
 
-struct Sim3 {
-    double q[4];  // x y z w
-    double t[3];
-    double s;
-};
-
-__device__ __forceinline__ void sim3_map(const Sim3& S, const double* X, double* o) {  // s * (r * xyz) + t
-    double r[3];
-    rotate(S.q, X, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = S.s * r[k] + S.t[k];
-}
-
-__device__ Sim3 sim3_inverse(const Sim3& S) {  // sim3.h:233-236
-    Sim3 I;
-    I.q[0] = -S.q[0], I.q[1] = -S.q[1], I.q[2] = -S.q[2], I.q[3] = S.q[3];
-    const double f = -1. / S.s;
-    const double v[3] = {f * S.t[0], f * S.t[1], f * S.t[2]};
-    rotate(I.q, v, I.t);
-    I.s = 1. / S.s;
-    return I;
-}
-
-// Sim3(update) * T (oplusImpl); update = (omega, upsilon, sigma)
-__device__ Sim3 oplus(const double* u, const Sim3& T) {
-    const double* om = u;
-    const double* up = u + 3;
-    const double sigma = u[6];
-    const double theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    Sim3 E;
-    E.s = exp(sigma);
-    double O[9], O2[9], R[9];
-    hat_sq(om, O, O2);
-    const double eps = 0.00001;
-    double A, B, C;
-    const bool small_theta = theta < eps;
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (small_theta) {
-            A = 1. / 2.;
-            B = 1. / 6.;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / (theta2);
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (E.s - 1) / sigma;
-        if (small_theta) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * E.s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * E.s) / (sigma2 * sigma);
-        } else {
-            const double a = E.s * sin(theta);
-            const double b = E.s * cos(theta);
-            const double theta2 = theta * theta;
-            const double sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-        }
-    }
-    rodrigues(O, O2, theta, R);
-    quat_from_matrix(R, E.q);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {  // t = (A * Omega + B * Omega2 + C * I) * upsilon
-        double W[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) W[j] = (A * O[3 * i + j] + B * O2[3 * i + j]) + C * (i == j ? 1.0 : 0.0);
-        double s = W[0] * up[0];
-        s += W[1] * up[1];
-        s += W[2] * up[2];
-        E.t[i] = s;
-    }
-    // Sim3::operator* (sim3.h:266-272)
-    Sim3 r;
-    quat_mul(E.q, T.q, r.q);
-    double rt[3];
-    rotate(E.q, T.t, rt);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r.t[k] = E.s * rt[k] + E.t[k];
-    r.s = E.s * T.s;
-    return r;
-}
+// struct Sim3, sim3_map, sim3_inverse, the product and the exponential are csrc/orb_g2o_math.h's
+__device__ __forceinline__ Sim3 oplus(const double* u, const Sim3& T) { return sim3_oplus(u, T); }
 
 // obs - cam_map(project(M.map(X))); project does not look at the depth
 __device__ __forceinline__ void edge_error(const Sim3& M, const double* K, const double* X, const double* obs,

@@ -1,6 +1,7 @@
 """Optimizer::PoseOptimization(Frame*) (reference src/Optimizer.cc:154-285, csrc/orb_optimizer.hip),
-Optimizer::OptimizeSim3 (Optimizer.cc:1721-1917, csrc/orb_sim3opt.hip) and
-Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536, csrc/orb_localba.hip) on the GPU, over the C
+Optimizer::OptimizeSim3 (Optimizer.cc:1721-1917, csrc/orb_sim3opt.hip),
+Optimizer::LocalBundleAdjustment (Optimizer.cc:287-536, csrc/orb_localba.hip) and
+Optimizer::OptimizeEssentialGraph (Optimizer.cc:1470-1719, csrc/orb_essgraph.hip) on the GPU, over the C
 ABI of ``include/orb_abi.h``.
 
 The motion-only optimisation of one frame's pose against its keypoint <-> MapPoint associations:
@@ -8,8 +9,9 @@ the whole g2o schedule (four rounds of Levenberg with the outlier classification
 runs in one launch per call, one workgroup per problem.  The Sim3 optimisation of a loop candidate
 (two optimize() calls with the pair classification between and after them) likewise, and so does
 the local bundle adjustment of a window of keyframes and points (both optimize() calls with the
-Schur complement, and both outlier classifications).  Global bundle adjustment and
-the essential graph are not part of this package.
+Schur complement, and both outlier classifications).  The essential graph of a loop
+correction is one synchronous call whose Levenberg state stays on the device.  Global
+bundle adjustment is not part of this package.
 """
 from __future__ import annotations
 
@@ -87,6 +89,44 @@ assert LOCAL_BA_INFO_DTYPE.itemsize == ctypes.sizeof(LocalBAInfo) == 104
 LOCAL_BA_MAX_FREE_KF = 64  # ORB_LBA_MAX_FREE_KF
 
 
+EG_MAX_TRIALS = 200  # ORB_EG_MAX_TRIALS
+EG_MAX_KF = 65536  # ORB_EG_MAX_KF
+EG_MAX_PROFILE_BYTES = 256 << 20  # ORB_EG_MAX_PROFILE_BYTES
+
+
+class EssentialGraphInfo(ctypes.Structure):
+    """orb_essential_graph_info_t."""
+
+    _fields_ = [("status", ctypes.c_int32), ("n_active", ctypes.c_int32), ("n_free", ctypes.c_int32),
+                ("n_edges", ctypes.c_int32), ("profile_bytes", ctypes.c_int64), ("iterations", ctypes.c_int32),
+                ("trials", ctypes.c_int32), ("refused", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("lambda_", ctypes.c_double), ("chi2_before", ctypes.c_double), ("chi2_after", ctypes.c_double),
+                ("trial_rho", ctypes.c_double * EG_MAX_TRIALS), ("trial_chi2", ctypes.c_double * EG_MAX_TRIALS),
+                ("trial_accepted", ctypes.c_uint8 * EG_MAX_TRIALS)]
+
+    def as_dict(self) -> dict:
+        n = min(self.trials, EG_MAX_TRIALS)
+        return {"status": self.status, "n_active": self.n_active, "n_free": self.n_free, "n_edges": self.n_edges,
+                "profile_bytes": self.profile_bytes, "iterations": self.iterations, "trials": self.trials,
+                "refused": self.refused, "lambda": self.lambda_, "chi2_before": self.chi2_before,
+                "chi2_after": self.chi2_after, "trial_rho": list(self.trial_rho[:n]),
+                "trial_chi2": list(self.trial_chi2[:n]), "trial_accepted": [int(v) for v in self.trial_accepted[:n]]}
+
+
+assert ctypes.sizeof(EssentialGraphInfo) == 3464
+
+
+def _sim3_table(table, flags, n):
+    """(n, 8) doubles and (n,) u8 flags, or (None, None) where the caller has no such table."""
+    if table is None:
+        return None, None
+    t = np.ascontiguousarray(table, np.float64).reshape(-1, 8)
+    f = np.ones(n, np.uint8) if flags is None else np.ascontiguousarray(flags, np.uint8).reshape(-1)
+    if len(t) != n or len(f) != n:
+        raise ValueError("a Sim3 table holds one row and one flag per keyframe")
+    return t, f
+
+
 def _sim3_13(sim3) -> np.ndarray:
     """13 floats (R row-major, t, s) from that, or from a (R, t, s) triple."""
     if isinstance(sim3, (tuple, list)) and len(sim3) == 3:
@@ -110,7 +150,8 @@ def _pose12(pose) -> np.ndarray:
 
 class Optimizer:
     """The GPU half of the reference's Optimizer: ``pose_optimization``, ``optimize_sim3``,
-    ``local_bundle_adjustment`` and their batch forms."""
+    ``local_bundle_adjustment`` and their batch forms, ``OptimizeEssentialGraph`` and
+    ``sim3_correct_points``."""
 
     def __init__(self, device: int = 0):
         self._lib = hip_lib()
@@ -317,6 +358,62 @@ class Optimizer:
             ptr(out["edge_erased"]), ptr(out["pt_bad"]), ctypes.addressof(info) if want_info else None, self.device))
         if want_info:
             out["info"] = info.as_dict()
+        return out
+
+    def OptimizeEssentialGraph(self, kf_pose, kf_fixed, edge_i, edge_j, edge_kind, kf_corrected=None,
+                               kf_has_corrected=None, kf_noncorrected=None, kf_has_noncorrected=None, pt_pos=None,
+                               pt_ref=None, pt_skip=None, n_iterations: int = 20, want_info: bool = True) -> dict:
+        """Optimizer::OptimizeEssentialGraph on the pose graph as flat arrays (host buffers,
+        synchronous).  kf_pose (n_kf, 12) (Rcw row-major, tcw) or (n_kf, 4, 4) in the
+        caller's order; kf_fixed (n_kf,) flags; kf_corrected / kf_noncorrected (n_kf, 8) doubles (q x y z
+        w, t, s) with their (n_kf,) flags (a table without flags applies to every keyframe); the edges
+        in the order the reference adds them: edge_i (vertex 0), edge_j (vertex 1), edge_kind (0 a loop
+        connection, 1 a spanning-tree, loop or covisibility edge).  pt_pos (n_pt, 3), pt_ref (n_pt,) the
+        reference keyframe's index or -1, pt_skip (n_pt,) flags of bad points, whose rows come back as
+        they went in.  Returns kf_sim3 (n_kf, 8), kf_pose (n_kf, 12) float32, kf_pose_f64, pt_pos (n_pt,
+        3) float32, pt_pos_f64 and info."""
+        kp = np.asarray(kf_pose, np.float32)
+        if kp.ndim == 3 and kp.shape[1:] == (4, 4):
+            kp = np.concatenate([kp[:, :3, :3].reshape(-1, 9), kp[:, :3, 3]], 1)
+        kp = np.ascontiguousarray(kp, np.float32).reshape(-1, 12)
+        nk = len(kp)
+        kf = np.ascontiguousarray(kf_fixed, np.uint8).reshape(-1)
+        ei = np.ascontiguousarray(edge_i, np.int32).reshape(-1)
+        ej = np.ascontiguousarray(edge_j, np.int32).reshape(-1)
+        ek = np.ascontiguousarray(edge_kind, np.uint8).reshape(-1)
+        ne = len(ei)
+        pp = np.zeros((0, 3), np.float32) if pt_pos is None else np.ascontiguousarray(pt_pos, np.float32).reshape(-1, 3)
+        npt = len(pp)
+        pr = np.zeros(0, np.int32) if pt_ref is None else np.ascontiguousarray(pt_ref, np.int32).reshape(-1)
+        ps = None if pt_skip is None else np.ascontiguousarray(pt_skip, np.uint8).reshape(-1)
+        if len(kf) != nk or len(ej) != ne or len(ek) != ne or len(pr) != npt or (ps is not None and len(ps) != npt):
+            raise ValueError("the keyframe, edge and point arrays must hold one entry per keyframe, edge and point")
+        kc, hc = _sim3_table(kf_corrected, kf_has_corrected, nk)
+        kn, hn = _sim3_table(kf_noncorrected, kf_has_noncorrected, nk)
+        out = {"kf_sim3": np.zeros((nk, 8), np.float64), "kf_pose": np.zeros((nk, 12), np.float32),
+               "kf_pose_f64": np.zeros((nk, 12), np.float64), "pt_pos": pp.copy(), "pt_pos_f64": pp.astype(np.float64)}
+        info = EssentialGraphInfo()
+        check(self._lib.orb_optimize_essential_graph(
+            nk, ptr(kp), ptr(kc), ptr(hc), ptr(kn), ptr(hn), ptr(kf), ne, ptr(ei), ptr(ej), ptr(ek), npt, ptr(pp),
+            ptr(pr), ptr(ps), int(n_iterations), ptr(out["kf_sim3"]), ptr(out["kf_pose"]), ptr(out["kf_pose_f64"]),
+            ptr(out["pt_pos"]), ptr(out["pt_pos_f64"]), ctypes.addressof(info) if want_info else None, self.device))
+        if want_info:
+            out["info"] = info.as_dict()
+        return out
+
+    def sim3_correct_points(self, pt_pos, pt_pair, sim3_from, sim3_to) -> dict:
+        """to[pair]^-1.map(from[pair].map(P)) per point (LoopClosing::CorrectLoop lines 466-495;
+        host buffers, synchronous).  pt_pos (n_pt, 3); pt_pair (n_pt,) the row of the two (n_pair, 8)
+        Sim3 tables, -1 leaves the point as it is.  Returns pt_pos (n_pt, 3) float32 and pt_pos_f64."""
+        pp = np.ascontiguousarray(pt_pos, np.float32).reshape(-1, 3)
+        pr = np.ascontiguousarray(pt_pair, np.int32).reshape(-1)
+        sf = np.ascontiguousarray(sim3_from, np.float64).reshape(-1, 8)
+        st = np.ascontiguousarray(sim3_to, np.float64).reshape(-1, 8)
+        if len(pr) != len(pp) or len(sf) != len(st):
+            raise ValueError("one pair index per point and one row of each table per pair")
+        out = {"pt_pos": np.zeros((len(pp), 3), np.float32), "pt_pos_f64": np.zeros((len(pp), 3), np.float64)}
+        check(self._lib.orb_sim3_correct_points(len(pp), ptr(pp), ptr(pr), len(sf), ptr(sf), ptr(st), ptr(out["pt_pos"]),
+                                                ptr(out["pt_pos_f64"]), self.device))
         return out
 
     def local_bundle_adjustment_batch_device(self, kf_off, pt_off, edge_off, d_kf_pose, d_kf_K, d_kf_fixed, d_pt_pos,
