@@ -1254,6 +1254,95 @@ int orb_sim3_correct_points(int n_pt, const float* pt_pos, const int32_t* pt_pai
                             const double* sim3_from, const double* sim3_to, float* pt_pos_out,
                             double* pt_pos_out_f64, int device);
 
+/* The local map of a tracked frame and a keyframe's covisibility (csrc/orb_localmapref.hip, DESIGN.md
+ * §23): the counting, thresholding, ordering and de-duplicating of Tracking::UpdateReference and
+ * KeyFrame::UpdateConnections over flat tables.  Integer only: parity is exact.  The caller owns the
+ * map, hands the tables over with every call (the calls keep nothing) and mutates its map from what
+ * comes back.  std::map<KeyFrame*, ...>'s pointer order is ASCENDING KEYFRAME INDEX here: the caller's
+ * numbering decides ties for the reference keyframe, who is inside the limit of 80 and the order of
+ * the local points.
+ *   keyframes  n_kf (<= ORB_LM_MAX_KF): kf_bad n_kf u8 (isBad()); kf_mp_off n_kf + 1 offsets into kf_mp
+ *              (n_kf_mp entries in all): GetMapPointMatches() per keypoint, a point index or -1 for
+ *              NULL, at most ORB_LM_MAX_ROW per keyframe; kf_cov n_kf x 10:
+ *              GetBestCovisibilityKeyFrames(10) in its order, the first -1 ends a row
+ *   points     n_pt: pt_bad n_pt u8; pt_obs_off n_pt + 1 offsets into pt_obs_kf (n_obs entries in all):
+ *              the keys of mObservations, each row strictly ascending
+ * ORB_EINVAL: an index out of range anywhere, an offset table that is not monotone or leaves its
+ * array, an observation row that is not strictly ascending.  ORB_ENOTSUP: more than ORB_LM_MAX_KF
+ * keyframes, a row above ORB_LM_MAX_ROW, more than 65535 frames / keyframes in a batch, or scratch for
+ * a single frame / keyframe above ORB_LM_MAX_SCRATCH_BYTES (decided from the sizes alone). */
+#define ORB_LM_MAX_KF 65536
+#define ORB_LM_MAX_ROW 8192
+#define ORB_LM_MAX_SCRATCH_BYTES (256ull << 20)
+typedef struct {
+    const uint8_t* kf_bad;
+    const int32_t* kf_mp_off;
+    const int32_t* kf_mp;
+    const int32_t* kf_cov;
+    const uint8_t* pt_bad;
+    const int32_t* pt_obs_off;
+    const int32_t* pt_obs_kf;
+    int32_t n_kf, n_pt, n_kf_mp, n_obs;
+} orb_local_map_tables_t;
+typedef struct {
+    int32_t status;      /* ORB_OK, or why the frame was refused (counts 0, ref_kf -1; ORB_ERANGE: the counts needed) */
+    int32_t n_voted;     /* voted keyframes that are not bad: the list before the neighbour step      */
+    int32_t n_local_kf;  /* mvpLocalKeyFrames.size()                                                   */
+    int32_t ref_kf;      /* mpReferenceKF: the first keyframe with the strict maximum, -1: none voted  */
+    int32_t ref_votes;
+    int32_t n_local_pt;  /* mvpLocalMapPoints.size()                                                   */
+    int32_t n_cleared;   /* bad points of the frame set to NULL (Tracking.cc:821)                      */
+} orb_local_map_info_t;
+/* Tracking::UpdateReferenceKeyFrames (Tracking.cc:804-879), UpdateReferencePoints (778-801) and the
+ * "already matched" pass of SearchReferencePointsInFrustum (718-734) for one frame on host buffers,
+ * synchronous.  f_mp n entries (n <= ORB_LM_MAX_ROW): mCurrentFrame.mvpMapPoints, a point index or -1.
+ * Outputs: f_mp_out n (bad points -1); local_kf cap_kf (mvpLocalKeyFrames: the voted keyframes in
+ * ascending index, then the neighbours in the order they were appended); local_pt cap_pt
+ * (mvpLocalMapPoints in order); local_pt_seen cap_pt u8 (1: the frame already holds the point, i.e.
+ * mnLastFrameSeen == mnId at line 744: pass !seen as `usable` to orb_frame_is_in_frustum and
+ * orb_search_by_projection_local); kf_votes n_kf (keyframeCounter, 0 where absent, bad keyframes
+ * included; may be NULL); info.  ORB_ERANGE: a capacity too small; info holds the counts needed and
+ * nothing else is written.  A frame that is empty or whose points are all bad: ORB_OK, empty lists,
+ * ref_kf -1. */
+int orb_local_map_reference(const orb_local_map_tables_t* map, int n, const int32_t* f_mp, int cap_kf, int cap_pt,
+                            int32_t* f_mp_out, int32_t* local_kf, int32_t* local_pt, uint8_t* local_pt_seen,
+                            int32_t* kf_votes, orb_local_map_info_t* info, int device);
+/* B (<= 65535) frames on device arrays: d_map is a host struct of device pointers; d_f_mp B x cap with
+ * d_counts[b] entries used (what lies past them is neither read nor written); outputs strided by cap,
+ * cap_kf, cap_pt and n_kf.  A frame that the host form would refuse is left unwritten and reports its
+ * status in d_info[b] (the call itself returns ORB_OK); a bad table refuses every frame.  Each
+ * frame's result is the host form's bit for bit.  Frames run in chunks so that scratch stays under
+ * ORB_LM_MAX_SCRATCH_BYTES.  Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_local_map_reference_batch_device(const orb_local_map_tables_t* d_map, int B, int cap, const int32_t* d_f_mp,
+                                         const int32_t* d_counts, int cap_kf, int cap_pt, int32_t* d_f_mp_out,
+                                         int32_t* d_local_kf, int32_t* d_local_pt, uint8_t* d_local_pt_seen,
+                                         int32_t* d_kf_votes, orb_local_map_info_t* d_info, void* stream);
+typedef struct {
+    int32_t status;
+    int32_t n_conn;     /* KFcounter.size()                                                            */
+    int32_t n_ord;      /* mvpOrderedConnectedKeyFrames.size()                                         */
+    int32_t unchanged;  /* 1: KFcounter was empty, the early return of KeyFrame.cc:365: write nothing back */
+} orb_update_connections_info_t;
+/* KeyFrame::UpdateConnections (KeyFrame.cc:332-411) for K (<= 65535) keyframes kf_idx, each on its own
+ * (the function reads observations only).  Votes over the keyframe's non-NULL, non-bad points, itself
+ * excluded, bad keyframes counted (the reference does not test them here); threshold >= 15, else the
+ * first strict maximum alone.  Outputs, strided by cap_conn / cap_ord: conn_kf / conn_w
+ * (mConnectedKeyFrameWeights in ascending index), ord_kf / ord_w (mvpOrderedConnectedKeyFrames /
+ * mvOrderedWeights: weight descending, index descending among equal weights), info K records.  The
+ * reverse AddConnection calls, the mbFirstConnection / mpParent step (ord_kf[0]) and the map mutation
+ * stay with the caller.  Host form: synchronous; every record is returned, the rows
+ * of the keyframes whose status is ORB_OK are written, and the first other status is the return
+ * value.  ORB_ERANGE per keyframe: a capacity too small, counts in the record, its rows unwritten. */
+int orb_keyframe_update_connections(const orb_local_map_tables_t* map, int K, const int32_t* kf_idx, int cap_conn,
+                                    int cap_ord, int32_t* conn_kf, int32_t* conn_w, int32_t* ord_kf, int32_t* ord_w,
+                                    orb_update_connections_info_t* info, int device);
+/* The same on device arrays (d_map: a host struct of device pointers); statuses in d_info, the call
+ * returns ORB_OK.  Asynchronous on `stream`; scratch is stream-ordered. */
+int orb_keyframe_update_connections_batch_device(const orb_local_map_tables_t* d_map, int K, const int32_t* d_kf_idx,
+                                                 int cap_conn, int cap_ord, int32_t* d_conn_kf, int32_t* d_conn_w,
+                                                 int32_t* d_ord_kf, int32_t* d_ord_w,
+                                                 orb_update_connections_info_t* d_info, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------- */
 /* Per-stage HIP-event timing of the extraction kernels: when enabled, every
  * orb_extract_batch_device records an event pair around each stage on its launch stream.

@@ -66,6 +66,11 @@ int orb_debug_fill_pyramid(orb_extractor_t* h, int value);
  * a wrong score from a wrong order (device sync). */
 int orb_debug_kfdb_last_query(orb_keyframe_db_t* db, int q, int32_t* common, uint32_t* first_word, uint32_t* seq,
                               uint8_t* scored, double* score, int cap);
+/* The byte cap under which orb_local_map_reference* and orb_keyframe_update_connections* keep their
+ * per-chunk scratch, for the calls that follow in this process (0: ORB_LM_MAX_SCRATCH_BYTES).  A small
+ * cap makes a small batch run in several chunks, and a cap below one frame's scratch shows the
+ * ORB_ENOTSUP answer; results are identical (tests/test_gpu_local_map.py). */
+int orb_debug_set_local_map_scratch_cap(size_t bytes);
 
 #ifdef __cplusplus
 }

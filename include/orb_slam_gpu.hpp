@@ -1092,6 +1092,78 @@ public:
     }
 };
 
+// The counting of Tracking::UpdateReference (Tracking.cc:768-879, with lines 718-734) and
+// KeyFrame::UpdateConnections (KeyFrame.cc:332-411) over the map as flat tables (orb_abi.h states them;
+// INTEGRATION.md shows the flattening).  std::map's pointer order is ascending keyframe index.  The map
+// and its mutation stay with the caller.
+class LocalMap {
+public:
+    struct Tables {
+        std::vector<uint8_t> kfBad;                  // isBad() per keyframe
+        std::vector<int32_t> kfMpOff, kfMp;          // GetMapPointMatches() per keypoint: a point index or -1
+        std::vector<int32_t> kfCov;                  // 10 per keyframe: GetBestCovisibilityKeyFrames(10), then -1
+        std::vector<uint8_t> ptBad;                  // isBad() per point
+        std::vector<int32_t> ptObsOff, ptObsKf;      // the keys of mObservations, ascending per point
+        orb_local_map_tables_t abi() const {
+            if (kfMpOff.size() != kfBad.size() + 1 || ptObsOff.size() != ptBad.size() + 1 || kfCov.size() != kfBad.size() * 10)
+                throw std::invalid_argument("LocalMap::Tables: array sizes disagree");
+            orb_local_map_tables_t t;
+            t.kf_bad = kfBad.data(), t.kf_mp_off = kfMpOff.data(), t.kf_mp = kfMp.data(), t.kf_cov = kfCov.data();
+            t.pt_bad = ptBad.data(), t.pt_obs_off = ptObsOff.data(), t.pt_obs_kf = ptObsKf.data();
+            t.n_kf = (int32_t)kfBad.size(), t.n_pt = (int32_t)ptBad.size();
+            t.n_kf_mp = (int32_t)kfMp.size(), t.n_obs = (int32_t)ptObsKf.size();
+            return t;
+        }
+    };
+    struct Reference {
+        std::vector<int32_t> vpMapPoints;      // mCurrentFrame.mvpMapPoints after line 821
+        std::vector<int32_t> vpLocalKeyFrames; // mvpLocalKeyFrames
+        std::vector<int32_t> vpLocalMapPoints; // mvpLocalMapPoints
+        std::vector<uint8_t> vbSeen;           // 1: mnLastFrameSeen == mnId at line 744 (pass !seen as usable)
+        orb_local_map_info_t info;             // ref_kf is mpReferenceKF
+    };
+    // UpdateReference for the frame whose mvpMapPoints is vpMapPoints (point indices or -1).
+    static void UpdateReference(const Tables& T, const std::vector<int32_t>& vpMapPoints, Reference& R, int device = 0) {
+        const orb_local_map_tables_t t = T.abi();
+        const size_t n = vpMapPoints.size();
+        R.vpMapPoints.assign(n, -1);
+        R.vpLocalKeyFrames.assign(T.kfBad.size(), -1);
+        R.vpLocalMapPoints.assign(T.ptBad.size(), -1);
+        R.vbSeen.assign(T.ptBad.size(), 0);
+        orb_check(orb_local_map_reference(&t, (int)n, vpMapPoints.data(), t.n_kf, t.n_pt, R.vpMapPoints.data(),
+                                          R.vpLocalKeyFrames.data(), R.vpLocalMapPoints.data(), R.vbSeen.data(), nullptr,
+                                          &R.info, device));
+        R.vpLocalKeyFrames.resize((size_t)R.info.n_local_kf);
+        R.vpLocalMapPoints.resize((size_t)R.info.n_local_pt);
+        R.vbSeen.resize((size_t)R.info.n_local_pt);
+    }
+
+    struct Connections {
+        std::vector<int32_t> connKF, connW;  // mConnectedKeyFrameWeights, ascending index
+        std::vector<int32_t> ordKF, ordW;    // mvpOrderedConnectedKeyFrames / mvOrderedWeights
+        bool unchanged;                      // the early return of line 365: write nothing back
+    };
+    // UpdateConnections of the keyframes vKF, each on its own.
+    static void UpdateConnections(const Tables& T, const std::vector<int32_t>& vKF, std::vector<Connections>& R,
+                                  int device = 0) {
+        const orb_local_map_tables_t t = T.abi();
+        const size_t K = vKF.size(), cap = T.kfBad.size();
+        std::vector<int32_t> ck(K * cap), cw(K * cap), ok(K * cap), ow(K * cap);
+        std::vector<orb_update_connections_info_t> info(K);
+        orb_check(orb_keyframe_update_connections(&t, (int)K, vKF.data(), (int)cap, (int)cap, ck.data(), cw.data(), ok.data(),
+                                                  ow.data(), info.data(), device));
+        R.assign(K, Connections());
+        for (size_t q = 0; q < K; ++q) {
+            const size_t nc = (size_t)info[q].n_conn, no = (size_t)info[q].n_ord;
+            R[q].connKF.assign(ck.begin() + q * cap, ck.begin() + q * cap + nc);
+            R[q].connW.assign(cw.begin() + q * cap, cw.begin() + q * cap + nc);
+            R[q].ordKF.assign(ok.begin() + q * cap, ok.begin() + q * cap + no);
+            R[q].ordW.assign(ow.begin() + q * cap, ow.begin() + q * cap + no);
+            R[q].unchanged = info[q].unchanged != 0;
+        }
+    }
+};
+
 }  // namespace gpu
 }  // namespace ORB_SLAM
 

@@ -17,6 +17,7 @@ from .matcher import Frame, ORBmatcher
 from .synth import SYN_FLAT, SYN_LOWTEX, SYN_NOISE, SYN_SCENE, synth_special, synth_stream
 from .database import KeyFrameDatabase
 from .local_mapping import LocalMapping
+from .local_map import LocalMap, MapTables
 from .initializer import Initializer, InitializerRansac, initializer_minimal_sets
 from .optimizer import Optimizer
 from .solvers import (PnPConsensus, PnPRansac, Sim3Consensus, Sim3Ransac, pnp_minimal_sets, pnp_ransac_parameters,
@@ -33,6 +34,8 @@ __all__ = [
     "initializer_minimal_sets",
     "Optimizer",
     "LocalMapping",
+    "LocalMap",
+    "MapTables",
     "PnPConsensus",
     "Sim3Consensus",
     "Sim3Ransac",

@@ -249,7 +249,12 @@ HIP_SIGNATURES = {
     "orb_sim3_from_pose": (None, [_vp, _vp]),
     "orb_sim3_to_pose": (None, [_vp, _vp, _vp]),
     "orb_sim3_correct_points": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
-    "orb_debug_kfdb_last_query": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orb_local_map_reference": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orb_local_map_reference_batch_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_keyframe_update_connections": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orb_keyframe_update_connections_batch_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orb_debug_set_local_map_scratch_cap": (_i, [ctypes.c_size_t]),
+    "orb_debug_kfdb_last_query":(_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
     "orb_profile_enable": (_i, [_vp, _i]),
     "orb_profile_enable_stages": (_i, [_vp, ctypes.c_uint]),
     "orb_extract_set_phases": (_i, [_vp, ctypes.c_uint]),
